@@ -2,8 +2,14 @@
 """Benchmark of the hot path: ECBS (w = 1.3) low-level searches on 32x32_obst204-shaped instances, batched on MI355X.
 
 Contract (one JSON line on rank 0):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline needs: it generates and preloads the K + W batches, solves the W warm-up steps, times
+the K steps, writes --dump-outputs DIR (what the last timed step delivered: per-instance results and path lengths, the
+schedules of a fixed sample of its instances; see dump_outputs) and prints the result line.  Everything else in the
+line (one_call_per_step, cpu_baseline*, parity_whole_first_batch, by_workload, host_threads_sweep, the sharded
+conflict tree at N > 1) is measured with --full only; --legs / --sync-steps / --no-cpu-baseline narrow it.
 
 A "step" = one batch of B fresh synthetic agents10 instances per GPU (BASELINE.json configs[1] shape) solved to
 completion by the host conflict-tree driver, every low-level search of which runs in the HIP kernel (through the C-ABI).
@@ -48,6 +54,7 @@ Extra objects in the same line:
                  64-bit digest of its schedule (parity_whole_first_batch).
 """
 import argparse
+import concurrent.futures
 import json
 import os
 import sys
@@ -59,9 +66,9 @@ if ROOT not in sys.path:
 
 # Every host worker thread keeps up to two resident kernels (front + heavy workgroups) on streams of their own, and each
 # needs its own hardware queue (the ROCm default of 4 makes streams share queues and serialise their kernels — fatal for
-# resident kernels, which only end when their host thread is done; measured on this box, scripts/micro/hw_queues.hip: 64
-# streams hold 64 resident kernels at once with GPU_MAX_HW_QUEUES=64).  Must be set before the HIP runtime initialises.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "64")
+# resident kernels, which only end when their host thread is done; scripts/micro/hw_queues.hip).  Importing the package
+# sets GPU_MAX_HW_QUEUES; it must come before the HIP runtime initialises (torch below).
+import libmultirobotplanning_amd  # noqa: E402,F401
 
 ALGO_BYTES_PER_EXPANSION = 128
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s
@@ -129,6 +136,45 @@ def cpu_leg(oracle, ia, ra, cap, n_sample, hl):
             "parity_fields": "status, cost, makespan, highLevelExpanded, lowLevelExpanded, schedule digest"}
 
 
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: all files together
+DUMP_PATHS_SAMPLE = 1024       # instances whose schedules are written out in full
+DUMP_SEED = 20241016           # fixes which instances a sample takes
+
+
+def dump_outputs(out_dir, ra, pxy, solved_status, prefix=""):
+    """--dump-outputs: what the caller of the timed path received for the last timed batch, as .npy files in float64
+    (per-instance result fields; schedule_digest as two exact 32-bit halves) and float32 (path_len [n][agents] and the
+    schedules [m][agents][path_cap][2] of a fixed seeded sample of m instances, paths_sample_index naming them; entries
+    past an agent's path length and the schedules of unsolved instances are -1).  When the per-instance arrays would
+    not fit the budget either, they cover a seeded sample as well (instance_index)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n, na = ra["path_len"].shape
+    path_cap = pxy.shape[2]
+    rng = np.random.default_rng(DUMP_SEED)
+    m = min(n, DUMP_PATHS_SAMPLE, max(1, (DUMP_BUDGET_BYTES // 4) // (na * path_cap * 8 + 8)))
+    pick = np.sort(rng.choice(n, m, replace=False))
+    plen = np.minimum(ra["path_len"][pick], path_cap)
+    paths = pxy[pick].astype(np.float32)
+    paths[np.arange(path_cap)[None, None, :] >= plen[:, :, None]] = -1
+    paths[ra["status"][pick] != solved_status] = -1
+    files = {"paths_sample": paths, "paths_sample_index": pick.astype(np.float64)}
+    left = DUMP_BUDGET_BYTES - (1 << 16) - sum(a.nbytes for a in files.values())  # (64 KB for the .npy headers)
+    per_instance = 8 * 8 + 4 * na
+    rows = slice(None)
+    if n * per_instance > left:
+        rows = np.sort(rng.choice(n, left // (per_instance + 8), replace=False))
+        files["instance_index"] = rows.astype(np.float64)
+    for k in ("status", "cost", "makespan", "hl_expanded", "ll_expanded", "ll_searches"):
+        files[k] = ra[k][rows].astype(np.float64)
+    digest = ra["schedule_digest"][rows].astype(np.uint64)
+    files["schedule_digest_hi"] = (digest >> np.uint64(32)).astype(np.float64)
+    files["schedule_digest_lo"] = (digest & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    files["path_len"] = ra["path_len"][rows].astype(np.float32)
+    for k, a in files.items():
+        np.save(os.path.join(out_dir, prefix + k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -142,18 +188,32 @@ def main():
     ap.add_argument("--cpu-sample", type=int, default=4096, help="headline instances timed on the CPU port (rank 0)")
     ap.add_argument("--path-cap", type=int, default=128, help="states per agent the caller's schedule buffers hold in the "
                                                                "headline region (a longer path would be reported, not hidden)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baselines and the parity check of the first "
+                         "timed batch, one_call_per_step, the other workloads (by_workload), the host-thread sweep and, at "
+                         "N > 1, the sharded conflict tree.  Without it a run sets up, warms up, times the K steps, writes "
+                         "--dump-outputs and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them delivered (per-instance results, path lengths, "
+                         "a fixed sample of the schedules) to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU legs")
     ap.add_argument("--no-stream", action="store_true",
                     help="one solver call per step with a barrier between steps (the default hands the K timed steps to the "
                          "solver as one stream of batches, mrp_hl_solver_solve_stream)")
-    ap.add_argument("--sync-steps", type=int, default=2,
-                    help="after the timed region: that many of its steps again, one call each (reported as one_call_per_step)")
-    ap.add_argument("--legs", default="auto", help="'auto' (all at N=1, none otherwise), 'none', or a comma list of "
-                                                   "agents50,agents100,shipped,sipp50,sipp100,sipp200")
+    ap.add_argument("--sync-steps", type=int, default=None,
+                    help="after the timed region: that many of its steps again, one call each (reported as one_call_per_step; "
+                         "default 2 with --full, 0 without)")
+    ap.add_argument("--legs", default=None, help="'auto' (all at N=1, none otherwise; the default with --full), 'none' (the "
+                                                 "default without), or a comma list of "
+                                                 "agents50,agents100,shipped,sipp50,sipp100,sipp200")
     ap.add_argument("--max-ll-expansions", type=int, default=50000,
                     help="harness cap per instance of the headline workload (the reference has none and never returns "
                          "on infeasible inputs); applied identically to the GPU path and to the CPU baseline")
     args = ap.parse_args()
+    if args.sync_steps is None:
+        args.sync_steps = 2 if args.full else 0
+    if args.legs is None:
+        args.legs = "auto" if args.full else "none"
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -192,10 +252,15 @@ def main():
         return hl.generate_instances(sharding.seed_base(args.agents, rank, K + W, step_idx, B), B, 32, 32, 204, args.agents)
 
     t_gen = time.perf_counter()
-    batches = [batch(i) for i in range(K + W)]
     # marshal the batches and upload their static maps to HBM before the timed region (the reference constructs its
-    # Environment before it starts its Timer, example/ecbs.cpp:576-582); the timed region is the searches only
-    prepared = [solver.prepare(b, want_paths=True, path_cap=args.path_cap) for b in batches]
+    # Environment before it starts its Timer, example/ecbs.cpp:576-582); the timed region is the searches only.  One
+    # thread generates the next batches while this one preloads (both native calls release the GIL).
+    with concurrent.futures.ThreadPoolExecutor(1) as pool:
+        batches = []
+        prepared = []
+        for b in pool.map(batch, range(K + W)):
+            batches.append(b)
+            prepared.append(solver.prepare(b, want_paths=True, path_cap=args.path_cap))
     t_gen = time.perf_counter() - t_gen
 
     def barrier():
@@ -231,6 +296,10 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     lls = solver.ll_stats()
+    if args.dump_outputs and K > 0:
+        last = prepared[W + K - 1]
+        dump_outputs(args.dump_outputs, solver.result_arrays(last), last["pxy"], hl.SOLVED,
+                     prefix="rank%d_" % rank if world > 1 else "")
     # the same steps again, one solver call each (a barrier between steps): what the stream is worth
     sync_ref = None
     if stream and args.sync_steps > 0:
@@ -363,7 +432,7 @@ def main():
                       "heavy_workgroups_busy_fraction": lls["heavy_busy_ms"] / max(lls["heavy_busy_ms"] + lls["heavy_idle_ms"], 1e-9),
                       "tickets_per_step": int(rounds_total // max(K, 1))},
         }
-        do_cpu = not args.no_cpu_baseline and world == 1  # the CPU legs run at N=1 only (rank 0)
+        do_cpu = args.full and not args.no_cpu_baseline and world == 1  # the CPU legs run at N=1 only (rank 0)
         oracle = None
         if do_cpu:
             import oracle

@@ -10,8 +10,8 @@
 //   Location    { int x, y; }                                                       (ecbs.cpp:216-230)
 //   Constraints { set<VertexConstraint{time,x,y}> vertexConstraints; set<EdgeConstraint{time,x1,y1,x2,y2}> edgeConstraints; }
 //                                                                                   (ecbs.cpp:108-214)
-// tests/test_integration_adapter.py compiles this header against the reference's own planresult.hpp / neighbor.hpp and
-// links libmrp_ll.so (in the build container, where /root/reference exists).
+// tests/test_integration_adapter.py compiles this header against the oracle's restatement of planresult.hpp /
+// neighbor.hpp (and against the library's own headers when MRP_REFERENCE_INCLUDE names them) and links libmrp_ll.so.
 #pragma once
 #include <mrp_ll.h>
 

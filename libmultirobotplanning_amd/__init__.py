@@ -10,8 +10,11 @@ The product path never imports ``oracle`` and has no CPU fallback.
 """
 import os as _os
 
-# one hardware queue per host worker stream (ROCm default: 4); only effective if set before HIP initialises
-_os.environ.setdefault("GPU_MAX_HW_QUEUES", "64")
+# one hardware queue per host worker stream (ROCm default: 4); only effective if set before HIP initialises.  32 covers
+# the sixteen resident kernels of eight engines and the runtime's own streams; a smaller inherited value is raised to it
+_q = _os.environ.get("GPU_MAX_HW_QUEUES", "")
+if not _q.isdigit() or int(_q) < 32:
+    _os.environ["GPU_MAX_HW_QUEUES"] = "32"
 
 from . import _build  # noqa: F401,E402
 

@@ -1005,7 +1005,7 @@ int mrp_hl_solver_create(int32_t device, int32_t nThreads, const mrp_ll_options*
   nThreads = std::min(nThreads, maxEngines);
   // One HIP stream (= one resident kernel) per worker: each needs its own hardware queue, the ROCm default is 4.  Only
   // effective if the HIP runtime has not been initialised yet in this process; never overrides the caller.
-  (void)setenv("GPU_MAX_HW_QUEUES", "64", 0);
+  (void)setenv("GPU_MAX_HW_QUEUES", "32", 0);
   auto* s = new mrp_hl_solver();
   s->device = device;
   s->nWorkers = nWorkers;

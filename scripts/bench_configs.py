@@ -2,7 +2,7 @@
 import os, sys, time, json
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "64")
+os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 # a CBS session is ONE resident kernel per engine (no heavy workgroups), so sixteen engines stay below the ~20 hardware
 # queues at which the device starts time-slicing; with these tiny searches the step is host-bound and
 # sixteen separate rings beat eight shared ones (scripts/r4_run29.sh: +2 / +16 / +13 / +37 % at 4 / 6 / 8 / 10 agents)

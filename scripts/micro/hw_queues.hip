@@ -1,5 +1,5 @@
 // How many HIP streams can hold a resident (never-ending) kernel at the same time?  Streams that share a hardware queue
-// serialise their kernels, which is fatal for resident kernels.  Usage: GPU_MAX_HW_QUEUES=64 ./hw_queues 48
+// serialise their kernels, which is fatal for resident kernels.  Usage: GPU_MAX_HW_QUEUES=32 ./hw_queues 24
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstdio>

@@ -2,7 +2,7 @@
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "64")
+os.environ.setdefault("GPU_MAX_HW_QUEUES", "32")
 from libmultirobotplanning_amd import hl
 ag, nb, cap, k = (int(x) for x in sys.argv[1:5])
 s = hl.BatchSolver(device=0, n_threads=16)

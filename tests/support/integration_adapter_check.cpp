@@ -1,7 +1,7 @@
-// TEST INFRASTRUCTURE (tests/test_integration_adapter.py, build container only): include/gpu_low_level.hpp — the binding
+// TEST INFRASTRUCTURE (tests/test_integration_adapter.py): include/gpu_low_level.hpp — the binding
 // INTEGRATION.md §1 shows — instantiated over types with the member names of example/ecbs.cpp's State / Action /
-// Location / Constraints (declared here: the example's own definitions sit in a .cpp that needs Boost), against the
-// REFERENCE's planresult.hpp and neighbor.hpp, and linked with libmrp_ll.so.  Without a GPU the engine refuses to start
+// Location / Constraints (declared here: the example's own definitions sit in a .cpp that needs Boost), against a
+// planresult.hpp and neighbor.hpp (the oracle's restatement, or the library's own headers), and linked with libmrp_ll.so.  Without a GPU the engine refuses to start
 // (MRP_LL_E_DEVICE): that, and the build itself, is what the check is about; with one it runs a search on a 3 x 3 map.
 #include <cstdio>
 #include <set>
@@ -33,7 +33,7 @@ struct Constraints {
 };
 typedef mrp::GpuLowLevelSearch<State, Action, Location, Constraints> LowLevelSearch_t;
 template class mrp::GpuLowLevelSearch<State, Action, Location, Constraints>;  // every member is compiled
-typedef libMultiRobotPlanning::Neighbor<State, Action, int> Neighbor_t;       // (the reference's neighbor.hpp parses too)
+typedef libMultiRobotPlanning::Neighbor<State, Action, int> Neighbor_t;       // (neighbor.hpp parses too)
 
 int main() {
   mrp_ll_ctx* ctx = nullptr;
