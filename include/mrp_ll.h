@@ -51,14 +51,33 @@ extern "C" {
                            /* jobs, not both                                                                         */
 
 #define MRP_LL_ASTAR_TA 3  /* a_star.hpp AStar::search over the Environment of example/cbs_ta.cpp:283-372 — the low level of */
-                           /* the task-assignment callers (cbs_ta.hpp:106-109,155-158,196-199; ecbs_ta's Environment is the */
-                           /* same): optional goal (MRP_LL_JOB_NO_GOAL), h = an uploaded shortest-path table               */
+                           /* CBS with task assignment ONLY (cbs_ta.hpp:106-109,155-158,196-199; ecbs_ta.hpp runs          */
+                           /* AStarEpsilon over the same Environment: MRP_LL_ASTAR_EPS_TA below): optional goal            */
+                           /* (MRP_LL_JOB_NO_GOAL), h = an uploaded shortest-path table                                    */
                            /* (mrp_ll_upload_heuristic), Wait costs 0 at the goal, so g != time and decrease-key is live.  */
                            /* Two tiers, like the other searches: the LDS tier (maps up to 32 x 32, at most 64 vertex and  */
                            /* 64 edge constraints, time steps <= 61, f <= 254, 1023 open nodes) and, for everything beyond */
                            /* it, the arena tier (any map the context accepts, any number of constraints; limits:           */
                            /* mrp_ll_options.arena_nodes / max_horizon — MRP_LL_CAP_NODES / MRP_LL_CAP_HORIZON — and as many */
                            /* time steps as arena_nodes x 4 status words hold: 512 on a 32 x 32 map by default).            */
+
+#define MRP_LL_ASTAR_EPS_TA 4 /* a_star_epsilon.hpp AStarEpsilon::search over the Environment of example/ecbs_ta.cpp:283-445 */
+                           /* — the low level of ECBS with task assignment (ecbs_ta.hpp:498-499; calls :126-128, :278, :321). */
+                           /* Goal, heuristic_id and MRP_LL_JOB_NO_GOAL as for MRP_LL_ASTAR_TA; w, agent_idx, n_agents,        */
+                           /* path_len and path_xy (the shipped focal context) as for MRP_LL_ASTAR_EPS.  The focal heuristics   */
+                           /* look the other agents up at the successor's TIME (g != time here).  A state found again with a  */
+                           /* smaller g is re-keyed in the open list and, if it already sits in the focal list, keeps its      */
+                           /* place there with the new key (a_star_epsilon.hpp:249-269), exactly as the reference's heaps do.   */
+                           /* Rejected (MRP_LL_BAD_JOB): initial_cost != 0, path_ids, MRP_LL_JOB_ROOT_CHAIN, _HEAVY,           */
+                           /* _STORE_RESULT.  Runs in batches and in mixed sessions (mrp_ll_session_begin); the one-algorithm  */
+                           /* sessions and mrp_ll_session_occupancy answer MRP_LL_E_INVALID for it.                          */
+                           /* One tier, the arena (result.tier == 1): any map the context accepts, any number of              */
+                           /* constraints, any number of context agents.  Limits, with B = 40 * arena_nodes + 48 bytes:       */
+                           /*   time steps  min(max_horizon, B / (8 * dimx * dimy))            -> MRP_LL_CAP_HORIZON          */
+                           /*   nodes       (B - 4 * time steps * dimx * dimy - 64) / 48       -> MRP_LL_CAP_NODES            */
+                           /*   g <= 1023, f <= 2045 (MRP_LL_CAP_HORIZON), focalH <= 2047 (MRP_LL_CAP_FOCAL)                  */
+                           /* By default (arena_nodes 131072, max_horizon 512): 512 time steps and 65 534 nodes on a          */
+                           /* 32 x 32 map, 284 and 54 698 on 48 x 48, 160 and 54 613 on 64 x 64.                              */
 
 /* ---- per-job status (mrp_ll_result.status) ----------------------------------------------------------------- */
 #define MRP_LL_OK 0             /* search() returned true                                                    */

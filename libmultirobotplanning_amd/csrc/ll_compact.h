@@ -861,7 +861,8 @@ WV_ENTRY int32_t compactSearch(Lds window) {
 
 // ---- the low level of the task-assignment callers ----------------------------------------------
 // AStar::search (a_star.hpp:63-161) over the Environment of example/cbs_ta.cpp:283-372,483-496 (cbs_ta.hpp:106-109,
-// 155-158,196-199; ecbs_ta's low level shares the Environment):
+// 155-158,196-199).  CBS-TA only: ecbs_ta.hpp:498-499 runs AStarEpsilon over the same Environment, which is
+// MRP_LL_ASTAR_EPS_TA (ll_kernel.hip runJobTaEps), not this search:
 //   * the task (goal) is optional: without one h = 0, every cell is a goal cell, and the search may end as soon as
 //     time > the time of the agent's LAST vertex constraint of any cell (setLowLevelContext :283-303, isSolution :313-319);
 //   * h = shortest-path distance to the task's cell from an uploaded table (shortest_path_heuristic.hpp:56-60);

@@ -32,7 +32,7 @@ constexpr uint32_t kHeartbeatWord = 32;                           // ring_head[3
 // status codes mirror include/mrp_ll.h
 enum : int32_t { ST_OK = 0, ST_NO_SOLUTION = 1, ST_CAP_EXP = 2, ST_CAP_NODES = 3, ST_CAP_HORIZON = 4, ST_BAD = 5 };
 
-struct DevJob {            // 96 bytes, 16-byte aligned
+struct DevJob {            // 112 bytes, 16-byte aligned
   uint32_t map_word_off;   // offset (uint32 words) of the obstacle bitmap inside the maps buffer
   uint32_t dimx, dimy;
   uint32_t words_per_row;  // ceil(dimx*dimy / 32)
@@ -52,6 +52,9 @@ struct DevJob {            // 96 bytes, 16-byte aligned
   uint32_t n_ctx;          // agents in that list
   uint32_t store_out_id;   // kNoStoreSlot, or the path-store slot that also receives the result path
   uint32_t reserved;
+  uint32_t heur_off;       // MRP_LL_ASTAR_EPS_TA: word offset of the goal's heuristic table in the maps buffer (path_off is
+                           // taken by its focal path table; MRP_LL_ASTAR_TA keeps the table's offset in path_off)
+  uint32_t pad_[3];
 };
 constexpr uint32_t kNoStoreSlot = 0xFFFFFFFFu;
 constexpr uint32_t kCtxById = 1u;
@@ -87,8 +90,9 @@ constexpr uint32_t kChainRows = 64;                                // rows of th
 // (n_vc = room per record of this job: the longest list among its records, as a power of two >= 4).
 // n_ctx = the job's epoch (1..255).  One job per table in flight.  The workgroup finds the start interval itself
 // (findSafeInterval, sipp.hpp:286-296) — the host's copy of the table may be behind the device's (kSippCommit).
-constexpr uint32_t kTaNoGoal = 16u;                                // MRP_LL_ASTAR_TA: ctx_flags bit 4: the agent has no task; path_off =
-                                                                   // word offset of the goal's heuristic table in the maps buffer
+constexpr uint32_t kTaNoGoal = 16u;                                // MRP_LL_ASTAR_TA / _EPS_TA: ctx_flags bit 4: the agent has no task;
+                                                                   // MRP_LL_ASTAR_TA: path_off = word offset of the goal's heuristic
+                                                                   // table in the maps buffer (MRP_LL_ASTAR_EPS_TA: heur_off)
 constexpr uint32_t kHeurWords = 512;                               // a heuristic table: [32][32] halfwords (0xFFFF: unreachable)
 constexpr uint32_t kSippResident = 2u;
 constexpr uint32_t kSippCommit = 8u;                               // ctx_flags bit 3: on success the workgroup adds the path's stays to the table

@@ -109,6 +109,7 @@ struct TierHbm {
   static constexpr int AS = 1;   // address space of the heaps (and bitmap rows)
   static constexpr int NAS = 1;  // ... of the node records
   static constexpr bool kWideNodes = true;   // four words per node (the position of its open entry in word 3)
+  static constexpr bool kPosPair = false;    // TierFocalPos: two words per record, the position in word 1
   static constexpr bool kEntryHasX = false;
   static constexpr bool kEntryXy = false;    // A* tiers: the entry also carries the node's x | y << 8 (TierHybXy)
   static constexpr bool kHybrid = false;
@@ -142,6 +143,7 @@ struct TierLdsT {
   static constexpr int AS = 3;
   static constexpr int NAS = 3;
   static constexpr bool kWideNodes = false;  // one word per node + a halfword position array
+  static constexpr bool kPosPair = false;
   static constexpr bool kEntryHasX = false;
   static constexpr bool kEntryXy = false;
   static constexpr bool kHybrid = false;
@@ -237,6 +239,13 @@ struct TierHybXy : TierHbm {
   DEVI static E withXy(E e, uint32_t xy) { return e | ((uint64_t)(xy & 0xFFFFu) << 16); }
 };
 
+// MRP_LL_ASTAR_EPS_TA (runJobTaEps): the FOCAL list of a search whose nodes can be re-keyed while they sit in it.  Same
+// entries as TierHbm; `nodes` of its Mem view is a second record per node, {focalH, position of its entry in the focal
+// array}, so that POS = true on the focal heap keeps handle -> focal position the way the open heap keeps word 3.
+struct TierFocalPos : TierHbm {
+  static constexpr bool kPosPair = true;
+};
+
 template <class T, bool HYB = T::kHybrid>
 struct HeapPtr {
   typedef __attribute__((address_space(T::AS))) typename T::E* type;
@@ -267,7 +276,9 @@ struct Mem {
 
 template <class T>
 DEVI void setPos(Mem<T>& m, uint32_t id, uint32_t idx) {
-  if constexpr (!T::kWideNodes)
+  if constexpr (T::kPosPair)
+    m.nodes[id * 2 + 1] = idx;
+  else if constexpr (!T::kWideNodes)
     m.pos[id] = (uint16_t)idx;
   else
     m.nodes[id * 4 + 3] = idx;
@@ -1748,6 +1759,416 @@ DEVI void runJobTA(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
   res.prof[3] = (uint32_t)res.expanded;
 }
 
+// ---- MRP_LL_ASTAR_EPS_TA: the low level of ECBS with task assignment ---------------------------------------------------
+// AStarEpsilon::search (a_star_epsilon.hpp:86-285) over the Environment of example/ecbs_ta.cpp:283-445 — what
+// ecbs_ta.hpp:498-499 instantiates.  The Environment is runTaArena's (optional task, shortest-path heuristic from the
+// uploaded table, a Wait at the goal is free), the focal heuristics are example/ecbs.cpp's, taken at the successor's TIME
+// (ecbs_ta.cpp:314-344).  Because g != time a state can be discovered again with a smaller g, and this is the one search of
+// the reference in which a_star_epsilon.hpp:249-269 is live: g and f drop, `openSet.increase(handle)` sifts the open entry
+// up, focalH keeps its value, and a node that already sits in the focal list is NOT moved there — the reference's focal
+// heap compares through handles, so the entry simply reads the new f and g where it lies.  Replayed verbatim: the focal
+// entry's key is rewritten at its position (TierFocalPos keeps handle -> focal position) and nothing is sifted; every later
+// focal operation then sees the same (possibly out-of-order) array the reference's heap sees.
+//
+// The arena slot's node + heap area (LaunchParams.arena_nodes * 40 + 48 bytes; the (time, cell) bitmap behind it stays
+// where it is) is cut differently from the other searches, because this one needs the status table AND both heaps:
+//   status   one word per (t, cell): 0 unseen, node + 1 in the open list, bit 31 closed; rows = min(arena_rows,
+//            area / 8 / cells) time steps (at most half of the area)
+//   then, for capN = (area - status - 64) / 48 nodes:
+//   node A   {x | y << 8 | t << 16 | action << 27, parent, g, position in the open array}
+//   node B   {focalH, position in the focal array (kNoPos: not there)}
+//   open, focal, walk queue: capN 64-bit entries each (TierHbm keys)
+// Beyond those: MRP_LL_CAP_HORIZON / MRP_LL_CAP_NODES; focalH beyond its key field: MRP_LL_CAP_FOCAL.
+template <class T>
+DEVI void eraseOpen(Mem<T>& m, uint32_t& nOpen, uint32_t curPos) {  // boost erase: bubble to the root, then pop
+  typedef typename T::E E;
+  const uint32_t lane = threadIdx.x;
+  const uint32_t nOld = nOpen;
+  nOpen -= 1;
+  E lastOv = 0;
+  if (nOpen > 0) lastOv = m.open[nOld - 1];
+  const uint32_t depth = 31u - (uint32_t)__builtin_clz(curPos + 1);
+  const bool act = lane < depth;
+  const uint32_t anc = act ? ((curPos + 1) >> (lane + 1)) - 1 : 0;
+  E ae = 0;
+  if (depth != 0) ae = m.open[anc];
+  if (act) {  // every ancestor of curPos moves down one level
+    const uint32_t dest = ((curPos + 1) >> lane) - 1;
+    m.open[dest] = ae;
+    setPos<T>(m, T::id(ae), dest);
+  }
+  // the element pop() moves to the root: the last one — which the shift has just overwritten if the erased node WAS the
+  // last one (then it is the erased node's parent)
+  E lastO = T::first(lastOv);
+  if (curPos == nOld - 1 && depth != 0) lastO = T::fromLane(ae, 0);
+  if (nOpen > 0) descend<T, 0, true, false>(m, m.open, nOpen, 0, lastO);
+}
+
+// orderedWalk (above) with the focal pushes recorded in the nodes' B records.  Returns false if the focal array is full
+// (cannot happen while every open node sits in it at most once; checked because the array must never be overrun).
+DEVI bool orderedWalkTaEps(Mem<TierHbm>& m, Mem<TierFocalPos>& mf, SState& s, float w, int32_t oldBest) {
+  typedef TierHbm T;
+  typedef T::E E;
+  const float lo = __fmul_rn((float)oldBest, w);  // a_star_epsilon.hpp:145,149: int * float in binary32
+  const float hi = __fmul_rn((float)s.bestF, w);
+  uint32_t npq = 0;
+  E curA = T::aux(T::keyOpen(ldU<T>(m.open, 0)), 0);
+  for (;;) {
+    const uint32_t cur = T::auxIdx(curA);
+    const uint32_t first = 2 * cur + 1;
+    if (first < s.nOpen) {
+      E e1, e2;
+      ldPair<T>(m.open, first, e1, e2);
+      E ee[5];
+      ee[0] = T::aux(T::keyOpen(e1), first);
+      ee[1] = T::aux(T::keyOpen(e2), first + 1);
+      ee[2] = ee[3] = ee[4] = 0;
+      const uint32_t pm = first + 1 < s.nOpen ? 3u : 1u;
+      PushChains<T> pc;
+      pc.load(m.aux, npq, pm);
+      pc.template resolve<2, false>(m, m.aux, npq, pm, ee);
+      npq += pm == 3u ? 2u : 1u;
+    }
+    const float fv = (float)(int32_t)T::f(curA);
+    if (fv > lo && fv <= hi) {
+      if (s.nFocal + 1u >= mf.capHeap) return false;
+      const E e = ldU<T>(m.open, cur);
+      siftUp<TierFocalPos, 1, true>(mf, mf.focal, s.nFocal, e);
+      s.nFocal += 1;
+    }
+    if (fv > hi) break;
+    if (npq == 0) break;
+    curA = auxPop<T>(m, npq);
+  }
+  return true;
+}
+
+// A real function (its own register allocation): the kernels that host it keep theirs.  The job is read where the kernel
+// staged it, the result goes to `out` (status, cost, fmin, n_states, expanded, nodes_created, tier).
+__device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResult* out, uint8_t* arenaSlot, const uint32_t* maps,
+                                                      const uint32_t* consHost, const uint16_t* pathsHost,
+                                                      uint32_t scratchOff, uint32_t outStride, uint32_t arenaNodes,
+                                                      uint32_t arenaRows, uint32_t arenaRowWords, uint32_t arenaPathsBytes) {
+  typedef TierHbm T;
+  typedef TierFocalPos TF;
+  typedef T::E E;
+  const uint32_t lane = threadIdx.x;
+  const uint32_t dimx = rfl(Jp->dimx), dimy = rfl(Jp->dimy), cells = dimx * dimy;
+  const uint32_t sx = rfl(Jp->sx), sy = rfl(Jp->sy), gx = rfl(Jp->gx), gy = rfl(Jp->gy);
+  const uint32_t nVc = rfl(Jp->n_vc), nEc = rfl(Jp->n_ec), vcOff = rfl(Jp->vc_off), ecOff = rfl(Jp->ec_off);
+  const uint32_t nAgentsPad = rfl(Jp->n_agents_pad), tPad = rfl(Jp->t_pad), pathOff = rfl(Jp->path_off);
+  const bool noGoal = (rfl(Jp->ctx_flags) & kTaNoGoal) != 0;
+  const int32_t lastGoal = rfli(Jp->last_goal_constraint);
+  const float w = __builtin_bit_cast(float, rfl(__builtin_bit_cast(uint32_t, Jp->w)));
+  const int64_t maxExp = (int64_t)rfl64((uint64_t)Jp->max_expansions);
+  const bool small = dimx <= 32u && dimy <= 32u;
+  const uint16_t* heur = (const uint16_t*)(maps + rfl(Jp->heur_off));
+  const uint32_t heurStride = small ? 32u : dimx;
+
+  int32_t status = ST_NO_SOLUTION, cost = 0, fmin = 0, nStates = 0;
+  SState s;
+  s.nNodes = 0; s.nOpen = 0; s.nFocal = 0; s.rowsReady = 0; s.bestF = 0; s.expansions = 0;
+
+  // ---- the job's constraint words and focal path table leave host memory in one pass
+  uint8_t* scratch = arenaSlot + scratchOff;
+  uint16_t* outPath = (uint16_t*)scratch;
+  uint32_t* consLocal = (uint32_t*)(scratch + (size_t)outStride * 2);
+  uint8_t* pathsArena = (uint8_t*)(consLocal + kConsLocalWords);
+  Ctx c;
+  c.dimx = dimx; c.dimy = dimy; c.wpr = rfl(Jp->words_per_row);
+  c.gx = gx; c.gy = gy; c.sx = sx; c.sy = sy;
+  c.lastGoal = lastGoal;
+  c.w = w;
+  c.nVc = nVc; c.nEc = nEc;
+  c.obst = maps + rfl(Jp->map_word_off);
+  c.pathsLds = nullptr;
+  c.nAgentsPad = nAgentsPad; c.tPad = tPad;
+  c.maxExp = maxExp;
+  c.debug = nullptr;
+  if (nVc + nEc <= kConsLocalWords) {
+    for (uint32_t i = lane; i < nVc; i += 64) consLocal[i] = hostLoad32(consHost + vcOff + i);
+    for (uint32_t i = lane; i < nEc; i += 64) consLocal[nVc + i] = hostLoad32(consHost + ecOff + i);
+    c.vc = consLocal;
+    c.ec = consLocal + nVc;
+  } else {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+    c.vc = consHost + vcOff;
+    c.ec = consHost + ecOff;
+  }
+  {
+    const uint32_t pathBytes = tPad * nAgentsPad * 2;  // multiple of 32
+    if (pathBytes == 0) {
+      c.paths = nullptr;
+      c.nAgentsPad = 0;
+    } else if (pathBytes <= arenaPathsBytes) {
+      const uint32_t* psrc = (const uint32_t*)(pathsHost + pathOff);
+      uint32_t* dst = (uint32_t*)pathsArena;
+      for (uint32_t i = lane; i < pathBytes / 4; i += 64) dst[i] = hostLoad32(psrc + i);
+      c.paths = (const uint16_t*)pathsArena;
+    } else {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+      c.paths = pathsHost + pathOff;
+    }
+  }
+  __syncthreads();
+
+  // ---- this search's cut of the slot
+  const uint64_t area = (uint64_t)arenaNodes * 16 + 3 * ((uint64_t)arenaNodes * 8 + 16);
+  const uint64_t rows64 = area / 8 / cells;
+  const uint32_t rows = (uint32_t)(rows64 < arenaRows ? rows64 : arenaRows);
+  const uint64_t statusBytes = ((uint64_t)rows * cells * 4 + 15) & ~15ull;
+  uint64_t capN64 = area > statusBytes + 64 ? (area - statusBytes - 64) / 48 : 0;
+  if (capN64 > kMaxArenaNodes) capN64 = kMaxArenaNodes;
+  const uint32_t capN = (uint32_t)capN64 & ~1u;
+  Mem<T> g;
+  Mem<TF> gf;
+  uint32_t* stTab = (uint32_t*)arenaSlot;
+  {
+    uint8_t* p = arenaSlot + statusBytes;
+    g.nodes = (Mem<T>::PN32)p;             p += (size_t)capN * 16;
+    gf.nodes = (Mem<TF>::PN32)p;           p += (size_t)capN * 8;
+    g.open = (Mem<T>::PE)(p + 8);          p += (size_t)capN * 8 + 16;
+    g.focal = (Mem<T>::PE)(p + 8);         p += (size_t)capN * 8 + 16;
+    g.aux = (Mem<T>::PE)(p + 8);
+    g.pos = nullptr; g.gOf = nullptr;
+    g.bits = (Mem<T>::P32)(arenaSlot + area);
+    g.capNodes = capN; g.capHeap = capN; g.capRows = arenaRows; g.rowWords = arenaRowWords;
+    gf.pos = nullptr; gf.gOf = nullptr;
+    gf.open = g.open; gf.focal = g.focal; gf.aux = g.aux; gf.bits = g.bits;
+    gf.capNodes = capN; gf.capHeap = capN; gf.capRows = arenaRows; gf.rowWords = arenaRowWords;
+  }
+  typedef __attribute__((address_space(1))) u32x2* PNodeB;
+  const PNodeB nodesB = (PNodeB)gf.nodes;
+
+  bool run = true;
+  const uint32_t h0 = noGoal ? 0u : heur[sy * heurStride + sx];
+  if (rows < 2u || h0 > kFMax - 2u) {  // no room for a second time step / the task is unreachable or beyond f's field
+    status = ST_CAP_HORIZON;
+    run = false;
+  } else if (capN < 16u) {
+    status = ST_CAP_NODES;
+    run = false;
+  }
+  uint32_t statusReady = 1;  // rows of the status table that have been zeroed
+  if (run) {
+    u32x4 n0;
+    n0.x = sx | (sy << 8) | (0u << 16) | (7u << 27);
+    n0.y = kNoParent;
+    n0.z = 0;
+    n0.w = 0;
+    ((Mem<T>::PNode4)g.nodes)[0] = n0;
+    u32x2 b0;
+    b0.x = 0;
+    b0.y = 0;  // focal position 0
+    nodesB[0] = b0;
+    const E e0 = T::pack(0, h0, 0, 0);
+    g.open[0] = e0;
+    g.focal[0] = e0;
+    for (uint32_t i = lane; i < cells; i += 64) stTab[i] = 0;
+    __syncthreads();
+    stTab[sy * dimx + sx] = 1u;  // node 0, in the open list
+    s.nNodes = 1; s.nOpen = 1; s.nFocal = 1;
+    s.bestF = (int32_t)h0;
+  }
+  const uint32_t ecReg = lane < nEc ? c.ec[lane] : 0xFFFFFFFFu;
+  const int32_t dx = (lane == 2) - (lane == 1);
+  const int32_t dy = (lane == 3) - (lane == 4);
+  while (run) {
+    if (s.nOpen == 0) {
+      status = ST_NO_SOLUTION;
+      break;
+    }
+    const E topE = ldU<T>(g.open, 0);
+    {  // a_star_epsilon.hpp:134-154: bestFScore follows open.top() (also down); the ordered walk only when it rose
+      const int32_t oldBest = s.bestF;
+      s.bestF = (int32_t)T::f(topE);
+      if (s.bestF > oldBest && !orderedWalkTaEps(g, gf, s, w, oldBest)) {
+        status = ST_CAP_NODES;
+        break;
+      }
+    }
+    if (s.nFocal == 0) {  // (w < 1: the reference reads the top of an empty heap here)
+      status = ST_BAD;
+      break;
+    }
+    const E curE = ldU<T>(g.focal, 0);  // focalSet.top(): g, f, focalH as they are NOW (re-keyed in place)
+    const uint32_t curId = T::id(curE), gcur = T::g(curE), curFh = T::fh(curE);
+    const u32x4 nd = ((Mem<T>::PNode4)g.nodes)[curId];
+    const uint32_t xyt = rfl(nd.x), curPos = rfl(nd.w);
+    const uint32_t x = xyt & 0xFFu, y = (xyt >> 8) & 0xFFu, t = (xyt >> 16) & 0x7FFu;
+    const uint32_t xy = xyt & 0xFFFFu;
+    const bool atGoal = noGoal || (x == gx && y == gy);
+    s.expansions += 1;  // onExpandNode (a_star_epsilon.hpp:193) — counts the goal pop too
+    if (maxExp >= 0 && s.expansions > maxExp) {
+      status = ST_CAP_EXP;
+      break;
+    }
+    if (atGoal && (int32_t)t > lastGoal) {  // isSolution (ecbs_ta.cpp:384-390) -> a_star_epsilon.hpp:195-213
+      if (t + 1u > outStride) {
+        status = ST_CAP_HORIZON;
+        break;
+      }
+      uint32_t nid = curId;
+      for (int32_t k = (int32_t)t; k >= 0; --k) {
+        const u32x4 pn = ((Mem<T>::PNode4)g.nodes)[nid];
+        outPath[k] = (uint16_t)(rfl(pn.x) & 0xFFFFu);  // all lanes, same address, same value
+        nid = rfl(pn.y);
+      }
+      status = ST_OK;
+      cost = (int32_t)gcur;
+      fmin = (int32_t)T::f(topE);  // openSet.top().fScore (a_star_epsilon.hpp:210)
+      nStates = (int32_t)t + 1;
+      break;
+    }
+    const uint32_t t1 = t + 1u;
+    if (t1 >= rows || t1 >= g.capRows) {
+      status = ST_CAP_HORIZON;
+      break;
+    }
+    if (s.nNodes + 5u > capN || s.nOpen + 5u > capN || s.nFocal + 5u > capN) {
+      status = ST_CAP_NODES;
+      break;
+    }
+    // other agents' cells at t and t + 1 (x | y << 8), 64 agents per lane load; rows beyond the table repeat its last one
+    uint32_t a0 = kEmptyCell, b0 = kEmptyCell, a1 = kEmptyCell, b1 = kEmptyCell;
+    const uint16_t* rowA = nullptr;
+    const uint16_t* rowB = nullptr;
+    if (c.nAgentsPad) {
+      const uint32_t ra = t < tPad ? t : tPad - 1;
+      const uint32_t rb = t1 < tPad ? t1 : tPad - 1;
+      rowA = c.paths + (size_t)ra * c.nAgentsPad;
+      rowB = c.paths + (size_t)rb * c.nAgentsPad;
+      if (lane < c.nAgentsPad) {
+        a0 = rowA[lane];
+        b0 = rowB[lane];
+      }
+      if (64 + lane < c.nAgentsPad) {
+        a1 = rowA[64 + lane];
+        b1 = rowB[64 + lane];
+      }
+    }
+    heapPop<TF, 1, true>(gf, gf.focal, s.nFocal);  // focalSet.pop()          (a_star_epsilon.hpp:215)
+    eraseOpen<T>(g, s.nOpen, curPos);              // openSet.erase(handle)   (:216)
+    stTab[t * cells + y * dimx + x] = 0x80000000u;  // stateToHeap.erase, closedSet.insert (:217-218)
+    ensureRows<T>(g, s, c, t1, (Mem<T>::P32)c.obst, false);
+    while (statusReady <= t1) {  // the status rows of the next time steps: nothing seen
+      for (uint32_t i = lane; i < cells; i += 64) stTab[statusReady * cells + i] = 0;
+      statusReady += 1;
+    }
+    __syncthreads();
+    // getNeighbors (ecbs_ta.cpp:392-438): Wait, Left, Right, Up, Down on lanes 0..4 — bounds, obstacle | vertex constraint
+    // (one bit of the bitmap), edge constraints by key
+    const uint32_t nx = x + (uint32_t)dx, ny = y + (uint32_t)dy;
+    const bool inb = (lane < 5) && (nx < dimx) && (ny < dimy);
+    const uint32_t ncell = inb ? ny * dimx + nx : 0;
+    const uint32_t word = g.bits[t1 * g.rowWords + (ncell >> 5)];
+    const uint32_t hN = (noGoal || !inb) ? 0u : heur[ny * heurStride + nx];
+    const uint32_t stN = inb ? stTab[t1 * cells + ncell] : 0u;
+    const uint32_t nxyL = nx | (ny << 8);
+    uint32_t mask = (uint32_t)(ballot64(inb && !((word >> (ncell & 31)) & 1u)) & 0x1Full);
+    if (nEc) {  // transitionValid
+      const uint32_t base = (t << 19) | ((y * dimx + x) << 3);
+      uint32_t blocked = 0;
+      for (uint32_t j0 = 0; j0 < nEc; j0 += 64) {
+        const uint32_t d = (j0 == 0 ? ecReg : (j0 + lane < nEc ? c.ec[j0 + lane] : 0xFFFFFFFFu)) - base;
+#pragma unroll
+        for (uint32_t k = 0; k < 5; ++k) blocked |= ballot64(d == k) ? (1u << k) : 0u;
+      }
+      mask &= ~blocked;
+    }
+    const float bound = __fmul_rn((float)s.bestF, w);  // bestFScore * m_w (a_star_epsilon.hpp:240,265), binary32
+    const uint64_t swap0 = ballot64(b0 == xy);
+    const uint64_t swap1 = ballot64(b1 == xy);
+    bool fail = false;
+    for (uint32_t mm = mask; mm; mm &= mm - 1) {  // a_star_epsilon.hpp:223-281, neighbour by neighbour
+      const uint32_t k = (uint32_t)__builtin_ctz(mm);
+      const uint32_t st = __builtin_amdgcn_readlane(stN, k);
+      if (st & 0x80000000u) continue;  // closed (:224)
+      const uint32_t nc = __builtin_amdgcn_readlane(ncell, k);
+      const uint32_t g2 = gcur + ((k == 0 && atGoal) ? 0u : 1u);  // tentative_gScore (:225)
+      if (st == 0) {  // a new node (:227-247)
+        const uint32_t h = __builtin_amdgcn_readlane(hN, k);
+        const uint32_t cc = __builtin_amdgcn_readlane(nxyL, k);
+        if (h > kFMax || g2 + h > kFMax - 2u || g2 > kGMask) {
+          status = ST_CAP_HORIZON;
+          fail = true;
+          break;
+        }
+        // focalStateHeuristic + focalTransitionHeuristic (ecbs_ta.cpp:314-344): an agent counts once if it stands on the
+        // successor's cell at time t + 1 and once more if it is there at t and on this node's cell at t + 1 (a Wait too)
+        uint32_t cnt = 0;
+        if (c.nAgentsPad) {
+          cnt = (uint32_t)__popcll(ballot64(b0 == cc)) + (uint32_t)__popcll(ballot64(a0 == cc) & swap0) +
+                (uint32_t)__popcll(ballot64(b1 == cc)) + (uint32_t)__popcll(ballot64(a1 == cc) & swap1);
+          for (uint32_t base = 128; base < c.nAgentsPad; base += 64) {
+            uint32_t av = kEmptyCell, bv = kEmptyCell;
+            if (base + lane < c.nAgentsPad) {
+              av = rowA[base + lane];
+              bv = rowB[base + lane];
+            }
+            cnt += (uint32_t)__popcll(ballot64(bv == cc)) + (uint32_t)__popcll(ballot64(av == cc && bv == xy));
+          }
+        }
+        const uint32_t fh = curFh + cnt;
+        if (fh > kFhMax) {
+          status = ST_CAP_FOCAL;
+          fail = true;
+          break;
+        }
+        const uint32_t f2 = g2 + h;
+        const uint32_t nid = s.nNodes++;
+        u32x4 nn;
+        nn.x = cc | (t1 << 16) | (k << 27);
+        nn.y = curId;
+        nn.z = g2;
+        nn.w = 0;
+        ((Mem<T>::PNode4)g.nodes)[nid] = nn;
+        u32x2 nb;
+        nb.x = fh;
+        nb.y = kNoPos;
+        nodesB[nid] = nb;
+        stTab[t1 * cells + nc] = nid + 1u;
+        const E e = T::pack(fh, f2, g2, nid);
+        siftUp<T, 0, true>(g, g.open, s.nOpen, e);  // openSet.push (:237)
+        s.nOpen += 1;
+        if ((float)(int32_t)f2 <= bound) {          // focalSet.push (:240-243)
+          siftUp<TF, 1, true>(gf, gf.focal, s.nFocal, e);
+          s.nFocal += 1;
+        }
+      } else {  // still in the open list (:248-270)
+        const uint32_t nid = st - 1u;
+        const u32x4 on = ((Mem<T>::PNode4)g.nodes)[nid];
+        const uint32_t gOld = rfl(on.z), posOld = rfl(on.w);
+        if (g2 >= gOld) continue;  // (:251-253)
+        const u32x2 ob = nodesB[nid];
+        const uint32_t fhOld = rfl(ob.x), fpos = rfl(ob.y);
+        const uint32_t fOld = T::f(ldU<T>(g.open, posOld));
+        const uint32_t fNew = fOld - (gOld - g2);  // fScore -= delta (:259-261)
+        g.nodes[nid * 4 + 0] = (rfl(on.x) & 0x07FFFFFFu) | (k << 27);  // cameFrom is replaced (:275-279)
+        g.nodes[nid * 4 + 1] = curId;
+        g.nodes[nid * 4 + 2] = g2;
+        const E e = T::pack(fhOld, fNew, g2, nid);  // focalH keeps its value
+        siftUp<T, 0, true>(g, g.open, posOld, e);   // openSet.increase(handle) (:262)
+        if (fpos != kNoPos) {
+          // already in the focal list: its entry reads the new f and g where it lies; the heap is not repaired
+          if (fpos < s.nFocal) g.focal[fpos] = e;
+        } else if ((float)(int32_t)fNew <= bound && (float)(int32_t)fOld > bound) {  // crossed the bound (:265-269)
+          siftUp<TF, 1, true>(gf, gf.focal, s.nFocal, e);
+          s.nFocal += 1;
+        }
+      }
+    }
+    if (fail) break;
+  }
+  out->status = status;
+  out->cost = cost;
+  out->fmin = fmin;
+  out->n_states = nStates;
+  out->expanded = s.expansions;
+  out->nodes_created = s.nNodes;
+  out->tier = 1;
+}
+
 // ---- SIPP (config 5): A* over (cell, safe interval) states ---------------------------------------------------
 // Reference: SIPP::search sipp.hpp:91-134 -> AStar::search a_star.hpp:63-161 over SIPPState with
 // SIPPEnvironment::getNeighbors sipp.hpp:191-223 (motions Up, Down, Left, Right of mapf_prioritized_sipp.cpp:99-121;
@@ -2639,7 +3060,19 @@ DEVI bool processJob(const LaunchParams& P, const DevJob* jobSrc, DevResult* res
       runJob<true, false, kTiersAll>(P, J, smem, arenaSlot, res, outPath);
     else if (algo == 3)
       runJobTA(P, J, smem, arenaSlot, res, outPath);
-    else
+    else if (algo == 4) {  // MRP_LL_ASTAR_EPS_TA: arena tier only; the result comes back through the staging record
+      const uint64_t th0 = __builtin_amdgcn_s_memrealtime();
+      runJobTaEps(&jobS, &resS, arenaSlot, P.maps, P.cons, P.paths, P.arena_scratch_off, P.out_stride, P.arena_nodes,
+                  P.arena_rows, P.arena_row_words, P.arena_paths_bytes);
+      __syncthreads();
+      res.status = rfli(resS.status); res.cost = rfli(resS.cost); res.fmin = rfli(resS.fmin);
+      res.n_states = rfli(resS.n_states);
+      res.expanded = (int64_t)rfl64((uint64_t)resS.expanded);
+      res.nodes_created = rfl(resS.nodes_created);
+      res.tier = rfl(resS.tier);
+      res.prof[2] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - th0);
+      res.prof[3] = (uint32_t)res.expanded;
+    } else
       runJob<false, false, kTiersAll>(P, J, smem, arenaSlot, res, outPath);
   } else if constexpr (KIND == 1) {  // the A*-epsilon-only kernels: the small window (mrp_ll_lds_bytes(kind = 1))
     if (algo == 1) {

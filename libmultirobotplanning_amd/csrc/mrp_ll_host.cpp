@@ -728,8 +728,14 @@ template <class ConsSink, class PathSink>
 bool packJob(mrp_ll_ctx* ctx, const mrp_ll_job& j, ConsSink& cs, PathSink& ps, DevJob& d) {
   if (j.map_id < 0 || j.map_id >= static_cast<int32_t>(ctx->maps.size())) return false;
   const MapRec& mp = ctx->maps[j.map_id];
-  if (j.algo != MRP_LL_ASTAR && j.algo != MRP_LL_ASTAR_EPS && j.algo != MRP_LL_SIPP && j.algo != MRP_LL_ASTAR_TA) return false;
+  if (j.algo != MRP_LL_ASTAR && j.algo != MRP_LL_ASTAR_EPS && j.algo != MRP_LL_SIPP && j.algo != MRP_LL_ASTAR_TA &&
+      j.algo != MRP_LL_ASTAR_EPS_TA)
+    return false;
   if (j.algo == MRP_LL_ASTAR_EPS && j.initial_cost != 0) return false;  // AStarEpsilon::search has no initialCost
+  const bool epsTa = j.algo == MRP_LL_ASTAR_EPS_TA;
+  // MRP_LL_ASTAR_EPS_TA serves ecbs_ta.hpp's calls only: no initial cost, no root chain, no tier hint, no path store
+  if (epsTa && (j.initial_cost != 0 || (j.flags & (MRP_LL_JOB_ROOT_CHAIN | MRP_LL_JOB_HEAVY | MRP_LL_JOB_STORE_RESULT)) || j.path_ids))
+    return false;
   if (j.initial_cost < 0 || j.initial_cost >= 0x40000000) return false;  // (bit 30 of the per-job word marks MRP_LL_ASTAR_TA, jobInitOf)
   if (j.flags & MRP_LL_JOB_ROOT_CHAIN) {  // the root step of an ECBS conflict tree as one job (mrp_ll.h; ll_device.h kCtxChain)
     const int n = j.n_agents, first = j.agent_idx;
@@ -786,7 +792,7 @@ bool packJob(mrp_ll_ctx* ctx, const mrp_ll_job& j, ConsSink& cs, PathSink& ps, D
   d.words_per_row = mp.wpr;
   d.sx = j.start_x;
   d.sy = j.start_y;
-  const bool taNoGoal = j.algo == MRP_LL_ASTAR_TA && (j.flags & MRP_LL_JOB_NO_GOAL) != 0;
+  const bool taNoGoal = (j.algo == MRP_LL_ASTAR_TA || epsTa) && (j.flags & MRP_LL_JOB_NO_GOAL) != 0;
   // a goal outside the grid can never be reached; keep the reference behaviour (search until open is exhausted /
   // capped) by parking it on an unreachable coordinate that still fits the 8-bit fields only if in range
   if (!taNoGoal && !inGrid(j.goal_x, j.goal_y)) return false;
@@ -796,14 +802,16 @@ bool packJob(mrp_ll_ctx* ctx, const mrp_ll_job& j, ConsSink& cs, PathSink& ps, D
   d.w = j.w;
   d.max_expansions = j.max_expansions;
   if (j.algo == MRP_LL_SIPP) return packSipp(ctx, j, mp, cs, d);
-  if (j.algo == MRP_LL_ASTAR_TA) {
-    // (the compact tier serves what fits it — maps up to 32 x 32, 64 + 64 constraints —, the arena tier the rest)
+  uint32_t heurOff = 0;
+  if (j.algo == MRP_LL_ASTAR_TA || epsTa) {
+    // (MRP_LL_ASTAR_TA: the compact tier serves what fits it — maps up to 32 x 32, 64 + 64 constraints —, the arena tier
+    // the rest; MRP_LL_ASTAR_EPS_TA: arena tier only)
     if (j.initial_cost != 0) return false;
     if (!taNoGoal) {
       if (j.heuristic_id < 0 || j.heuristic_id >= static_cast<int32_t>(ctx->heurs.size()) ||
           ctx->heurs[j.heuristic_id].mapId != j.map_id)
         return false;
-      d.path_off = ctx->heurs[j.heuristic_id].wordOff;
+      heurOff = ctx->heurs[j.heuristic_id].wordOff;
     } else {
       d.ctx_flags |= mrp::kTaNoGoal;
     }
@@ -831,7 +839,6 @@ bool packJob(mrp_ll_ctx* ctx, const mrp_ll_job& j, ConsSink& cs, PathSink& ps, D
   d.n_ec = static_cast<uint32_t>(cs.size()) - d.ec_off;
   if (cs.failed) return false;
   if (j.algo == MRP_LL_ASTAR_TA) {
-    const uint32_t heurOff = d.path_off;
     d.n_agents_pad = 0;
     d.t_pad = 0;
     d.path_off = heurOff;
@@ -842,6 +849,7 @@ bool packJob(mrp_ll_ctx* ctx, const mrp_ll_job& j, ConsSink& cs, PathSink& ps, D
   d.n_agents_pad = 0;
   d.t_pad = 0;
   d.path_off = 0;
+  d.heur_off = epsTa ? heurOff : 0;  // (MRP_LL_ASTAR_EPS_TA needs both: the heuristic table and the focal path table)
   if ((j.flags & MRP_LL_JOB_HEAVY) && j.algo == MRP_LL_ASTAR_EPS) d.ctx_flags |= mrp::kCtxHeavy;
   // the result path also goes to a path-store slot only when the caller says so (a zero-initialised job names no slot)
   const bool storeResult = (j.flags & MRP_LL_JOB_STORE_RESULT) != 0;
@@ -873,7 +881,7 @@ bool packJob(mrp_ll_ctx* ctx, const mrp_ll_job& j, ConsSink& cs, PathSink& ps, D
       d.n_agents_pad = (static_cast<uint32_t>(j.n_agents) + 15u) & ~15u;
       d.t_pad = static_cast<uint32_t>(tpad);
     }
-  } else if (j.algo == MRP_LL_ASTAR_EPS && j.n_agents > 0) {
+  } else if ((j.algo == MRP_LL_ASTAR_EPS || epsTa) && j.n_agents > 0) {
     if (!j.path_len || !j.path_xy) return false;
     int tpad = 0;
     for (int a = 0; a < j.n_agents; ++a)
@@ -1105,7 +1113,7 @@ void unpackResult(mrp_ll_ctx* ctx, const DevResult& d, const uint16_t* p, bool r
 // MRP_LL_ASTAR_TA, whose initial cost is always 0 — bit 30 + the goal cell and the no-task flag.
 int32_t jobInitOf(const mrp_ll_job& j, bool ok) {
   if (!ok) return 0;
-  if (j.algo == MRP_LL_ASTAR_TA)
+  if (j.algo == MRP_LL_ASTAR_TA || j.algo == MRP_LL_ASTAR_EPS_TA)
     return 0x40000000 | ((j.flags & MRP_LL_JOB_NO_GOAL) ? 0x10000 : ((j.goal_y & 0xFF) << 8 | (j.goal_x & 0xFF)));
   return j.initial_cost;
 }
@@ -2022,9 +2030,11 @@ int mrp_ll_submit(mrp_ll_ctx* ctx, int32_t nJobs, const mrp_ll_job* jobs, mrp_ll
       return MRP_LL_E_INVALID;
     }
     t.sipp = nSipp != 0;
-    int nEps = 0;
+    int nEps = 0, nEpsTa = 0;
     for (int i = 0; i < nJobs; ++i) nEps += jobs[i].algo == MRP_LL_ASTAR_EPS ? 1 : 0;
-    t.kind = t.sipp ? 0 : nEps == nJobs ? 1 : nEps == 0 ? 2 : 0;  // a one-algorithm batch runs the specialised kernel
+    for (int i = 0; i < nJobs; ++i) nEpsTa += jobs[i].algo == MRP_LL_ASTAR_EPS_TA ? 1 : 0;
+    // a one-algorithm batch runs the specialised kernel; MRP_LL_ASTAR_EPS_TA lives in the mixed kernel only
+    t.kind = (t.sipp || nEpsTa != 0) ? 0 : nEps == nJobs ? 1 : nEps == 0 ? 2 : 0;
   }
   t.jobs.clear();
   t.cons.clear();

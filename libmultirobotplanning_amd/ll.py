@@ -15,7 +15,7 @@ import numpy as np
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get("MRP_LL_LIB") or os.path.join(_PKG, "lib", "libmrp_ll.so")
 
-ASTAR, ASTAR_EPS, SIPP, ASTAR_TA = 0, 1, 2, 3
+ASTAR, ASTAR_EPS, SIPP, ASTAR_TA, ASTAR_EPS_TA = 0, 1, 2, 3, 4
 JOB_STORE_RESULT, JOB_NO_GOAL, JOB_ROOT_CHAIN, JOB_HEAVY = 1, 2, 4, 8  # mrp_ll_job.flags (include/mrp_ll.h)
 OK, NO_SOLUTION, CAP_EXPANSIONS, CAP_NODES, CAP_HORIZON, BAD_JOB, PATH_TRUNCATED, CAP_FOCAL = range(8)
 ACTION_NAMES = ["Up", "Down", "Left", "Right", "Wait"]  # example/ecbs.cpp:49-55
@@ -152,7 +152,7 @@ class LLJob:
     map_id: int
     algo: int
     start: Sequence[int]
-    goal: Optional[Sequence[int]]  # None: ASTAR_TA for an agent without a task (MRP_LL_JOB_NO_GOAL)
+    goal: Optional[Sequence[int]]  # None: ASTAR_TA / ASTAR_EPS_TA for an agent without a task (MRP_LL_JOB_NO_GOAL)
     agent_idx: int = 0
     w: float = 1.0
     vertex_constraints: Sequence[Sequence[int]] = ()   # (time, x, y)
@@ -165,7 +165,7 @@ class LLJob:
     sipp_commit: bool = False         # SIPP with sipp_table: on success the path's stays join the table (mrp_ll.h)
     path_ids: Optional[Sequence[int]] = None  # f2: path-store slots of ctx_paths (-1 = none); lengths come from ctx_paths
     result_path_id: int = -1                  # f2: path-store slot that also receives the result path
-    heuristic_id: int = -1                    # ASTAR_TA: LowLevelEngine.upload_heuristic of the goal cell
+    heuristic_id: int = -1                    # ASTAR_TA / ASTAR_EPS_TA: LowLevelEngine.upload_heuristic of the goal cell
     heavy: bool = False                       # MRP_LL_JOB_HEAVY: the search is known to outgrow the LDS tier (a hint)
 
 
