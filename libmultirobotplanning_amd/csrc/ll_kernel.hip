@@ -1017,6 +1017,85 @@ DEVI uint32_t storeLoad(const uint16_t* p) {
 DEVI uint32_t hostLoad32(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 DEVI void hostStore32(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 
+// ---- job staging shared by the searches (runJob, runChain, runJobTA, runJobTaEps, runSipp) -----------------------------
+// The job's constraint words leave host memory in one coalesced pass into the arena's copy area; a list of more than
+// kConsLocalWords words is read where the host put it, with plain loads behind one acquire fence.  The vertex words and
+// the edge words are ONE run: the host packer pushes them back to back, ec_off == vc_off + n_vc (mrp_ll_host.cpp packJob).
+DEVI void stageConstraints(const uint32_t* consHost, uint32_t vcOff, uint32_t nVc, uint32_t nEc, uint32_t* consLocal,
+                           const uint32_t*& vc, const uint32_t*& ec) {
+  const uint32_t* src = consHost + vcOff;
+  const uint32_t nWords = nVc + nEc;
+  if (nWords <= kConsLocalWords) {
+    for (uint32_t i = threadIdx.x; i < nWords; i += 64) consLocal[i] = hostLoad32(src + i);
+    vc = consLocal;
+  } else {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+    vc = src;
+  }
+  ec = vc + nVc;
+}
+
+// What a search's Ctx takes from the job descriptor; vc / ec (stageConstraints) and the path table are the caller's.
+// UNI: the descriptor is read through a pointer the compiler cannot prove wave-uniform (runJobTaEps's argument).
+template <bool UNI = false>
+DEVI void fillCtx(Ctx& c, const DevJob& J, const uint32_t* maps, volatile uint32_t* debug) {
+  auto u = [](uint32_t v) { return UNI ? rfl(v) : v; };
+  c.dimx = u(J.dimx); c.dimy = u(J.dimy); c.wpr = u(J.words_per_row);
+  c.gx = u(J.gx); c.gy = u(J.gy); c.sx = u(J.sx); c.sy = u(J.sy);
+  c.lastGoal = (int32_t)u((uint32_t)J.last_goal_constraint);
+  c.w = __builtin_bit_cast(float, u(__builtin_bit_cast(uint32_t, J.w)));
+  c.nVc = u(J.n_vc); c.nEc = u(J.n_ec);
+  c.obst = maps + u(J.map_word_off);
+  c.nAgentsPad = u(J.n_agents_pad); c.tPad = u(J.t_pad);
+  c.maxExp = UNI ? (int64_t)rfl64((uint64_t)J.max_expansions) : J.max_expansions;
+  c.debug = debug;
+}
+
+// A compact-tier job goes into its block of the LDS window (every lane stores the same words) and the result comes back
+// from there: the ct:: searches are real functions with their own register allocation.
+DEVI void putCJob(uint8_t* smem, const ct::CJob& cj) {
+  auto w32 = (__attribute__((address_space(3))) uint32_t*)((wv::Lds)smem + ct::oJob);
+  const uint32_t* src = (const uint32_t*)&cj;
+#pragma unroll
+  for (uint32_t q = 0; q < sizeof(ct::CJob) / 4; ++q) w32[q] = src[q];
+}
+DEVI ct::CRes getCRes(uint8_t* smem) {
+  auto r32 = (__attribute__((address_space(3))) const uint32_t*)((wv::Lds)smem + ct::oRes);
+  ct::CRes cr;
+  cr.status = (int32_t)rfl(r32[0]); cr.cost = (int32_t)rfl(r32[1]); cr.fmin = (int32_t)rfl(r32[2]);
+  cr.nStates = (int32_t)rfl(r32[3]); cr.expanded = rfl(r32[4]); cr.nodes = rfl(r32[5]);
+  return cr;
+}
+// The narrow geometry as mrp_ll_configure_tiers sized it: lds_nodes / 2 = open-list entries, lds_rows = time steps a
+// search may use inside the tier; and the expansion budget in the tier's 32 bits (all ones: unlimited).
+DEVI uint32_t narrowOpenCap(const LaunchParams& P) { return P.lds_nodes / 2u < ct::kCap ? P.lds_nodes / 2u : ct::kCap; }
+DEVI uint32_t narrowMaxT(const LaunchParams& P) {
+  return P.lds_rows >= 3u && P.lds_rows - 2u < ct::kMaxT ? P.lds_rows - 2u : ct::kMaxT;
+}
+DEVI uint32_t clampMaxExp(int64_t maxExp) {
+  return maxExp < 0 ? 0xFFFFFFFFu : (maxExp > 0xFFFFFFFEll ? 0xFFFFFFFEu : (uint32_t)maxExp);
+}
+
+// Three heap arrays (open, focal, walk queue) of `cap` 64-bit entries each from `p` on, every one with the bias slot in
+// front of it; returns the first byte behind them.
+DEVI uint8_t* cutHeaps(Mem<TierHbm>& g, uint8_t* p, uint32_t cap) {
+  g.open = (Mem<TierHbm>::PE)(p + 8);          p += (size_t)cap * 8 + 16;
+  g.focal = (Mem<TierHbm>::PE)(p + 8);         p += (size_t)cap * 8 + 16;
+  g.aux = (Mem<TierHbm>::PE)(p + 8);           p += (size_t)cap * 8 + 16;
+  g.capNodes = cap; g.capHeap = cap;
+  return p;
+}
+// The arena slot as most searches use it: arena_nodes node records, the three heaps, the (time, cell) bitmap.
+DEVI Mem<TierHbm> cutArena(const LaunchParams& P, uint8_t* arenaSlot) {
+  Mem<TierHbm> g;
+  g.nodes = (Mem<TierHbm>::PN32)arenaSlot;
+  g.pos = nullptr;
+  g.gOf = nullptr;
+  g.bits = (Mem<TierHbm>::P32)cutHeaps(g, arenaSlot + (size_t)P.arena_nodes * 16, P.arena_nodes);
+  g.capRows = P.arena_rows; g.rowWords = P.arena_row_words;
+  return g;
+}
+
 // Which tiers a kernel carries:
 //   kTiersAll   — compact (narrow) tier, then the arena tier: batch kernels, CBS / mixed sessions, A*-epsilon sessions
 //                 without heavy workgroups;
@@ -1038,32 +1117,14 @@ DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t*
     if (heavyHint || P.lds_nodes == 0 || J.dimx > 32u || J.dimy > 32u || J.n_agents_pad > 128u || J.n_ec > 64u) return true;
   }
   Ctx c;
-  c.dimx = J.dimx; c.dimy = J.dimy; c.wpr = J.words_per_row;
-  c.gx = J.gx; c.gy = J.gy; c.sx = J.sx; c.sy = J.sy;
-  c.lastGoal = J.last_goal_constraint;
-  c.w = J.w;
-  c.nVc = J.n_vc; c.nEc = J.n_ec;
-  c.obst = P.maps + J.map_word_off;
-  c.nAgentsPad = J.n_agents_pad; c.tPad = J.t_pad;
-  c.maxExp = J.max_expansions;
-  c.debug = P.debug;
+  fillCtx(c, J, P.maps, P.debug);
 
   // ---- bulk-copy the job's constraint words and path table out of host memory (one pass, coalesced) ----
   uint8_t* scratch = arenaSlot + P.arena_scratch_off;
   uint32_t* consLocal = (uint32_t*)(scratch + (size_t)P.out_stride * 2);
   uint8_t* pathsArena = (uint8_t*)(consLocal + kConsLocalWords);
+  stageConstraints(P.cons, J.vc_off, c.nVc, c.nEc, consLocal, c.vc, c.ec);
   {
-    const uint32_t* src = P.cons + J.vc_off;          // vertex words, then edge words (contiguous)
-    const uint32_t nWords = c.nVc + c.nEc;
-    if (nWords <= kConsLocalWords) {
-      for (uint32_t i = lane; i < nWords; i += 64) consLocal[i] = hostLoad32(src + i);
-      c.vc = consLocal;
-      c.ec = consLocal + c.nVc;
-    } else {  // (more than 2048 constraint words: the search reads them where the host put them, with plain loads)
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-      c.vc = src;
-      c.ec = P.cons + J.ec_off;
-    }
     const uint32_t pathBytes = c.tPad * c.nAgentsPad * 2;  // multiple of 32
     const uint32_t* psrc = (const uint32_t*)(P.paths + J.path_off);
     uint8_t* ldsPaths = smem + Geo::windowBytes(BG);
@@ -1197,15 +1258,14 @@ DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t*
     cj.nVc = c.nVc; cj.nEc = c.nEc;
     cj.obstWords = c.wpr;
     cj.nAgentsPad = EPS ? c.nAgentsPad : 0u; cj.tPad = c.tPad;
-    cj.maxExp = c.maxExp < 0 ? 0xFFFFFFFFu : (c.maxExp > 0xFFFFFFFEll ? 0xFFFFFFFEu : (uint32_t)c.maxExp);
+    cj.maxExp = clampMaxExp(c.maxExp);
     cj.rows = geoRows;
     if (TIERS == kTiersHeavy) {  // the wide geometry at its full size
       cj.openCap = Geo::kCap;
       cj.maxT = Geo::kMaxT < geoRows - 2u ? Geo::kMaxT : geoRows - 2u;
     } else {
-      // mrp_ll_configure_tiers: lds_nodes / 2 = open-list entries, lds_rows = time steps a search may use inside the tier
-      cj.openCap = P.lds_nodes / 2u < Geo::kCap ? P.lds_nodes / 2u : Geo::kCap;
-      cj.maxT = P.lds_rows >= 3u && P.lds_rows - 2u < Geo::kMaxT ? P.lds_rows - 2u : Geo::kMaxT;
+      cj.openCap = narrowOpenCap(P);
+      cj.maxT = narrowMaxT(P);
     }
     cj.taNoGoal = 0;
     cj.vc = (uint64_t)c.vc; cj.ec = (uint64_t)c.ec;
@@ -1214,12 +1274,7 @@ DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t*
     cj.parentTab = (uint64_t)arenaSlot;  // the arena's node area: unused while the search is in this tier
     cj.outPath = (uint64_t)outPath;
     cj.bitsG = (uint64_t)(arenaSlot + Geo::parentBytes(geoRows));  // (BG) ... and its (time, cell) bitmap behind it
-    {
-      auto w32 = (__attribute__((address_space(3))) uint32_t*)((wv::Lds)smem + ct::oJob);
-      const uint32_t* src = (const uint32_t*)&cj;
-#pragma unroll
-      for (uint32_t q = 0; q < sizeof(ct::CJob) / 4; ++q) w32[q] = src[q];
-    }
+    putCJob(smem, cj);
     const bool tableInLds = !EPS || c.nAgentsPad == 0u || c.pathsLds != nullptr;
 #ifndef MRP_LL_TRACE  // (the trace build uses prof[] for its phase counters)
     const uint64_t tl0 = __builtin_amdgcn_s_memrealtime();
@@ -1229,12 +1284,7 @@ DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t*
       crc = ct::compactSearch<EPS, false, BG, ct::Wide>((wv::Lds)smem);
     else
       crc = tableInLds ? ct::compactSearch<EPS, true, BG>((wv::Lds)smem) : ct::compactSearch<EPS, false, BG>((wv::Lds)smem);
-    ct::CRes cr;
-    {
-      auto r32 = (__attribute__((address_space(3))) const uint32_t*)((wv::Lds)smem + ct::oRes);
-      cr.status = (int32_t)rfl(r32[0]); cr.cost = (int32_t)rfl(r32[1]); cr.fmin = (int32_t)rfl(r32[2]);
-      cr.nStates = (int32_t)rfl(r32[3]); cr.expanded = rfl(r32[4]); cr.nodes = rfl(r32[5]);
-    }
+    const ct::CRes cr = getCRes(smem);
 #ifndef MRP_LL_TRACE
     // 100 MHz ticks / expansions in the compact tier (of a search that was handed over: until then); the wide geometry
     // reports into the arena tier's pair — "the searches that outgrew the narrow tier"
@@ -1268,17 +1318,7 @@ DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t*
   } else {
     if (!done) {
       // HBM tier view of this workgroup's arena slot
-      Mem<TierHbm> g;
-      {
-        uint8_t* p = arenaSlot;
-        g.nodes = (Mem<TierHbm>::PN32)p;             p += (size_t)P.arena_nodes * 16;
-        g.pos = nullptr;
-        g.open = (Mem<TierHbm>::PE)(p + 8);          p += (size_t)P.arena_nodes * 8 + 16;
-        g.focal = (Mem<TierHbm>::PE)(p + 8);         p += (size_t)P.arena_nodes * 8 + 16;
-        g.aux = (Mem<TierHbm>::PE)(p + 8);           p += (size_t)P.arena_nodes * 8 + 16;
-        g.bits = (Mem<TierHbm>::P32)p;
-        g.capNodes = P.arena_nodes; g.capHeap = P.arena_nodes; g.capRows = P.arena_rows; g.rowWords = P.arena_row_words;
-      }
+      const Mem<TierHbm> g = cutArena(P, arenaSlot);
       // ... and the view the arena tier actually runs on: the same arrays, the heaps' first nTop entries in this
       // workgroup's LDS (the compact tier's area, free once a search has left it)
       Mem<TierHyb> gh;
@@ -1394,9 +1434,9 @@ DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
     cj.nVc = 0; cj.nEc = 0;
     cj.obstWords = J.words_per_row;
     cj.nAgentsPad = npad; cj.tPad = kChainRows;
-    cj.maxExp = budget < 0 ? 0xFFFFFFFFu : (budget > 0xFFFFFFFEll ? 0xFFFFFFFEu : (uint32_t)budget);
-    cj.openCap = P.lds_nodes / 2u < ct::kCap ? P.lds_nodes / 2u : ct::kCap;
-    cj.maxT = P.lds_rows >= 3u && P.lds_rows - 2u < ct::kMaxT ? P.lds_rows - 2u : ct::kMaxT;
+    cj.maxExp = clampMaxExp(budget);
+    cj.openCap = narrowOpenCap(P);
+    cj.maxT = narrowMaxT(P);
     cj.taNoGoal = 0;
     cj.rows = 0;
     cj.vc = 0; cj.ec = 0;
@@ -1406,19 +1446,14 @@ DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
     cj.outPath = (uint64_t)outPath;
     cj.bitsG = (uint64_t)(arenaSlot + ct::kParentBytes);
     __syncthreads();
-    {
-      auto w32 = (__attribute__((address_space(3))) uint32_t*)((wv::Lds)smem + ct::oJob);
-      const uint32_t* src = (const uint32_t*)&cj;
-#pragma unroll
-      for (uint32_t q = 0; q < sizeof(ct::CJob) / 4; ++q) w32[q] = src[q];
-    }
+    putCJob(smem, cj);
 #ifndef MRP_LL_TRACE
     const uint64_t tl0 = __builtin_amdgcn_s_memrealtime();
 #endif
     const int32_t crc = ct::compactSearch<true, true, BG>((wv::Lds)smem);
-    auto r32 = (__attribute__((address_space(3))) const uint32_t*)((wv::Lds)smem + ct::oRes);
-    const int32_t cost = (int32_t)rfl(r32[1]), fmin = (int32_t)rfl(r32[2]), nStates = (int32_t)rfl(r32[3]);
-    const uint32_t expanded = rfl(r32[4]);
+    const ct::CRes cr = getCRes(smem);
+    const int32_t cost = cr.cost, fmin = cr.fmin, nStates = cr.nStates;
+    const uint32_t expanded = cr.expanded;
 #ifndef MRP_LL_TRACE
     res.prof[0] += (uint32_t)(__builtin_amdgcn_s_memrealtime() - tl0);
     res.prof[1] += expanded;
@@ -1500,80 +1535,158 @@ DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
   }
 }
 
-// MRP_LL_ASTAR_TA in the arena tier: AStar::search (a_star.hpp:63-161) over the Environment of example/cbs_ta.cpp:283-372
-// for the searches the compact tier cannot hold (more than 1023 open nodes, t > 61, f > 254, more than 64 + 64
-// constraints, maps beyond 32 x 32).  Same rules as ct::compactSearchTA — optional task, shortest-path heuristic from the
-// uploaded table, a Wait at the goal is free, so a state can be reached again with a smaller g and
-// `openSet.increase(handle)` (a_star.hpp:139-145) is live — on the arena's node records:
+// ---- the Environment of the task-assignment searches (example/cbs_ta.cpp:283-372 == example/ecbs_ta.cpp:283-445) -----
+// What runTaArena (AStar) and runJobTaEps (AStarEpsilon) share: optional task, shortest-path heuristic from the uploaded
+// table, a Wait at the goal is free, so a state can be reached again with a smaller g.  On the arena's records:
 //   node   {x | y << 8 | t << 16 | action << 27, parent, g, position of its entry in the open array}
-//   entry  TierHbm: key = (f asc, g desc), low word = node id
-//   status one word per (t, cell) in the (unused) focal + walk-queue areas of the slot: 0 unseen, node + 1 in the open
-//          list, bit 31 closed (stateToHeap + closedSet, a_star.hpp:116-117)
+//   status one word per (t, cell): 0 unseen, node + 1 in the open list, bit 31 closed (stateToHeap + closedSet,
+//          a_star.hpp:116-117); rows are zeroed as the search reaches them
 //   bits   (time, cell) bitmap: obstacles | vertex constraints (stateValid, cbs_ta.cpp:483-489), rows made on demand
+// Wave-uniform but for ecReg, dx, dy (one value per lane).
+struct TaProbe {  // lanes 0..4: the successor by Wait, Left, Right, Up, Down
+  uint32_t nxy, ncell, h, st;  // x | y << 8, cell index, heuristic, status word
+};
+struct TaEnv {
+  typedef TierHbm T;
+  uint32_t dimx, dimy, cells, gx, gy;
+  bool noGoal;
+  const uint16_t* heur;  // the task's shortest-path table, rows of heurStride halfwords
+  uint32_t heurStride;
+  uint32_t* status;
+  uint32_t rows, statusReady;  // time steps the table has room for / that have been zeroed
+  const uint32_t* ec;
+  uint32_t nEc, ecReg;  // ecReg: this lane's word of the first 64 edge constraints
+  int32_t dx, dy;
+
+  DEVI void init(const Ctx& c, bool noGoal_, const uint16_t* heur_, uint32_t heurStride_, uint32_t* status_, uint32_t rows_) {
+    const uint32_t lane = threadIdx.x;
+    dimx = c.dimx; dimy = c.dimy; cells = c.dimx * c.dimy; gx = c.gx; gy = c.gy;
+    noGoal = noGoal_; heur = heur_; heurStride = heurStride_;
+    status = status_; rows = rows_; statusReady = 0;
+    ec = c.ec; nEc = c.nEc;
+    ecReg = lane < nEc ? ec[lane] : 0xFFFFFFFFu;
+    dx = (lane == 2) - (lane == 1);
+    dy = (lane == 3) - (lane == 4);
+  }
+  // false: the task cannot be reached from the start (the reference's table says INT_MAX), or not within f's field
+  DEVI bool startH(uint32_t sx, uint32_t sy, uint32_t& h0) const {
+    h0 = noGoal ? 0u : heur[sy * heurStride + sx];
+    return h0 <= kFMax - 2u;
+  }
+  DEVI bool atGoal(uint32_t x, uint32_t y) const { return noGoal || (x == gx && y == gy); }
+  DEVI void zeroRows(uint32_t t1) {  // the status rows up to time step t1: nothing seen
+    while (statusReady <= t1) {
+      for (uint32_t i = threadIdx.x; i < cells; i += 64) status[statusReady * cells + i] = 0;
+      statusReady += 1;
+    }
+  }
+  DEVI void close(uint32_t x, uint32_t y, uint32_t t) { status[t * cells + y * dimx + x] = 0x80000000u; }
+  // getNeighbors (cbs_ta.cpp:321-367, ecbs_ta.cpp:392-438): Wait, Left, Right, Up, Down on lanes 0..4 — bounds, obstacle |
+  // vertex constraint (one bit of the bitmap), edge constraints by key (transitionValid, cbs_ta.cpp:491-496).  Returns the
+  // 5-bit mask of the valid successors of (x, y, t).
+  DEVI uint32_t probe(const Mem<T>& g, uint32_t x, uint32_t y, uint32_t t, TaProbe& p) const {
+    const uint32_t lane = threadIdx.x;
+    const uint32_t t1 = t + 1u;
+    const uint32_t nx = x + (uint32_t)dx, ny = y + (uint32_t)dy;
+    const bool inb = (lane < 5) && (nx < dimx) && (ny < dimy);
+    p.ncell = inb ? ny * dimx + nx : 0;
+    const uint32_t word = g.bits[t1 * g.rowWords + (p.ncell >> 5)];
+    p.h = (noGoal || !inb) ? 0u : heur[ny * heurStride + nx];
+    p.st = inb ? status[t1 * cells + p.ncell] : 0u;
+    p.nxy = nx | (ny << 8);
+    uint32_t mask = (uint32_t)(ballot64(inb && !((word >> (p.ncell & 31)) & 1u)) & 0x1Full);
+    if (nEc) {
+      const uint32_t base = (t << 19) | ((y * dimx + x) << 3);
+      uint32_t blocked = 0;
+      for (uint32_t j0 = 0; j0 < nEc; j0 += 64) {
+        const uint32_t d = (j0 == 0 ? ecReg : (j0 + lane < nEc ? ec[j0 + lane] : 0xFFFFFFFFu)) - base;
+#pragma unroll
+        for (uint32_t k = 0; k < 5; ++k) blocked |= ballot64(d == k) ? (1u << k) : 0u;
+      }
+      mask &= ~blocked;
+    }
+    return mask;
+  }
+  // a new node's h, f = g + h and g fit the heap entry's fields
+  DEVI static bool fits(uint32_t h, uint32_t g2) { return !(h > kFMax || g2 + h > kFMax - 2u || g2 > kGMask); }
+  DEVI void newNode(Mem<T>& g, uint32_t nid, uint32_t xy, uint32_t t, uint32_t action, uint32_t parent, uint32_t g2,
+                    uint32_t cell) {
+    u32x4 nn;
+    nn.x = xy | (t << 16) | (action << 27);
+    nn.y = parent;
+    nn.z = g2;
+    nn.w = 0;
+    ((Mem<T>::PNode4)g.nodes)[nid] = nn;
+    status[t * cells + cell] = nid + 1u;
+  }
+  // A node that is still in the open list, reached again by `action` from `parent` with g2 (a_star.hpp:130-152,
+  // a_star_epsilon.hpp:248-279).  False: not an improvement.  Otherwise cameFrom and g are replaced and the caller gets
+  // what it needs to re-key the open entry: its position, its f so far and fNew = f - (gOld - g2).
+  DEVI static bool rekey(Mem<T>& g, uint32_t nid, uint32_t action, uint32_t parent, uint32_t g2, uint32_t& gOld,
+                         uint32_t& posOld, uint32_t& fOld, uint32_t& fNew) {
+    const u32x4 on = ((Mem<T>::PNode4)g.nodes)[nid];
+    gOld = rfl(on.z);
+    posOld = rfl(on.w);
+    if (g2 >= gOld) return false;
+    fOld = T::f(ldU<T>(g.open, posOld));
+    fNew = fOld - (gOld - g2);
+    g.nodes[nid * 4 + 0] = (rfl(on.x) & 0x07FFFFFFu) | (action << 27);
+    g.nodes[nid * 4 + 1] = parent;
+    g.nodes[nid * 4 + 2] = g2;
+    return true;
+  }
+  // the solution's states, goal first, along the parents (all lanes, same address, same value)
+  DEVI static void walkPath(Mem<T>& g, uint32_t nid, uint32_t t, uint16_t* outPath) {
+    for (int32_t k = (int32_t)t; k >= 0; --k) {
+      const u32x4 pn = ((Mem<T>::PNode4)g.nodes)[nid];
+      outPath[k] = (uint16_t)(rfl(pn.x) & 0xFFFFu);
+      nid = rfl(pn.y);
+    }
+  }
+};
+
+// MRP_LL_ASTAR_TA in the arena tier: AStar::search (a_star.hpp:63-161) over TaEnv for the searches the compact tier cannot
+// hold (more than 1023 open nodes, t > 61, f > 254, more than 64 + 64 constraints, maps beyond 32 x 32).  Same rules as
+// ct::compactSearchTA; `openSet.increase(handle)` (a_star.hpp:139-145) is live.
+//   entry  TierHbm: key = (f asc, g desc), low word = node id
+//   status in the (unused) focal + walk-queue areas of the slot
 // Time steps: as many as the status table has room for (and the job's horizon); beyond: MRP_LL_CAP_HORIZON.
 DEVI void runTaArena(const LaunchParams& P, const DevJob& J, uint8_t* arenaSlot, DevResult& res, uint16_t* outPath,
                      const uint32_t* vc, const uint32_t* ec, const uint16_t* heur, uint32_t heurStride) {
   typedef TierHbm T;
-  const uint32_t lane = threadIdx.x;
-  Mem<T> g;
-  {
-    uint8_t* p = arenaSlot;
-    g.nodes = (Mem<T>::PN32)p;             p += (size_t)P.arena_nodes * 16;
-    g.pos = nullptr;
-    g.gOf = nullptr;
-    g.open = (Mem<T>::PE)(p + 8);          p += (size_t)P.arena_nodes * 8 + 16;
-    g.focal = (Mem<T>::PE)(p + 8);         // (the status table lives from here on)
-    g.aux = g.focal;
-    g.bits = (Mem<T>::P32)(arenaSlot + (size_t)P.arena_nodes * 16 + 3 * ((size_t)P.arena_nodes * 8 + 16));
-    g.capNodes = P.arena_nodes; g.capHeap = P.arena_nodes; g.capRows = P.arena_rows; g.rowWords = P.arena_row_words;
-  }
-  uint32_t* status = (uint32_t*)(arenaSlot + (size_t)P.arena_nodes * 16 + ((size_t)P.arena_nodes * 8 + 16));
-  const uint32_t dimx = J.dimx, dimy = J.dimy, cells = dimx * dimy;
+  Mem<T> g = cutArena(P, arenaSlot);
+  uint32_t* status = (uint32_t*)((uint8_t*)g.focal - 8);  // (the status table lives from here on)
+  g.aux = g.focal;
   const uint64_t statusWords = ((uint64_t)P.arena_nodes * 8 + 16) * 2 / 4;
-  uint32_t rows = (uint32_t)(statusWords / cells < P.arena_rows ? statusWords / cells : P.arena_rows);
-  const bool noGoal = (J.ctx_flags & kTaNoGoal) != 0;
   Ctx c;
-  c.dimx = dimx; c.dimy = dimy; c.wpr = J.words_per_row;
-  c.gx = J.gx; c.gy = J.gy; c.sx = J.sx; c.sy = J.sy;
-  c.lastGoal = J.last_goal_constraint;
+  fillCtx(c, J, P.maps, P.debug);
   c.w = 1.0f;
-  c.nVc = J.n_vc; c.nEc = J.n_ec;
   c.vc = vc; c.ec = ec;
-  c.obst = P.maps + J.map_word_off;
   c.paths = nullptr; c.pathsLds = nullptr;
   c.nAgentsPad = 0; c.tPad = 0;
-  c.maxExp = J.max_expansions;
-  c.debug = P.debug;
+  const uint32_t cells = c.dimx * c.dimy;
+  const uint32_t rows = (uint32_t)(statusWords / cells < P.arena_rows ? statusWords / cells : P.arena_rows);
   res.tier = 1;
   res.status = ST_NO_SOLUTION;
   if (rows < 2u) {
     res.status = ST_CAP_HORIZON;
     return;
   }
+  TaEnv env;
+  env.init(c, (J.ctx_flags & kTaNoGoal) != 0, heur, heurStride, status, rows);
   SState s;
   s.nNodes = 1; s.nOpen = 1; s.nFocal = 0; s.rowsReady = 0; s.bestF = 0; s.expansions = 0;
-  {  // the table: nothing seen (rows are zeroed as the bitmap's rows are made, below: `statusReady`)
-    const uint32_t sc = J.sy * dimx + J.sx;
-    const uint32_t h0 = noGoal ? 0u : heur[J.sy * heurStride + J.sx];
-    if (h0 > kFMax - 2u) {  // the task cannot be reached from here (the reference's table says INT_MAX), or not within f's field
+  {
+    uint32_t h0;
+    if (!env.startH(c.sx, c.sy, h0)) {
       res.status = ST_CAP_HORIZON;
       return;
     }
-    u32x4 n0;
-    n0.x = J.sx | (J.sy << 8) | (0u << 16) | (7u << 27);
-    n0.y = kNoParent;
-    n0.z = 0;
-    n0.w = 0;
-    ((Mem<T>::PNode4)g.nodes)[0] = n0;
     g.open[0] = T::pack(0, h0, 0, 0);
-    for (uint32_t i = lane; i < cells; i += 64) status[i] = 0;
+    env.zeroRows(0);
     __syncthreads();
-    status[sc] = 1u;  // node 0, in the open list
+    env.newNode(g, 0, c.sx | (c.sy << 8), 0, 7u, kNoParent, 0, c.sy * c.dimx + c.sx);  // node 0, in the open list
   }
-  uint32_t statusReady = 1;  // rows of the status table that have been zeroed
-  const uint32_t ecReg = lane < c.nEc ? c.ec[lane] : 0xFFFFFFFFu;
-  const int32_t dx = (lane == 2) - (lane == 1);
-  const int32_t dy = (lane == 3) - (lane == 4);
   for (;;) {
     if (s.nOpen == 0) {
       res.status = ST_NO_SOLUTION;
@@ -1584,7 +1697,7 @@ DEVI void runTaArena(const LaunchParams& P, const DevJob& J, uint8_t* arenaSlot,
     const u32x4 nd = ((Mem<T>::PNode4)g.nodes)[curId];
     const uint32_t xyt = rfl(nd.x);
     const uint32_t x = xyt & 0xFFu, y = (xyt >> 8) & 0xFFu, t = (xyt >> 16) & 0x7FFu;
-    const bool atGoal = noGoal || (x == c.gx && y == c.gy);
+    const bool atGoal = env.atGoal(x, y);
     s.expansions += 1;  // onExpandNode (a_star.hpp:87)
     if (c.maxExp >= 0 && s.expansions > c.maxExp) {
       res.status = ST_CAP_EXP;
@@ -1595,12 +1708,7 @@ DEVI void runTaArena(const LaunchParams& P, const DevJob& J, uint8_t* arenaSlot,
         res.status = ST_CAP_HORIZON;
         break;
       }
-      uint32_t nid = curId;
-      for (int32_t k = (int32_t)t; k >= 0; --k) {
-        const u32x4 pn = ((Mem<T>::PNode4)g.nodes)[nid];
-        outPath[k] = (uint16_t)(rfl(pn.x) & 0xFFFFu);
-        nid = rfl(pn.y);
-      }
+      TaEnv::walkPath(g, curId, t, outPath);
       res.status = ST_OK;
       res.cost = (int32_t)gcur;
       res.fmin = (int32_t)fcur;
@@ -1608,7 +1716,7 @@ DEVI void runTaArena(const LaunchParams& P, const DevJob& J, uint8_t* arenaSlot,
       break;
     }
     const uint32_t t1 = t + 1u;
-    if (t1 >= rows || t1 >= g.capRows) {
+    if (t1 >= env.rows || t1 >= g.capRows) {
       res.status = ST_CAP_HORIZON;
       break;
     }
@@ -1617,66 +1725,33 @@ DEVI void runTaArena(const LaunchParams& P, const DevJob& J, uint8_t* arenaSlot,
       break;
     }
     heapPop<T, 0, true>(g, g.open, s.nOpen);  // openSet.pop() (a_star.hpp:109)
-    status[t * cells + y * dimx + x] = 0x80000000u;  // closedSet.insert (a_star.hpp:110)
+    env.close(x, y, t);                       // closedSet.insert (a_star.hpp:110)
     ensureRows<T>(g, s, c, t1, (Mem<T>::P32)c.obst, false);
-    while (statusReady <= t1) {  // the status rows of the next time steps: nothing seen
-      for (uint32_t i = lane; i < cells; i += 64) status[statusReady * cells + i] = 0;
-      statusReady += 1;
-    }
+    env.zeroRows(t1);
     __syncthreads();
-    // getNeighbors (cbs_ta.cpp:321-367): Wait, Left, Right, Up, Down on lanes 0..4 — bounds, obstacle | vertex constraint
-    // (one bit of the bitmap), edge constraints by key
-    const uint32_t nx = x + (uint32_t)dx, ny = y + (uint32_t)dy;
-    const bool inb = (lane < 5) && (nx < dimx) && (ny < dimy);
-    const uint32_t ncell = inb ? ny * dimx + nx : 0;
-    const uint32_t word = g.bits[t1 * g.rowWords + (ncell >> 5)];
-    const uint32_t hN = (noGoal || !inb) ? 0u : heur[ny * heurStride + nx];
-    const uint32_t stN = inb ? status[t1 * cells + ncell] : 0u;
-    uint32_t mask = (uint32_t)(ballot64(inb && !((word >> (ncell & 31)) & 1u)) & 0x1Full);
-    if (c.nEc) {  // transitionValid (cbs_ta.cpp:491-496)
-      const uint32_t base = (t << 19) | ((y * dimx + x) << 3);
-      uint32_t blocked = 0;
-      for (uint32_t j0 = 0; j0 < c.nEc; j0 += 64) {
-        const uint32_t d = (j0 == 0 ? ecReg : (j0 + lane < c.nEc ? c.ec[j0 + lane] : 0xFFFFFFFFu)) - base;
-#pragma unroll
-        for (uint32_t k = 0; k < 5; ++k) blocked |= ballot64(d == k) ? (1u << k) : 0u;
-      }
-      mask &= ~blocked;
-    }
+    TaProbe pr;
+    const uint32_t mask = env.probe(g, x, y, t, pr);
     bool fail = false;
     for (uint32_t mm = mask; mm && !fail; mm &= mm - 1) {  // the new / rediscovered / closed cases of a_star.hpp:116-153, in order
       const uint32_t k = (uint32_t)__builtin_ctz(mm);
-      const uint32_t st = __builtin_amdgcn_readlane(stN, k);
+      const uint32_t st = __builtin_amdgcn_readlane(pr.st, k);
       if (st & 0x80000000u) continue;  // closed
-      const uint32_t nc = __builtin_amdgcn_readlane(ncell, k), h = __builtin_amdgcn_readlane(hN, k);
-      const uint32_t nxk = __builtin_amdgcn_readlane(nx, k), nyk = __builtin_amdgcn_readlane(ny, k);
       const uint32_t g2 = gcur + ((k == 0 && atGoal) ? 0u : 1u);  // tentative_gScore (a_star.hpp:118)
       if (st == 0) {  // not in the open list, not closed: a new node (a_star.hpp:120-129)
-        if (h > kFMax || g2 + h > kFMax - 2u || g2 > kGMask) {
+        const uint32_t h = __builtin_amdgcn_readlane(pr.h, k);
+        if (!TaEnv::fits(h, g2)) {
           res.status = ST_CAP_HORIZON;
           fail = true;
           break;
         }
         const uint32_t nid = s.nNodes++;
-        u32x4 nn;
-        nn.x = nxk | (nyk << 8) | (t1 << 16) | (k << 27);
-        nn.y = curId;
-        nn.z = g2;
-        nn.w = 0;
-        ((Mem<T>::PNode4)g.nodes)[nid] = nn;
-        status[t1 * cells + nc] = nid + 1u;
+        env.newNode(g, nid, __builtin_amdgcn_readlane(pr.nxy, k), t1, k, curId, g2, __builtin_amdgcn_readlane(pr.ncell, k));
         siftUp<T, 0, true>(g, g.open, s.nOpen, T::pack(0, g2 + h, g2, nid));
         s.nOpen += 1;
       } else {        // still in the open list (a_star.hpp:130-146)
         const uint32_t nid = st - 1u;
-        const u32x4 on = ((Mem<T>::PNode4)g.nodes)[nid];
-        const uint32_t gOld = rfl(on.z), posOld = rfl(on.w);
-        if (g2 >= gOld) continue;  // not an improvement (a_star.hpp:135-137)
-        const uint32_t fOld = T::f(ldU<T>(g.open, posOld));
-        const uint32_t fNew = fOld - (gOld - g2);  // fScore -= delta (a_star.hpp:141-142)
-        g.nodes[nid * 4 + 0] = (rfl(on.x) & 0x07FFFFFFu) | (k << 27);  // cameFrom is replaced (a_star.hpp:150-152)
-        g.nodes[nid * 4 + 1] = curId;
-        g.nodes[nid * 4 + 2] = g2;
+        uint32_t gOld, posOld, fOld, fNew;
+        if (!TaEnv::rekey(g, nid, k, curId, g2, gOld, posOld, fOld, fNew)) continue;  // (a_star.hpp:135-137)
         siftUp<T, 0, true>(g, g.open, posOld, T::pack(0, fNew, g2, nid));  // increase(handle)
       }
     }
@@ -1693,19 +1768,10 @@ DEVI void runTaArena(const LaunchParams& P, const DevJob& J, uint8_t* arenaSlot,
 // for maps up to 32 x 32, [dimy][dimx] beyond.
 DEVI void runJobTA(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t* arenaSlot, DevResult& res, uint16_t* outPath) {
   res.tier = 0;
-  const uint32_t lane = threadIdx.x;
-  // the constraint words leave host memory in one pass (the arena's copy area holds 2048 of them; longer lists are read in place)
-  uint32_t* consLocal = (uint32_t*)(arenaSlot + P.arena_scratch_off + (size_t)P.out_stride * 2);
-  const uint32_t* vc = consLocal;
-  const uint32_t* ec = consLocal + J.n_vc;
-  if (J.n_vc + J.n_ec <= kConsLocalWords) {
-    for (uint32_t i = lane; i < J.n_vc; i += 64) consLocal[i] = hostLoad32(P.cons + J.vc_off + i);
-    for (uint32_t i = lane; i < J.n_ec; i += 64) consLocal[J.n_vc + i] = hostLoad32(P.cons + J.ec_off + i);
-  } else {
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-    vc = P.cons + J.vc_off;
-    ec = P.cons + J.ec_off;
-  }
+  const uint32_t* vc;
+  const uint32_t* ec;
+  stageConstraints(P.cons, J.vc_off, J.n_vc, J.n_ec, (uint32_t*)(arenaSlot + P.arena_scratch_off + (size_t)P.out_stride * 2),
+                   vc, ec);
   __syncthreads();
   const bool small = J.dimx <= 32u && J.dimy <= 32u;
   const uint16_t* heur = (const uint16_t*)(P.maps + J.path_off);
@@ -1719,9 +1785,9 @@ DEVI void runJobTA(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
     cj.nVc = J.n_vc; cj.nEc = J.n_ec;
     cj.obstWords = J.words_per_row;
     cj.nAgentsPad = 0; cj.tPad = 0;
-    cj.maxExp = J.max_expansions < 0 ? 0xFFFFFFFFu : (J.max_expansions > 0xFFFFFFFEll ? 0xFFFFFFFEu : (uint32_t)J.max_expansions);
-    cj.openCap = P.lds_nodes / 2u < ct::kCap ? P.lds_nodes / 2u : ct::kCap;
-    cj.maxT = P.lds_rows >= 3u && P.lds_rows - 2u < ct::kMaxT ? P.lds_rows - 2u : ct::kMaxT;
+    cj.maxExp = clampMaxExp(J.max_expansions);
+    cj.openCap = narrowOpenCap(P);
+    cj.maxT = narrowMaxT(P);
     cj.taNoGoal = (J.ctx_flags & kTaNoGoal) ? 1u : 0u;
     cj.rows = 0;
     cj.vc = (uint64_t)vc; cj.ec = (uint64_t)ec;
@@ -1729,27 +1795,22 @@ DEVI void runJobTA(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
     cj.pathsG = (uint64_t)heur;
     cj.parentTab = (uint64_t)arenaSlot;
     cj.outPath = (uint64_t)outPath;
-    {
-      auto w32 = (__attribute__((address_space(3))) uint32_t*)((wv::Lds)smem + ct::oJob);
-      const uint32_t* src = (const uint32_t*)&cj;
-#pragma unroll
-      for (uint32_t q = 0; q < sizeof(ct::CJob) / 4; ++q) w32[q] = src[q];
-    }
+    putCJob(smem, cj);
     const uint64_t tl0 = __builtin_amdgcn_s_memrealtime();
     const int32_t crc = ct::compactSearchTA((wv::Lds)smem);
-    auto r32 = (__attribute__((address_space(3))) const uint32_t*)((wv::Lds)smem + ct::oRes);
+    const ct::CRes cr = getCRes(smem);
     res.prof[0] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - tl0);
-    res.prof[1] = rfl(r32[4]);
+    res.prof[1] = cr.expanded;
     if (crc != ct::C_CAP_NODES && crc != ct::C_CAP_HORIZON) {  // an answer (C_OK / C_NO_SOLUTION / C_CAP_EXP == the ST_ codes)
       res.status = crc;
-      res.cost = (int32_t)rfl(r32[1]);
-      res.fmin = (int32_t)rfl(r32[2]);
-      res.n_states = (int32_t)rfl(r32[3]);
-      res.expanded = rfl(r32[4]);
-      res.nodes_created = rfl(r32[5]);
+      res.cost = cr.cost;
+      res.fmin = cr.fmin;
+      res.n_states = cr.nStates;
+      res.expanded = cr.expanded;
+      res.nodes_created = cr.nodes;
       return;
     }
-    res.prof[6] = rfl(r32[4]);  // expansions thrown away with the attempt
+    res.prof[6] = cr.expanded;  // expansions thrown away with the attempt
     res.prof[7] = 1;
     __syncthreads();
   }
@@ -1761,8 +1822,8 @@ DEVI void runJobTA(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
 
 // ---- MRP_LL_ASTAR_EPS_TA: the low level of ECBS with task assignment ---------------------------------------------------
 // AStarEpsilon::search (a_star_epsilon.hpp:86-285) over the Environment of example/ecbs_ta.cpp:283-445 — what
-// ecbs_ta.hpp:498-499 instantiates.  The Environment is runTaArena's (optional task, shortest-path heuristic from the
-// uploaded table, a Wait at the goal is free), the focal heuristics are example/ecbs.cpp's, taken at the successor's TIME
+// ecbs_ta.hpp:498-499 instantiates.  The Environment is TaEnv, shared with runTaArena (optional task, shortest-path
+// heuristic from the uploaded table, a Wait at the goal is free), the focal heuristics are example/ecbs.cpp's, taken at the successor's TIME
 // (ecbs_ta.cpp:314-344).  Because g != time a state can be discovered again with a smaller g, and this is the one search of
 // the reference in which a_star_epsilon.hpp:249-269 is live: g and f drop, `openSet.increase(handle)` sifts the open entry
 // up, focalH keeps its value, and a node that already sits in the focal list is NOT moved there — the reference's focal
@@ -1853,17 +1914,15 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
   typedef TierFocalPos TF;
   typedef T::E E;
   const uint32_t lane = threadIdx.x;
-  const uint32_t dimx = rfl(Jp->dimx), dimy = rfl(Jp->dimy), cells = dimx * dimy;
-  const uint32_t sx = rfl(Jp->sx), sy = rfl(Jp->sy), gx = rfl(Jp->gx), gy = rfl(Jp->gy);
-  const uint32_t nVc = rfl(Jp->n_vc), nEc = rfl(Jp->n_ec), vcOff = rfl(Jp->vc_off), ecOff = rfl(Jp->ec_off);
-  const uint32_t nAgentsPad = rfl(Jp->n_agents_pad), tPad = rfl(Jp->t_pad), pathOff = rfl(Jp->path_off);
-  const bool noGoal = (rfl(Jp->ctx_flags) & kTaNoGoal) != 0;
-  const int32_t lastGoal = rfli(Jp->last_goal_constraint);
-  const float w = __builtin_bit_cast(float, rfl(__builtin_bit_cast(uint32_t, Jp->w)));
-  const int64_t maxExp = (int64_t)rfl64((uint64_t)Jp->max_expansions);
-  const bool small = dimx <= 32u && dimy <= 32u;
-  const uint16_t* heur = (const uint16_t*)(maps + rfl(Jp->heur_off));
-  const uint32_t heurStride = small ? 32u : dimx;
+  // (arguments arrive in vector registers: with these two wave-uniform, so are rows, capN and `run` below, and TaEnv's
+  // row counter stays scalar)
+  arenaNodes = rfl(arenaNodes); arenaRows = rfl(arenaRows);
+  Ctx c;
+  fillCtx<true>(c, *Jp, maps, nullptr);
+  c.pathsLds = nullptr;
+  const uint32_t dimx = c.dimx, cells = dimx * c.dimy, tPad = c.tPad;
+  const float w = c.w;
+  const bool small = dimx <= 32u && c.dimy <= 32u;
 
   int32_t status = ST_NO_SOLUTION, cost = 0, fmin = 0, nStates = 0;
   SState s;
@@ -1874,29 +1933,10 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
   uint16_t* outPath = (uint16_t*)scratch;
   uint32_t* consLocal = (uint32_t*)(scratch + (size_t)outStride * 2);
   uint8_t* pathsArena = (uint8_t*)(consLocal + kConsLocalWords);
-  Ctx c;
-  c.dimx = dimx; c.dimy = dimy; c.wpr = rfl(Jp->words_per_row);
-  c.gx = gx; c.gy = gy; c.sx = sx; c.sy = sy;
-  c.lastGoal = lastGoal;
-  c.w = w;
-  c.nVc = nVc; c.nEc = nEc;
-  c.obst = maps + rfl(Jp->map_word_off);
-  c.pathsLds = nullptr;
-  c.nAgentsPad = nAgentsPad; c.tPad = tPad;
-  c.maxExp = maxExp;
-  c.debug = nullptr;
-  if (nVc + nEc <= kConsLocalWords) {
-    for (uint32_t i = lane; i < nVc; i += 64) consLocal[i] = hostLoad32(consHost + vcOff + i);
-    for (uint32_t i = lane; i < nEc; i += 64) consLocal[nVc + i] = hostLoad32(consHost + ecOff + i);
-    c.vc = consLocal;
-    c.ec = consLocal + nVc;
-  } else {
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-    c.vc = consHost + vcOff;
-    c.ec = consHost + ecOff;
-  }
+  stageConstraints(consHost, rfl(Jp->vc_off), c.nVc, c.nEc, consLocal, c.vc, c.ec);
   {
-    const uint32_t pathBytes = tPad * nAgentsPad * 2;  // multiple of 32
+    const uint32_t pathOff = rfl(Jp->path_off);
+    const uint32_t pathBytes = tPad * c.nAgentsPad * 2;  // multiple of 32
     if (pathBytes == 0) {
       c.paths = nullptr;
       c.nAgentsPad = 0;
@@ -1922,41 +1962,34 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
   const uint32_t capN = (uint32_t)capN64 & ~1u;
   Mem<T> g;
   Mem<TF> gf;
-  uint32_t* stTab = (uint32_t*)arenaSlot;
   {
     uint8_t* p = arenaSlot + statusBytes;
     g.nodes = (Mem<T>::PN32)p;             p += (size_t)capN * 16;
     gf.nodes = (Mem<TF>::PN32)p;           p += (size_t)capN * 8;
-    g.open = (Mem<T>::PE)(p + 8);          p += (size_t)capN * 8 + 16;
-    g.focal = (Mem<T>::PE)(p + 8);         p += (size_t)capN * 8 + 16;
-    g.aux = (Mem<T>::PE)(p + 8);
+    cutHeaps(g, p, capN);
     g.pos = nullptr; g.gOf = nullptr;
     g.bits = (Mem<T>::P32)(arenaSlot + area);
-    g.capNodes = capN; g.capHeap = capN; g.capRows = arenaRows; g.rowWords = arenaRowWords;
+    g.capRows = arenaRows; g.rowWords = arenaRowWords;
     gf.pos = nullptr; gf.gOf = nullptr;
     gf.open = g.open; gf.focal = g.focal; gf.aux = g.aux; gf.bits = g.bits;
     gf.capNodes = capN; gf.capHeap = capN; gf.capRows = arenaRows; gf.rowWords = arenaRowWords;
   }
   typedef __attribute__((address_space(1))) u32x2* PNodeB;
   const PNodeB nodesB = (PNodeB)gf.nodes;
+  TaEnv env;
+  env.init(c, (rfl(Jp->ctx_flags) & kTaNoGoal) != 0, (const uint16_t*)(maps + rfl(Jp->heur_off)), small ? 32u : dimx,
+           (uint32_t*)arenaSlot, rows);
 
   bool run = true;
-  const uint32_t h0 = noGoal ? 0u : heur[sy * heurStride + sx];
-  if (rows < 2u || h0 > kFMax - 2u) {  // no room for a second time step / the task is unreachable or beyond f's field
+  uint32_t h0 = 0;
+  if (rows < 2u || !env.startH(c.sx, c.sy, h0)) {  // no room for a second time step / the task is out of reach
     status = ST_CAP_HORIZON;
     run = false;
   } else if (capN < 16u) {
     status = ST_CAP_NODES;
     run = false;
   }
-  uint32_t statusReady = 1;  // rows of the status table that have been zeroed
   if (run) {
-    u32x4 n0;
-    n0.x = sx | (sy << 8) | (0u << 16) | (7u << 27);
-    n0.y = kNoParent;
-    n0.z = 0;
-    n0.w = 0;
-    ((Mem<T>::PNode4)g.nodes)[0] = n0;
     u32x2 b0;
     b0.x = 0;
     b0.y = 0;  // focal position 0
@@ -1964,15 +1997,12 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
     const E e0 = T::pack(0, h0, 0, 0);
     g.open[0] = e0;
     g.focal[0] = e0;
-    for (uint32_t i = lane; i < cells; i += 64) stTab[i] = 0;
+    env.zeroRows(0);
     __syncthreads();
-    stTab[sy * dimx + sx] = 1u;  // node 0, in the open list
+    env.newNode(g, 0, c.sx | (c.sy << 8), 0, 7u, kNoParent, 0, c.sy * dimx + c.sx);  // node 0, in the open list
     s.nNodes = 1; s.nOpen = 1; s.nFocal = 1;
     s.bestF = (int32_t)h0;
   }
-  const uint32_t ecReg = lane < nEc ? c.ec[lane] : 0xFFFFFFFFu;
-  const int32_t dx = (lane == 2) - (lane == 1);
-  const int32_t dy = (lane == 3) - (lane == 4);
   while (run) {
     if (s.nOpen == 0) {
       status = ST_NO_SOLUTION;
@@ -1997,23 +2027,18 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
     const uint32_t xyt = rfl(nd.x), curPos = rfl(nd.w);
     const uint32_t x = xyt & 0xFFu, y = (xyt >> 8) & 0xFFu, t = (xyt >> 16) & 0x7FFu;
     const uint32_t xy = xyt & 0xFFFFu;
-    const bool atGoal = noGoal || (x == gx && y == gy);
+    const bool atGoal = env.atGoal(x, y);
     s.expansions += 1;  // onExpandNode (a_star_epsilon.hpp:193) — counts the goal pop too
-    if (maxExp >= 0 && s.expansions > maxExp) {
+    if (c.maxExp >= 0 && s.expansions > c.maxExp) {
       status = ST_CAP_EXP;
       break;
     }
-    if (atGoal && (int32_t)t > lastGoal) {  // isSolution (ecbs_ta.cpp:384-390) -> a_star_epsilon.hpp:195-213
+    if (atGoal && (int32_t)t > c.lastGoal) {  // isSolution (ecbs_ta.cpp:384-390) -> a_star_epsilon.hpp:195-213
       if (t + 1u > outStride) {
         status = ST_CAP_HORIZON;
         break;
       }
-      uint32_t nid = curId;
-      for (int32_t k = (int32_t)t; k >= 0; --k) {
-        const u32x4 pn = ((Mem<T>::PNode4)g.nodes)[nid];
-        outPath[k] = (uint16_t)(rfl(pn.x) & 0xFFFFu);  // all lanes, same address, same value
-        nid = rfl(pn.y);
-      }
+      TaEnv::walkPath(g, curId, t, outPath);
       status = ST_OK;
       cost = (int32_t)gcur;
       fmin = (int32_t)T::f(topE);  // openSet.top().fScore (a_star_epsilon.hpp:210)
@@ -2021,7 +2046,7 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
       break;
     }
     const uint32_t t1 = t + 1u;
-    if (t1 >= rows || t1 >= g.capRows) {
+    if (t1 >= env.rows || t1 >= g.capRows) {
       status = ST_CAP_HORIZON;
       break;
     }
@@ -2049,47 +2074,25 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
     }
     heapPop<TF, 1, true>(gf, gf.focal, s.nFocal);  // focalSet.pop()          (a_star_epsilon.hpp:215)
     eraseOpen<T>(g, s.nOpen, curPos);              // openSet.erase(handle)   (:216)
-    stTab[t * cells + y * dimx + x] = 0x80000000u;  // stateToHeap.erase, closedSet.insert (:217-218)
+    env.close(x, y, t);                            // stateToHeap.erase, closedSet.insert (:217-218)
     ensureRows<T>(g, s, c, t1, (Mem<T>::P32)c.obst, false);
-    while (statusReady <= t1) {  // the status rows of the next time steps: nothing seen
-      for (uint32_t i = lane; i < cells; i += 64) stTab[statusReady * cells + i] = 0;
-      statusReady += 1;
-    }
+    env.zeroRows(t1);
     __syncthreads();
-    // getNeighbors (ecbs_ta.cpp:392-438): Wait, Left, Right, Up, Down on lanes 0..4 — bounds, obstacle | vertex constraint
-    // (one bit of the bitmap), edge constraints by key
-    const uint32_t nx = x + (uint32_t)dx, ny = y + (uint32_t)dy;
-    const bool inb = (lane < 5) && (nx < dimx) && (ny < dimy);
-    const uint32_t ncell = inb ? ny * dimx + nx : 0;
-    const uint32_t word = g.bits[t1 * g.rowWords + (ncell >> 5)];
-    const uint32_t hN = (noGoal || !inb) ? 0u : heur[ny * heurStride + nx];
-    const uint32_t stN = inb ? stTab[t1 * cells + ncell] : 0u;
-    const uint32_t nxyL = nx | (ny << 8);
-    uint32_t mask = (uint32_t)(ballot64(inb && !((word >> (ncell & 31)) & 1u)) & 0x1Full);
-    if (nEc) {  // transitionValid
-      const uint32_t base = (t << 19) | ((y * dimx + x) << 3);
-      uint32_t blocked = 0;
-      for (uint32_t j0 = 0; j0 < nEc; j0 += 64) {
-        const uint32_t d = (j0 == 0 ? ecReg : (j0 + lane < nEc ? c.ec[j0 + lane] : 0xFFFFFFFFu)) - base;
-#pragma unroll
-        for (uint32_t k = 0; k < 5; ++k) blocked |= ballot64(d == k) ? (1u << k) : 0u;
-      }
-      mask &= ~blocked;
-    }
+    TaProbe pr;
+    const uint32_t mask = env.probe(g, x, y, t, pr);
     const float bound = __fmul_rn((float)s.bestF, w);  // bestFScore * m_w (a_star_epsilon.hpp:240,265), binary32
     const uint64_t swap0 = ballot64(b0 == xy);
     const uint64_t swap1 = ballot64(b1 == xy);
     bool fail = false;
     for (uint32_t mm = mask; mm; mm &= mm - 1) {  // a_star_epsilon.hpp:223-281, neighbour by neighbour
       const uint32_t k = (uint32_t)__builtin_ctz(mm);
-      const uint32_t st = __builtin_amdgcn_readlane(stN, k);
+      const uint32_t st = __builtin_amdgcn_readlane(pr.st, k);
       if (st & 0x80000000u) continue;  // closed (:224)
-      const uint32_t nc = __builtin_amdgcn_readlane(ncell, k);
       const uint32_t g2 = gcur + ((k == 0 && atGoal) ? 0u : 1u);  // tentative_gScore (:225)
       if (st == 0) {  // a new node (:227-247)
-        const uint32_t h = __builtin_amdgcn_readlane(hN, k);
-        const uint32_t cc = __builtin_amdgcn_readlane(nxyL, k);
-        if (h > kFMax || g2 + h > kFMax - 2u || g2 > kGMask) {
+        const uint32_t h = __builtin_amdgcn_readlane(pr.h, k);
+        const uint32_t cc = __builtin_amdgcn_readlane(pr.nxy, k);
+        if (!TaEnv::fits(h, g2)) {
           status = ST_CAP_HORIZON;
           fail = true;
           break;
@@ -2117,17 +2120,11 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
         }
         const uint32_t f2 = g2 + h;
         const uint32_t nid = s.nNodes++;
-        u32x4 nn;
-        nn.x = cc | (t1 << 16) | (k << 27);
-        nn.y = curId;
-        nn.z = g2;
-        nn.w = 0;
-        ((Mem<T>::PNode4)g.nodes)[nid] = nn;
+        env.newNode(g, nid, cc, t1, k, curId, g2, __builtin_amdgcn_readlane(pr.ncell, k));
         u32x2 nb;
         nb.x = fh;
         nb.y = kNoPos;
         nodesB[nid] = nb;
-        stTab[t1 * cells + nc] = nid + 1u;
         const E e = T::pack(fh, f2, g2, nid);
         siftUp<T, 0, true>(g, g.open, s.nOpen, e);  // openSet.push (:237)
         s.nOpen += 1;
@@ -2137,16 +2134,10 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
         }
       } else {  // still in the open list (:248-270)
         const uint32_t nid = st - 1u;
-        const u32x4 on = ((Mem<T>::PNode4)g.nodes)[nid];
-        const uint32_t gOld = rfl(on.z), posOld = rfl(on.w);
-        if (g2 >= gOld) continue;  // (:251-253)
+        uint32_t gOld, posOld, fOld, fNew;
+        if (!TaEnv::rekey(g, nid, k, curId, g2, gOld, posOld, fOld, fNew)) continue;  // (:251-253)
         const u32x2 ob = nodesB[nid];
         const uint32_t fhOld = rfl(ob.x), fpos = rfl(ob.y);
-        const uint32_t fOld = T::f(ldU<T>(g.open, posOld));
-        const uint32_t fNew = fOld - (gOld - g2);  // fScore -= delta (:259-261)
-        g.nodes[nid * 4 + 0] = (rfl(on.x) & 0x07FFFFFFu) | (k << 27);  // cameFrom is replaced (:275-279)
-        g.nodes[nid * 4 + 1] = curId;
-        g.nodes[nid * 4 + 2] = g2;
         const E e = T::pack(fhOld, fNew, g2, nid);  // focalH keeps its value
         siftUp<T, 0, true>(g, g.open, posOld, e);   // openSet.increase(handle) (:262)
         if (fpos != kNoPos) {
@@ -2754,19 +2745,8 @@ DEVI void runSipp(const LaunchParams& P, const DevJob& J, uint8_t* arenaSlot, ui
   const uint32_t K = J.n_vc, totalIv = J.n_ec;
   const uint32_t gx = J.gx, gy = J.gy;
   typedef TierHbm T;
-  Mem<T> g;
-  Mem<T>::PNode4 gNodes;
-  {
-    uint8_t* p = arenaSlot;
-    g.nodes = (Mem<T>::PN32)p;
-    gNodes = (Mem<T>::PNode4)p;                  p += (size_t)P.arena_nodes * 16;
-    g.pos = nullptr;
-    g.open = (Mem<T>::PE)(p + 8);                p += (size_t)P.arena_nodes * 8 + 16;
-    g.focal = (Mem<T>::PE)(p + 8);               p += (size_t)P.arena_nodes * 8 + 16;
-    g.aux = (Mem<T>::PE)(p + 8);                 p += (size_t)P.arena_nodes * 8 + 16;
-    g.bits = (Mem<T>::P32)p;
-    g.capNodes = P.arena_nodes; g.capHeap = P.arena_nodes; g.capRows = P.arena_rows; g.rowWords = P.arena_row_words;
-  }
+  Mem<T> g = cutArena(P, arenaSlot);
+  const Mem<T>::PNode4 gNodes = (Mem<T>::PNode4)g.nodes;
   uint8_t* scratch = arenaSlot + P.arena_scratch_off;
   uint32_t* tab = (uint32_t*)((uint32_t*)(scratch + (size_t)P.out_stride * 2) + kConsLocalWords);  // path-table area
   SippView<RES> tv;

@@ -828,7 +828,7 @@ bool packJob(mrp_ll_ctx* ctx, const mrp_ll_job& j, ConsSink& cs, PathSink& ps, D
   }
   d.n_vc = static_cast<uint32_t>(cs.size()) - d.vc_off;
   d.last_goal_constraint = lastGoal;
-  d.ec_off = static_cast<uint32_t>(cs.size());
+  d.ec_off = static_cast<uint32_t>(cs.size());  // == vc_off + n_vc: the kernels copy both lists as one run (stageConstraints)
   for (int i = 0; i < j.n_edge_constraints; ++i) {
     const int32_t* e = j.edge_constraints + 5 * i;
     int k = neighborIndexFromDelta(e[3] - e[1], e[4] - e[2]);
