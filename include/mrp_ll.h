@@ -53,8 +53,8 @@ extern "C" {
 #define MRP_LL_ASTAR_TA 3  /* a_star.hpp AStar::search over the Environment of example/cbs_ta.cpp:283-372 — the low level of */
                            /* CBS with task assignment ONLY (cbs_ta.hpp:106-109,155-158,196-199; ecbs_ta.hpp runs          */
                            /* AStarEpsilon over the same Environment: MRP_LL_ASTAR_EPS_TA below): optional goal            */
-                           /* (MRP_LL_JOB_NO_GOAL), h = an uploaded shortest-path table                                    */
-                           /* (mrp_ll_upload_heuristic), Wait costs 0 at the goal, so g != time and decrease-key is live.  */
+                           /* (MRP_LL_JOB_NO_GOAL), h = a shortest-path table (mrp_ll_upload_heuristic, or computed on the   */
+                           /* device: mrp_ll_compute_heuristics), Wait costs 0 at the goal, so g != time and decrease-key is live. */
                            /* Two tiers, like the other searches: the LDS tier (maps up to 32 x 32, at most 64 vertex and  */
                            /* 64 edge constraints, time steps <= 61, f <= 254, 1023 open nodes) and, for everything beyond */
                            /* it, the arena tier (any map the context accepts, any number of constraints; limits:           */
@@ -161,7 +161,7 @@ typedef struct mrp_ll_job {
   const int32_t* path_ids;
   int32_t result_path_id;  /* with MRP_LL_JOB_STORE_RESULT: the slot (0 .. n_slots-1) that also receives the result path */
   int32_t flags;           /* MRP_LL_JOB_* bits; 0 = none */
-  /* MRP_LL_ASTAR_TA only: the shortest-path table of this job's goal cell (mrp_ll_upload_heuristic); ignored with
+  /* MRP_LL_ASTAR_TA / _EPS_TA: the shortest-path table of this job's goal cell (mrp_ll_upload_heuristic or mrp_ll_compute_heuristics); ignored with
    * MRP_LL_JOB_NO_GOAL.  (Zero-initialised jobs of the other algorithms never look at it.) */
   int32_t heuristic_id;
   int32_t chain_count;     /* MRP_LL_JOB_ROOT_CHAIN: plan at most this many agents (0 = all from agent_idx on): a caller with many
@@ -241,9 +241,33 @@ int mrp_ll_upload_map(mrp_ll_ctx* ctx, int32_t dimx, int32_t dimy, int32_t n_obs
 
 /* MRP_LL_ASTAR_TA: the heuristic of one goal cell of map `map_id` — dist[dimy][dimx] (row-major, dist[y * dimx + x]) =
  * ShortestPathHeuristic::getValue(cell, goal) (example/shortest_path_heuristic.hpp:56-60: all-pairs shortest paths on the
- * free cells; INT32_MAX = unreachable).  Computing it is the caller's business (the reference does it once per
- * Environment, cbs_ta.cpp:267); the engine keeps it next to the maps (any map size).  MRP_LL_E_BUSY during a session. */
+ * free cells; INT32_MAX = unreachable), computed by the caller (the reference does it once per Environment,
+ * cbs_ta.cpp:267); the engine keeps it next to the maps (any map size).  A caller without a table of its own lets the
+ * device compute it from the uploaded map: mrp_ll_compute_heuristics below.  MRP_LL_E_BUSY during a session. */
 int mrp_ll_upload_heuristic(mrp_ll_ctx* ctx, int32_t map_id, const int32_t* dist, int32_t* heuristic_id);
+
+/* The same tables computed where they are consumed: n tables in ONE kernel launch (one wavefront each, whatever n is),
+ * table k = ShortestPathHeuristic::getValue(cell, goal k) (example/shortest_path_heuristic.hpp:12-63) on map map_ids[k]
+ * for the goal cell goals_xy[k] = x, y.  The graph is the reference's (shortest_path_heuristic.hpp:22-45: a vertex per cell,
+ * an edge between two horizontally or vertically adjacent cells when BOTH are free), and Floyd-Warshall's d[v][v] = 0 holds
+ * for every vertex: a goal on an obstacle cell gives 0 at that cell and unreachable everywhere else.  heuristic_ids[k] are
+ * ordinary heuristic ids — interchangeable with mrp_ll_upload_heuristic's in mrp_ll_job.heuristic_id — and stay valid, like
+ * those, until mrp_ll_release_maps; the tables live on the device only (no host copy is made or kept) and survive every
+ * later upload or computation, also when the device buffer has to grow.
+ * MRP_LL_E_INVALID: NULL pointer, unknown map id, goal outside its map — no id is created, the context is unchanged.
+ * MRP_LL_E_BUSY while a session is active or a batch is in flight (the buffer may have to grow).  n == 0 succeeds. */
+int mrp_ll_compute_heuristics(mrp_ll_ctx* ctx, int32_t n, const int32_t* map_ids, const int32_t* goals_xy /* [n][2] */,
+                              int32_t* heuristic_ids /* [n] */);
+/* One table back on the host: dist[dimy][dimx] as mrp_ll_upload_heuristic takes it (dist[y * dimx + x], INT32_MAX =
+ * unreachable), for computed AND uploaded ids (an uploaded value beyond 65534 comes back as INT32_MAX: the table holds
+ * halfwords).  MRP_LL_E_INVALID: NULL pointer, unknown id.  MRP_LL_E_BUSY as above. */
+int mrp_ll_read_heuristic(mrp_ll_ctx* ctx, int32_t heuristic_id, int32_t* dist);
+/* out[k] = table heuristic_ids[k] at the cell cells_xy[k] = x, y (INT32_MAX = unreachable): what the assignment's cost
+ * matrix needs — cost(agent i, task j) = getValue(start_i, goal_j), example/cbs_ta.cpp:272-279 — in one gather launch and
+ * one copy of n words, without moving a table.  MRP_LL_E_INVALID: NULL pointer, unknown id, cell outside the table's map.
+ * MRP_LL_E_BUSY as above.  n == 0 succeeds. */
+int mrp_ll_heuristic_lookup(mrp_ll_ctx* ctx, int32_t n, const int32_t* heuristic_ids, const int32_t* cells_xy /* [n][2] */,
+                            int32_t* out /* [n] */);
 
 /* Copies every map uploaded so far to the device now (otherwise done lazily by the next submit / session_begin). */
 int mrp_ll_sync_maps(mrp_ll_ctx* ctx);

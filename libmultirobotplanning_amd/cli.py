@@ -7,6 +7,7 @@
                                                                                    (example/mapf_prioritized_sipp.cpp:157-295)
     python -m libmultirobotplanning_amd.cli a_star --startX 0 --startY 0 --goalX 2 --goalY 1 -m map.txt -o out.yaml
                                                                                    (example/a_star.cpp:128-213)
+    python -m libmultirobotplanning_amd.cli shortest_path_heuristic -i in.yaml     (example/shortest_path_heuristic.cpp:40-156)
 
 ecbs / cbs   input  (ecbs.cpp:554-574): map.dimensions [x, y], map.obstacles [[x, y]..], agents[].{name,start,goal}
              output (ecbs.cpp:584-617): statistics.{cost, makespan, runtime, highLevelExpanded, lowLevelExpanded} and
@@ -18,6 +19,10 @@ mapf_prioritized_sipp  input as ecbs; output (mapf_prioritized_sipp.cpp:211-272)
 a_star       text map, '#' = obstacle (a_star.cpp:163-178: width = longest line, height = lines incl. the empty one after
              the last newline, minus 1); output schedule.agent1 with t = index (a_star.cpp:207-213).  Host plumbing
              (BASELINE.json configs[0]): no GPU involved.
+shortest_path_heuristic  input: map.dimensions, map.obstacles (agents are not read); prints what the reference's example
+             prints, ShortestPathHeuristic::getValue((0, 0), (3, 0)) (shortest_path_heuristic.cpp:152-153; INT_MAX when
+             there is no path) — the table of the goal cell is computed on the device (mrp_ll_compute_heuristics) and the
+             one entry looked up there.  -o is accepted and, as in the reference (whose CSV dump is compiled out), unused.
 On failure the reference prints "Planning NOT successful!" (and, for ecbs / cbs, writes nothing); so does this tool.
 Several input files may be given to ecbs / cbs / mapf_prioritized_sipp (-i a.yaml -i b.yaml ... with matching -o): they
 are solved as one GPU batch.  Inputs are read with the package's own YAML-subset reader (yaml_subset.py): no PyYAML.
@@ -180,11 +185,31 @@ def main_a_star(args, ap) -> int:
     return 0
 
 
+def main_shortest_path_heuristic(args, ap) -> int:
+    from . import ll
+    if len(args.input) != 1:
+        ap.error("shortest_path_heuristic takes one -i")
+    cfg = yaml_subset.load(args.input[0])
+    dim = cfg["map"]["dimensions"]
+    dimx, dimy = int(dim[0]), int(dim[1])
+    if dimx < 4 or dimy < 1:
+        ap.error("shortest_path_heuristic asks for getValue((0, 0), (3, 0)): the map must be at least 4 cells wide")
+    obstacles = [[int(o[0]), int(o[1])] for o in (cfg["map"].get("obstacles") or [])]
+    eng = ll.LowLevelEngine(device=args.device, n_tickets=1, slots=16, max_cells=max(4096, dimx * dimy))
+    try:
+        mid = eng.upload_map(dimx, dimy, obstacles)
+        hid = eng.compute_heuristics([mid], [[3, 0]])[0]
+        print(int(eng.heuristic_lookup([hid], [[0, 0]])[0]))
+    finally:
+        eng.close()
+    return 0
+
+
 def main(argv: List[str] = None) -> int:
     ap = argparse.ArgumentParser(prog="libmultirobotplanning_amd.cli")
-    ap.add_argument("algo", choices=["ecbs", "cbs", "sipp", "mapf_prioritized_sipp", "a_star"])
+    ap.add_argument("algo", choices=["ecbs", "cbs", "sipp", "mapf_prioritized_sipp", "a_star", "shortest_path_heuristic"])
     ap.add_argument("-i", "--input", action="append", default=[], help="input file (YAML)")
-    ap.add_argument("-o", "--output", action="append", required=True, help="output file (YAML)")
+    ap.add_argument("-o", "--output", action="append", default=[], help="output file (YAML)")
     ap.add_argument("-w", "--suboptimality", type=float, default=1.0, help="suboptimality bound (ecbs)")
     ap.add_argument("-m", "--map", help="input map (txt) (a_star)")
     for k in ("startX", "startY", "goalX", "goalY"):
@@ -194,6 +219,10 @@ def main(argv: List[str] = None) -> int:
     args = ap.parse_args(argv)
     if args.algo != "a_star" and not args.input:
         ap.error("-i is required")
+    if args.algo == "shortest_path_heuristic":
+        return main_shortest_path_heuristic(args, ap)
+    if not args.output:
+        ap.error("the following arguments are required: -o/--output")
     if args.algo in ("ecbs", "cbs"):
         return main_mapf(args, ap)
     if args.algo == "mapf_prioritized_sipp":

@@ -16,6 +16,7 @@
 
 #include "../../include/mrp_ll.h"
 #include "ll_device.h"
+#include "heur_layout.h"
 
 extern "C" uint32_t mrp_ll_lds_bytes(int kind, uint32_t capNodes, uint32_t rows, uint32_t rowWords, uint32_t pathBytes);
 extern "C" int mrp_ll_persistent_occupancy(int kind, uint32_t ldsBytes);
@@ -45,6 +46,22 @@ struct ConflictParams {
 }  // namespace mrp
 extern "C" hipError_t mrp_ll_launch_conflict(const mrp::ConflictParams* P, hipStream_t stream);
 
+namespace mrp {
+struct HeurParams {  // heur_kernel.hip
+  uint32_t* maps;
+  const hb::HeurJob* jobs;
+  uint32_t n;
+};
+struct LookupParams {
+  const uint32_t* maps;
+  const hb::LookupJob* jobs;
+  int32_t* out;
+  uint32_t n;
+};
+}  // namespace mrp
+extern "C" hipError_t mrp_ll_launch_heur_bfs(const mrp::HeurParams* P, uint32_t ldsBytes, hipStream_t stream);
+extern "C" hipError_t mrp_ll_launch_heur_lookup(const mrp::LookupParams* P, hipStream_t stream);
+
 namespace {
 
 using mrp::DevJob;
@@ -54,10 +71,17 @@ struct MapRec {
   int32_t dimx, dimy;
   uint32_t wpr, wordOff;
 };
-struct HeurRec {  // MRP_LL_ASTAR_TA: shortest-path table of one goal cell, kHeurWords words inside the maps buffer
+struct HeurRec {  // MRP_LL_ASTAR_TA: shortest-path table of one goal cell, heurTableWords words inside the maps buffer
   int32_t mapId;
   uint32_t wordOff;
 };
+// halfwords, 0xFFFF = unreachable: [y * 32 + x] for maps up to 32 x 32 (what the compact tier copies into its window),
+// [y * dimx + x] beyond (arena tier only)
+inline bool heurSmall(const MapRec& m) { return mrp::hb::isSmall(static_cast<uint32_t>(m.dimx), static_cast<uint32_t>(m.dimy)); }
+inline size_t heurTableWords(const MapRec& m) {
+  return heurSmall(m) ? mrp::kHeurWords : (static_cast<size_t>(m.dimx) * m.dimy + 1) / 2;
+}
+inline int heurStride(const MapRec& m) { return heurSmall(m) ? 32 : m.dimx; }
 
 // Growable pinned host buffer that the device accesses in place (zero-copy staging, see ll_device.h).
 template <typename T>
@@ -225,11 +249,15 @@ struct mrp_ll_ctx {
   int device = 0;
   std::string err;
   std::vector<MapRec> maps;
-  std::vector<uint32_t> mapWords;  // host copy of all obstacle bitmaps (and of the heuristic tables of MRP_LL_ASTAR_TA)
+  // The maps buffer (obstacle bitmaps and the heuristic tables of the task-assignment searches) is laid out in words
+  // 0 .. mapsBase + mapWords.size(): the first mapsBase words are on the device ONLY (uploads already copied, tables the
+  // device computed itself: mrp_ll_compute_heuristics), mapWords holds what has been uploaded since and not copied yet.
+  std::vector<uint32_t> mapWords;
+  size_t mapsBase = 0;
   std::vector<HeurRec> heurs;
   uint32_t* mapsDev = nullptr;
   size_t mapsDevCap = 0;
-  bool mapsDirty = false;
+  hipEvent_t heurEv0 = nullptr, heurEv1 = nullptr;  // kernel time of mrp_ll_compute_heuristics / mrp_ll_heuristic_lookup
   uint32_t maxWpr = 1;
   uint32_t extraHbmWgs = 0;       // session mode: additional resident workgroups without an LDS tier (see Ring::grid2)
   uint32_t tierRows = 64, tierPathBytes = 4096;  // LDS tier geometry (mrp_ll_configure_tiers); nodes live in opt.lds_nodes
@@ -296,21 +324,51 @@ int neighborIndexFromDelta(int dx, int dy) {
   return -1;
 }
 
-int syncMaps(mrp_ll_ctx* ctx) {
-  if (!ctx->mapsDirty) return MRP_LL_SUCCESS;
+// The conflict scan's stream: one of its own, because the scan also runs beside a session's resident kernel.
+int auxStream(mrp_ll_ctx* ctx, hipStream_t* out) {
+  if (!ctx->scanStream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->scanStream, hipStreamNonBlocking));
+  *out = ctx->scanStream;
+  return MRP_LL_SUCCESS;
+}
+
+// Room for `need` words in the device maps buffer.  When it has to grow, the words that live on the device only (the
+// first mapsBase) move device to device: nothing on the host could restore a computed table.
+int reserveMapsDev(mrp_ll_ctx* ctx, size_t need) {
+  need = std::max<size_t>(need, 1);
+  if (need <= ctx->mapsDevCap) return MRP_LL_SUCCESS;
   // all tickets must be idle before the maps buffer may move
-  size_t need = std::max<size_t>(ctx->mapWords.size(), 1);
-  if (need > ctx->mapsDevCap) {
-    for (auto& t : ctx->tickets)
-      if (t.inFlight) HIPCHK(ctx, hipEventSynchronize(t.evK1));
-    if (ctx->mapsDev) HIPCHK(ctx, hipFree(ctx->mapsDev));
-    size_t ncap = std::max<size_t>(need * 2, 1u << 20);  // >= 4 MB: room for in-session uploads
-    HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->mapsDev), ncap * sizeof(uint32_t)));
-    ctx->mapsDevCap = ncap;
+  for (auto& t : ctx->tickets)
+    if (t.inFlight) HIPCHK(ctx, hipEventSynchronize(t.evK1));
+  const size_t ncap = std::max<size_t>(need * 2, 1u << 20);  // >= 4 MB: room for in-session uploads
+  uint32_t* nd = nullptr;
+  HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(&nd), ncap * sizeof(uint32_t)));
+  if (ctx->mapsDev && ctx->mapsBase) {
+    // on the first ticket's stream, idle here (no session, every ticket waited for): a stream of its own would be one more
+    // for the hardware queues the resident kernels of a later session are spread over
+    hipStream_t st = ctx->tickets[0].stream;
+    hipError_t e = hipMemcpyAsync(nd, ctx->mapsDev, ctx->mapsBase * sizeof(uint32_t), hipMemcpyDeviceToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) {
+      (void)hipFree(nd);  // the old buffer stays in place
+      ctx->err = std::string("maps buffer growth: ") + hipGetErrorString(e);
+      return MRP_LL_E_DEVICE;
+    }
   }
-  HIPCHK(ctx, hipMemcpy(ctx->mapsDev, ctx->mapWords.data(), ctx->mapWords.size() * sizeof(uint32_t),
+  if (ctx->mapsDev) HIPCHK(ctx, hipFree(ctx->mapsDev));
+  ctx->mapsDev = nd;
+  ctx->mapsDevCap = ncap;
+  return MRP_LL_SUCCESS;
+}
+
+// Copies what has been uploaded since the last call — and only that — behind what the device already holds.
+int syncMaps(mrp_ll_ctx* ctx) {
+  if (ctx->mapWords.empty()) return MRP_LL_SUCCESS;
+  int rc = reserveMapsDev(ctx, ctx->mapsBase + ctx->mapWords.size());
+  if (rc != MRP_LL_SUCCESS) return rc;
+  HIPCHK(ctx, hipMemcpy(ctx->mapsDev + ctx->mapsBase, ctx->mapWords.data(), ctx->mapWords.size() * sizeof(uint32_t),
                         hipMemcpyHostToDevice));
-  ctx->mapsDirty = false;
+  ctx->mapsBase += ctx->mapWords.size();
+  ctx->mapWords.clear();
   return MRP_LL_SUCCESS;
 }
 
@@ -1227,6 +1285,8 @@ void mrp_ll_destroy(mrp_ll_ctx* ctx) {
   }
   if (ctx->mapsDev) (void)hipFree(ctx->mapsDev);
   if (ctx->scanDev) (void)hipFree(ctx->scanDev);
+  if (ctx->heurEv0) (void)hipEventDestroy(ctx->heurEv0);
+  if (ctx->heurEv1) (void)hipEventDestroy(ctx->heurEv1);
   if (ctx->scanStream) (void)hipStreamDestroy(ctx->scanStream);
   if (ctx->pathStore) (void)hipFree(ctx->pathStore);
   for (uint8_t* c : ctx->sippTabChunks) (void)hipFree(c);
@@ -1250,10 +1310,15 @@ int mrp_ll_upload_map(mrp_ll_ctx* ctx, int32_t dimx, int32_t dimy, int32_t nObst
   // Every bitmap starts on its own 128-byte line: a map uploaded while a resident kernel runs (below) must not share a
   // cache line with an older one — the kernels read obstacle words with plain cached loads, and an XCD's L2 may still
   // hold the line's previous contents (nothing invalidates it between jobs, ll_kernel.hip residentLoop).
-  while (ctx->mapWords.size() & 31u) ctx->mapWords.push_back(0);
-  m.wordOff = static_cast<uint32_t>(ctx->mapWords.size());
+  const size_t pending0 = ctx->mapWords.size();
+  if (ctx->mapsBase + pending0 + 31u + m.wpr > UINT32_MAX) {
+    ctx->err = "mrp_ll_upload_map: the maps buffer is full (2^32 words)";
+    return MRP_LL_E_NOMEM;
+  }
+  while ((ctx->mapsBase + ctx->mapWords.size()) & 31u) ctx->mapWords.push_back(0);
+  m.wordOff = static_cast<uint32_t>(ctx->mapsBase + ctx->mapWords.size());
   ctx->mapWords.resize(ctx->mapWords.size() + m.wpr, 0u);
-  uint32_t* w = ctx->mapWords.data() + m.wordOff;
+  uint32_t* w = ctx->mapWords.data() + (m.wordOff - ctx->mapsBase);
   // cells past dimx*dimy in the last word are never addressed
   for (int i = 0; i < nObst; ++i) {
     int x = obstXY[2 * i], y = obstXY[2 * i + 1];
@@ -1266,17 +1331,15 @@ int mrp_ll_upload_map(mrp_ll_ctx* ctx, int32_t dimx, int32_t dimy, int32_t nObst
   if (ctx->ring.active) {
     // a resident kernel is reading the maps buffer: it may be appended to, but neither moved nor re-laid-out
     // (a map wider than the session's LDS rows is served from the HBM tier until the next session)
-    if (ctx->mapWords.size() > ctx->mapsDevCap) {
+    if (ctx->mapsBase + ctx->mapWords.size() > ctx->mapsDevCap) {
       ctx->maps.pop_back();
-      ctx->mapWords.resize(m.wordOff);
+      ctx->mapWords.resize(pending0);
       ctx->err = "mrp_ll_upload_map: no room in the device map buffer during a session (upload maps before "
                  "mrp_ll_session_begin, or end the session first)";
       return MRP_LL_E_BUSY;
     }
-    HIPCHK(ctx, hipMemcpy(ctx->mapsDev + m.wordOff, ctx->mapWords.data() + m.wordOff, m.wpr * sizeof(uint32_t),
-                          hipMemcpyHostToDevice));
-  } else {
-    ctx->mapsDirty = true;
+    int rc = syncMaps(ctx);  // (no growth: checked above)
+    if (rc != MRP_LL_SUCCESS) return rc;
   }
   *mapId = static_cast<int32_t>(ctx->maps.size()) - 1;
   return MRP_LL_SUCCESS;
@@ -1287,25 +1350,201 @@ int mrp_ll_upload_heuristic(mrp_ll_ctx* ctx, int32_t mapId, const int32_t* dist,
   if (!ctx || !dist || !heurId || mapId < 0 || mapId >= static_cast<int32_t>(ctx->maps.size())) return MRP_LL_E_INVALID;
   if (ctx->ring.active) return MRP_LL_E_BUSY;  // (the maps buffer may have to grow)
   const MapRec& mp = ctx->maps[mapId];
-  while (ctx->mapWords.size() & 31u) ctx->mapWords.push_back(0);  // own 128-byte lines, as the bitmaps
+  if (ctx->mapsBase + ctx->mapWords.size() + 31u + heurTableWords(mp) > UINT32_MAX) return MRP_LL_E_NOMEM;
+  while ((ctx->mapsBase + ctx->mapWords.size()) & 31u) ctx->mapWords.push_back(0);  // own 128-byte lines, as the bitmaps
   HeurRec h;
   h.mapId = mapId;
-  h.wordOff = static_cast<uint32_t>(ctx->mapWords.size());
-  // halfwords, 0xFFFF = unreachable (the reference's table holds INT_MAX there): [y * 32 + x] for maps up to 32 x 32 (what
-  // the compact tier copies into its window), [y * dimx + x] beyond (arena tier only)
-  const bool small = mp.dimx <= 32 && mp.dimy <= 32;
-  const int stride = small ? 32 : mp.dimx;
-  const size_t words = small ? mrp::kHeurWords : (static_cast<size_t>(mp.dimx) * mp.dimy + 1) / 2;
-  ctx->mapWords.resize(ctx->mapWords.size() + words, 0xFFFFFFFFu);
-  uint16_t* t16 = reinterpret_cast<uint16_t*>(ctx->mapWords.data() + h.wordOff);
+  h.wordOff = static_cast<uint32_t>(ctx->mapsBase + ctx->mapWords.size());
+  // halfwords, 0xFFFF = unreachable (the reference's table holds INT_MAX there)
+  const int stride = heurStride(mp);
+  ctx->mapWords.resize(ctx->mapWords.size() + heurTableWords(mp), 0xFFFFFFFFu);
+  uint16_t* t16 = reinterpret_cast<uint16_t*>(ctx->mapWords.data() + (h.wordOff - ctx->mapsBase));
   for (int y = 0; y < mp.dimy; ++y)
     for (int x = 0; x < mp.dimx; ++x) {
       const int32_t v = dist[y * mp.dimx + x];
       t16[y * stride + x] = (v < 0 || v > 0xFFFE) ? 0xFFFFu : static_cast<uint16_t>(v);
     }
   ctx->heurs.push_back(h);
-  ctx->mapsDirty = true;
   *heurId = static_cast<int32_t>(ctx->heurs.size()) - 1;
+  return MRP_LL_SUCCESS;
+}
+
+namespace {
+bool heurBusy(const mrp_ll_ctx* ctx) {
+  if (ctx->ring.active) return true;
+  for (const Ticket& t : ctx->tickets)
+    if (t.inFlight) return true;
+  return false;
+}
+// device staging of the table calls (shared with mrp_ll_conflict_scan: neither keeps anything there between calls)
+int reserveScanDev(mrp_ll_ctx* ctx, size_t bytes) {
+  if (bytes <= ctx->scanDevCap) return MRP_LL_SUCCESS;
+  if (ctx->scanDev) HIPCHK(ctx, hipFree(ctx->scanDev));
+  ctx->scanDev = nullptr;
+  ctx->scanDevCap = 0;
+  HIPCHK(ctx, hipMalloc(reinterpret_cast<void**>(&ctx->scanDev), bytes * 2));
+  ctx->scanDevCap = bytes * 2;
+  return MRP_LL_SUCCESS;
+}
+int heurEvents(mrp_ll_ctx* ctx) {
+  if (!ctx->heurEv0) HIPCHK(ctx, hipEventCreate(&ctx->heurEv0));
+  if (!ctx->heurEv1) HIPCHK(ctx, hipEventCreate(&ctx->heurEv1));
+  return MRP_LL_SUCCESS;
+}
+void heurKernelDone(mrp_ll_ctx* ctx) {
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, ctx->heurEv0, ctx->heurEv1) == hipSuccess) ctx->stats.kernel_ms += ms;
+  ctx->stats.launches += 1;
+}
+}  // namespace
+
+int mrp_ll_compute_heuristics(mrp_ll_ctx* ctx, int32_t n, const int32_t* mapIds, const int32_t* goalsXY, int32_t* heurIds) {
+  if (!ctx) return MRP_LL_E_INVALID;
+  if (n < 0 || (n > 0 && (!mapIds || !goalsXY || !heurIds))) {
+    ctx->err = "mrp_ll_compute_heuristics: invalid argument";
+    return MRP_LL_E_INVALID;
+  }
+  if (heurBusy(ctx)) {
+    ctx->err = "mrp_ll_compute_heuristics: a session is active or a batch is in flight (the maps buffer may have to grow)";
+    return MRP_LL_E_BUSY;
+  }
+  for (int32_t k = 0; k < n; ++k) {
+    if (mapIds[k] < 0 || mapIds[k] >= static_cast<int32_t>(ctx->maps.size())) {
+      ctx->err = "mrp_ll_compute_heuristics: unknown map id";
+      return MRP_LL_E_INVALID;
+    }
+    const MapRec& mp = ctx->maps[mapIds[k]];
+    const int32_t gx = goalsXY[2 * k], gy = goalsXY[2 * k + 1];
+    if (gx < 0 || gx >= mp.dimx || gy < 0 || gy >= mp.dimy) {
+      ctx->err = "mrp_ll_compute_heuristics: goal outside its map";
+      return MRP_LL_E_INVALID;
+    }
+  }
+  if (n == 0) return MRP_LL_SUCCESS;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  // the bitmaps the kernel reads must be on the device; after this the layout ends at mapsBase
+  int rc = syncMaps(ctx);
+  if (rc != MRP_LL_SUCCESS) return rc;
+  // the tables go behind everything else, each on its own 128-byte lines, and exist on the device only
+  std::vector<mrp::hb::HeurJob> jobs(static_cast<size_t>(n));
+  size_t off = (ctx->mapsBase + 31u) & ~size_t(31);
+  uint32_t ldsBytes = 0;
+  for (int32_t k = 0; k < n; ++k) {
+    const MapRec& mp = ctx->maps[mapIds[k]];
+    if (off + heurTableWords(mp) + 31u > UINT32_MAX) {
+      ctx->err = "mrp_ll_compute_heuristics: the maps buffer is full (2^32 words)";
+      return MRP_LL_E_NOMEM;
+    }
+    mrp::hb::HeurJob& j = jobs[k];
+    j.mapOff = mp.wordOff;
+    j.tabOff = static_cast<uint32_t>(off);
+    j.dims = static_cast<uint32_t>(mp.dimx) | static_cast<uint32_t>(mp.dimy) << 8;
+    j.goal = static_cast<uint32_t>(goalsXY[2 * k]) | static_cast<uint32_t>(goalsXY[2 * k + 1]) << 8;
+    ldsBytes = std::max(ldsBytes, mrp::hb::ldsBytes(static_cast<uint32_t>(mp.dimx), static_cast<uint32_t>(mp.dimy)));
+    off = (off + heurTableWords(mp) + 31u) & ~size_t(31);
+  }
+  rc = reserveMapsDev(ctx, off);
+  if (rc != MRP_LL_SUCCESS) return rc;
+  const size_t jobBytes = jobs.size() * sizeof(mrp::hb::HeurJob);
+  rc = reserveScanDev(ctx, jobBytes);
+  if (rc != MRP_LL_SUCCESS) return rc;
+  hipStream_t st = ctx->tickets[0].stream;  // idle: no session, no batch in flight (heurBusy above)
+  rc = heurEvents(ctx);
+  if (rc != MRP_LL_SUCCESS) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->scanDev, jobs.data(), jobBytes, hipMemcpyHostToDevice, st));
+  mrp::HeurParams P;
+  P.maps = ctx->mapsDev;
+  P.jobs = reinterpret_cast<const mrp::hb::HeurJob*>(ctx->scanDev);
+  P.n = static_cast<uint32_t>(n);
+  HIPCHK(ctx, hipEventRecord(ctx->heurEv0, st));
+  HIPCHK(ctx, mrp_ll_launch_heur_bfs(&P, ldsBytes, st));  // ONE launch, one wavefront per table
+  HIPCHK(ctx, hipEventRecord(ctx->heurEv1, st));
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  heurKernelDone(ctx);
+  ctx->stats.staged_bytes += static_cast<int64_t>(jobBytes);
+  for (int32_t k = 0; k < n; ++k) {
+    ctx->heurs.push_back(HeurRec{mapIds[k], jobs[k].tabOff});
+    heurIds[k] = static_cast<int32_t>(ctx->heurs.size()) - 1;
+  }
+  ctx->mapsBase = off;
+  return MRP_LL_SUCCESS;
+}
+
+int mrp_ll_read_heuristic(mrp_ll_ctx* ctx, int32_t heurId, int32_t* dist) {
+  if (!ctx) return MRP_LL_E_INVALID;
+  if (!dist || heurId < 0 || heurId >= static_cast<int32_t>(ctx->heurs.size())) {
+    ctx->err = "mrp_ll_read_heuristic: invalid argument (NULL pointer or unknown heuristic id)";
+    return MRP_LL_E_INVALID;
+  }
+  if (heurBusy(ctx)) {
+    ctx->err = "mrp_ll_read_heuristic: a session is active or a batch is in flight";
+    return MRP_LL_E_BUSY;
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int rc = syncMaps(ctx);  // an uploaded table is read back from where the searches read it
+  if (rc != MRP_LL_SUCCESS) return rc;
+  const HeurRec& h = ctx->heurs[heurId];
+  const MapRec& mp = ctx->maps[h.mapId];
+  std::vector<uint32_t> words(heurTableWords(mp));
+  HIPCHK(ctx, hipMemcpy(words.data(), ctx->mapsDev + h.wordOff, words.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  const uint16_t* t16 = reinterpret_cast<const uint16_t*>(words.data());
+  const int stride = heurStride(mp);
+  for (int y = 0; y < mp.dimy; ++y)
+    for (int x = 0; x < mp.dimx; ++x) {
+      const uint16_t v = t16[y * stride + x];
+      dist[y * mp.dimx + x] = v == 0xFFFFu ? INT32_MAX : static_cast<int32_t>(v);
+    }
+  return MRP_LL_SUCCESS;
+}
+
+int mrp_ll_heuristic_lookup(mrp_ll_ctx* ctx, int32_t n, const int32_t* heurIds, const int32_t* cellsXY, int32_t* out) {
+  if (!ctx) return MRP_LL_E_INVALID;
+  if (n < 0 || (n > 0 && (!heurIds || !cellsXY || !out))) {
+    ctx->err = "mrp_ll_heuristic_lookup: invalid argument";
+    return MRP_LL_E_INVALID;
+  }
+  if (heurBusy(ctx)) {
+    ctx->err = "mrp_ll_heuristic_lookup: a session is active or a batch is in flight";
+    return MRP_LL_E_BUSY;
+  }
+  std::vector<mrp::hb::LookupJob> jobs(static_cast<size_t>(n));
+  for (int32_t k = 0; k < n; ++k) {
+    if (heurIds[k] < 0 || heurIds[k] >= static_cast<int32_t>(ctx->heurs.size())) {
+      ctx->err = "mrp_ll_heuristic_lookup: unknown heuristic id";
+      return MRP_LL_E_INVALID;
+    }
+    const HeurRec& h = ctx->heurs[heurIds[k]];
+    const MapRec& mp = ctx->maps[h.mapId];
+    const int32_t x = cellsXY[2 * k], y = cellsXY[2 * k + 1];
+    if (x < 0 || x >= mp.dimx || y < 0 || y >= mp.dimy) {
+      ctx->err = "mrp_ll_heuristic_lookup: cell outside its map";
+      return MRP_LL_E_INVALID;
+    }
+    jobs[k].tabOff = h.wordOff;
+    jobs[k].half = static_cast<uint32_t>(y * heurStride(mp) + x);
+  }
+  if (n == 0) return MRP_LL_SUCCESS;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int rc = syncMaps(ctx);
+  if (rc != MRP_LL_SUCCESS) return rc;
+  const size_t jobBytes = (jobs.size() * sizeof(mrp::hb::LookupJob) + 255) & ~size_t(255), outBytes = static_cast<size_t>(n) * 4;
+  rc = reserveScanDev(ctx, jobBytes + outBytes);
+  if (rc != MRP_LL_SUCCESS) return rc;
+  hipStream_t st = ctx->tickets[0].stream;  // idle: no session, no batch in flight (heurBusy above)
+  rc = heurEvents(ctx);
+  if (rc != MRP_LL_SUCCESS) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->scanDev, jobs.data(), jobs.size() * sizeof(mrp::hb::LookupJob), hipMemcpyHostToDevice, st));
+  mrp::LookupParams P;
+  P.maps = ctx->mapsDev;
+  P.jobs = reinterpret_cast<const mrp::hb::LookupJob*>(ctx->scanDev);
+  P.out = reinterpret_cast<int32_t*>(ctx->scanDev + jobBytes);
+  P.n = static_cast<uint32_t>(n);
+  HIPCHK(ctx, hipEventRecord(ctx->heurEv0, st));
+  HIPCHK(ctx, mrp_ll_launch_heur_lookup(&P, st));
+  HIPCHK(ctx, hipEventRecord(ctx->heurEv1, st));
+  HIPCHK(ctx, hipMemcpyAsync(out, ctx->scanDev + jobBytes, outBytes, hipMemcpyDeviceToHost, st));  // n words, no table moves
+  HIPCHK(ctx, hipStreamSynchronize(st));
+  heurKernelDone(ctx);
   return MRP_LL_SUCCESS;
 }
 
@@ -2335,7 +2574,7 @@ int mrp_ll_release_maps(mrp_ll_ctx* ctx) {
   ctx->maps.clear();
   ctx->heurs.clear();
   ctx->mapWords.clear();
-  ctx->mapsDirty = false;  // nothing to copy; the device buffer (and its capacity) is kept for the next uploads
+  ctx->mapsBase = 0;  // nothing to copy; the device buffer (and its capacity) is kept for the next uploads
   return MRP_LL_SUCCESS;
 }
 
@@ -2385,8 +2624,8 @@ int mrp_ll_conflict_scan(mrp_ll_ctx* ctx, int32_t nSets, const int32_t* setFirst
   // A stream of its own (non-blocking): during a session tickets[0].stream is held by the resident kernel until
   // mrp_ll_session_end, and a scan queued behind it would never start (while its caller, blocked here, stops moving the
   // session's heartbeat).  The scan kernel runs beside the resident wavefronts: they leave wave slots and registers free.
-  if (!ctx->scanStream) HIPCHK(ctx, hipStreamCreateWithFlags(&ctx->scanStream, hipStreamNonBlocking));
-  hipStream_t st = ctx->scanStream;
+  hipStream_t st = nullptr;
+  if (auxStream(ctx, &st) != MRP_LL_SUCCESS) return MRP_LL_E_DEVICE;
   HIPCHK(ctx, hipMemcpyAsync(ctx->scanDev + oSet, setFirstAgent, (nSets + 1) * 4, hipMemcpyHostToDevice, st));
   HIPCHK(ctx, hipMemcpyAsync(ctx->scanDev + oPath, pathFirstState, (nAgents + 1) * 4, hipMemcpyHostToDevice, st));
   if (nStates)

@@ -83,6 +83,8 @@ WV_FN V writelane(V v, uint32_t val, uint32_t lane) { return V((uint32_t)mrp_llv
 WV_FN V shr1(V v) { return V((uint32_t)__builtin_amdgcn_update_dpp((int)v.v, (int)v.v, 0x138, 0xF, 0xF, false)); }
 // lane i of every 16-lane row receives lane i + 1's value; the last lane of a row receives `fill`
 WV_FN V rowShl1(V v, uint32_t fill) { return V((uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v.v, 0x101, 0xF, 0xF, false)); }
+// lane i receives the value of lane src[i] (0 .. 63): ds_bpermute_b32 — the crossbar of the LDS unit, no LDS memory
+WV_FN V bpermute(V v, V src) { return V((uint32_t)__builtin_amdgcn_ds_bpermute((int)((src.v & 63u) << 2), (int)v.v)); }
 WV_FN V clz(V v) { return V((uint32_t)__builtin_clz(v.v)); }          // v != 0
 WV_FN V popc(V v) { return V((uint32_t)__builtin_popcount(v.v)); }
 WV_FN float uintAsFloat(uint32_t v) { return __uint_as_float(v); }
@@ -127,6 +129,9 @@ WV_FN void ldsStore128m(Lds l, V addr, V4 val, B m) {
 }
 WV_FN void ldsStore8m(Lds l, V addr, V val, B m) {
   if (lanePred(m)) *(__attribute__((address_space(3))) uint8_t*)(l + addr.v) = (uint8_t)val.v;
+}
+WV_FN void ldsStoreU16m(Lds l, V addr, V val, B m) {
+  if (lanePred(m)) *(__attribute__((address_space(3))) uint16_t*)(l + addr.v) = (uint16_t)val.v;
 }
 WV_FN void ldsOr32m(Lds l, V addr, V bits, B m) {
   if (lanePred(m))

@@ -83,6 +83,10 @@ WV_FN void ldsStore128(Lds l, V addr, V4 val) {
 WV_FN void ldsStore128m(Lds l, V addr, V4 val, B m) {
   if (m) ldsStore128(l, addr, val);
 }
+WV_FN V bpermute(V v, V src) { return (uint32_t)__builtin_amdgcn_ds_bpermute((int)((src & 63u) << 2), (int)v); }
+WV_FN void ldsStoreU16m(Lds l, V addr, V val, B m) {
+  if (m) *(__attribute__((address_space(3))) uint16_t*)(l + addr) = (uint16_t)val;
+}
 WV_FN void ldsStore8m(Lds l, V addr, V val, B m) {
   if (m) *(__attribute__((address_space(3))) uint8_t*)(l + addr) = (uint8_t)val;
 }

@@ -71,7 +71,8 @@ EXPORTS = ["mrp_ll_create", "mrp_ll_destroy", "mrp_ll_last_error", "mrp_ll_uploa
            "mrp_ll_configure_tiers", "mrp_ll_session_occupancy", "mrp_ll_session_begin_sipp", "mrp_ll_release_maps", "mrp_ll_session_begin_algo", "mrp_ll_conflict_scan",
            "mrp_ll_sipp_table_create", "mrp_ll_sipp_table_add", "mrp_ll_sipp_table_destroy", "mrp_ll_path_store_reserve",
            "mrp_ll_upload_heuristic", "mrp_ll_session_begin_tiers", "mrp_ll_session_tiers_geometry",
-           "mrp_ll_session_begin_tiers_gated", "mrp_ll_submit_tagged", "mrp_ll_poll_any_tagged"]
+           "mrp_ll_session_begin_tiers_gated", "mrp_ll_submit_tagged", "mrp_ll_poll_any_tagged",
+           "mrp_ll_compute_heuristics", "mrp_ll_read_heuristic", "mrp_ll_heuristic_lookup"]
 
 _lib = None
 
@@ -133,6 +134,12 @@ def load_library(path: Optional[str] = None):
     lib.mrp_ll_upload_heuristic.restype = ctypes.c_int
     lib.mrp_ll_upload_heuristic.argtypes = [ctypes.c_void_p, ctypes.c_int32, I32P, ctypes.POINTER(ctypes.c_int32)]
     lib.mrp_ll_path_store_reserve.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+    lib.mrp_ll_compute_heuristics.restype = ctypes.c_int
+    lib.mrp_ll_compute_heuristics.argtypes = [ctypes.c_void_p, ctypes.c_int32, I32P, I32P, I32P]
+    lib.mrp_ll_read_heuristic.restype = ctypes.c_int
+    lib.mrp_ll_read_heuristic.argtypes = [ctypes.c_void_p, ctypes.c_int32, I32P]
+    lib.mrp_ll_heuristic_lookup.restype = ctypes.c_int
+    lib.mrp_ll_heuristic_lookup.argtypes = [ctypes.c_void_p, ctypes.c_int32, I32P, I32P, I32P]
     lib.mrp_ll_sipp_table_create.restype = ctypes.c_int
     lib.mrp_ll_sipp_table_create.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p)]
     lib.mrp_ll_sipp_table_add.restype = ctypes.c_int
@@ -193,6 +200,8 @@ class LowLevelEngine:
             raise RuntimeError(f"mrp_ll_create failed (rc={rc}): a HIP device is required, there is no CPU fallback")
         self._h = h
         self.max_horizon = max_horizon or 512
+        self._map_dims = {}  # map id -> (dimx, dimy), heuristic id -> map id: the shape read_heuristic returns
+        self._heur_map = {}
 
     def close(self):
         if getattr(self, "_h", None):
@@ -214,6 +223,7 @@ class LowLevelEngine:
         mid = ctypes.c_int32(-1)
         self._check(self._lib.mrp_ll_upload_map(self._h, dimx, dimy, len(ob), ob.ctypes.data_as(I32P),
                                                 ctypes.byref(mid)), "mrp_ll_upload_map")
+        self._map_dims[mid.value] = (dimx, dimy)
         return mid.value
 
     def _marshal(self, jobs: Sequence[LLJob], cap: int):
@@ -318,7 +328,56 @@ class LowLevelEngine:
         hid = ctypes.c_int32(-1)
         self._check(self._lib.mrp_ll_upload_heuristic(self._h, map_id, d.ctypes.data_as(I32P), ctypes.byref(hid)),
                     "mrp_ll_upload_heuristic")
+        self._heur_map[hid.value] = map_id
         return hid.value
+
+    def compute_heuristics(self, map_ids: Sequence[int], goals: Sequence[Sequence[int]]) -> List[int]:
+        """mrp_ll_compute_heuristics: the shortest-path tables of goals[k] = (x, y) on map map_ids[k], computed on the
+        device from the uploaded maps in one launch; returns their heuristic ids (as upload_heuristic's)."""
+        mids = np.ascontiguousarray(np.asarray(map_ids, dtype=np.int32).reshape(-1))
+        gxy = np.ascontiguousarray(np.asarray(goals, dtype=np.int32).reshape(-1, 2))
+        if len(mids) != len(gxy):
+            raise ValueError("compute_heuristics: one goal per map id")
+        hids = np.full(max(len(mids), 1), -1, dtype=np.int32)
+        self._check(self._lib.mrp_ll_compute_heuristics(self._h, len(mids), mids.ctypes.data_as(I32P),
+                                                        gxy.ctypes.data_as(I32P), hids.ctypes.data_as(I32P)),
+                    "mrp_ll_compute_heuristics")
+        out = hids[:len(mids)].tolist()
+        self._heur_map.update(zip(out, mids.tolist()))
+        return out
+
+    def read_heuristic(self, hid: int) -> np.ndarray:
+        """mrp_ll_read_heuristic: table `hid` (computed or uploaded) as an int32 array [dimy, dimx], INT32_MAX =
+        unreachable."""
+        mid = self._heur_map.get(hid)
+        if mid is None:
+            raise ValueError("read_heuristic: unknown heuristic id %r" % (hid,))
+        dimx, dimy = self._map_dims[mid]
+        dist = np.zeros((dimy, dimx), dtype=np.int32)
+        self._check(self._lib.mrp_ll_read_heuristic(self._h, hid, dist.ctypes.data_as(I32P)), "mrp_ll_read_heuristic")
+        return dist
+
+    def heuristic_lookup(self, hids: Sequence[int], cells: Sequence[Sequence[int]]) -> np.ndarray:
+        """mrp_ll_heuristic_lookup: out[k] = table hids[k] at cells[k] = (x, y) (INT32_MAX = unreachable) — the entries of
+        the assignment's cost matrix without moving whole tables."""
+        ids = np.ascontiguousarray(np.asarray(hids, dtype=np.int32).reshape(-1))
+        cxy = np.ascontiguousarray(np.asarray(cells, dtype=np.int32).reshape(-1, 2))
+        if len(ids) != len(cxy):
+            raise ValueError("heuristic_lookup: one cell per heuristic id")
+        out = np.zeros(max(len(ids), 1), dtype=np.int32)
+        self._check(self._lib.mrp_ll_heuristic_lookup(self._h, len(ids), ids.ctypes.data_as(I32P), cxy.ctypes.data_as(I32P),
+                                                      out.ctypes.data_as(I32P)), "mrp_ll_heuristic_lookup")
+        return out[:len(ids)]
+
+    def sync_maps(self) -> None:
+        """mrp_ll_sync_maps: copy what has been uploaded so far to the device now (otherwise done by the next submit)."""
+        self._check(self._lib.mrp_ll_sync_maps(self._h), "mrp_ll_sync_maps")
+
+    def release_maps(self) -> None:
+        """mrp_ll_release_maps: forget every map and heuristic table; ids start again at 0."""
+        self._check(self._lib.mrp_ll_release_maps(self._h), "mrp_ll_release_maps")
+        self._map_dims.clear()
+        self._heur_map.clear()
 
     def path_store_reserve(self, n_slots: int) -> None:
         """Allocate the device-resident path store (f2): slots 0..n_slots-1 are the caller's to hand out."""
