@@ -187,6 +187,7 @@ class LLResult:
     actions: List[int] = field(default_factory=list)
     tier: int = 0
     action_costs: List[int] = field(default_factory=list)
+    n_states: int = 0  # mrp_ll_result.n_states as the library left it (0 unless a path came back)
 
 
 class LowLevelEngine:
@@ -300,7 +301,7 @@ class LowLevelEngine:
             out.append(LLResult(status=r.status, success=r.status in (OK, PATH_TRUNCATED), cost=r.cost, fmin=r.fmin,
                                 expanded=r.expanded, states=states[i, :m].tolist(),
                                 actions=actions[i, :max(m - 1, 0)].tolist(), tier=r.tier,
-                                action_costs=costs[i, :max(m - 1, 0)].tolist()))
+                                action_costs=costs[i, :max(m - 1, 0)].tolist(), n_states=r.n_states))
         return out
 
     def conflict_scan(self, solutions: Sequence[Sequence[Sequence[Sequence[int]]]]) -> List[dict]:

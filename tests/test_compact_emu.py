@@ -3,6 +3,7 @@ on the CPU: the same file built against tests/support/wave_emu.h, a 64-lane lock
 and run on low-level searches harvested from the oracle's CBS / ECBS conflict trees.  Every search the tier finishes must
 equal the oracle bit for bit (success, cost, fmin, expansions, path); a search it hands over (overflow) is the arena
 tier's business and is only counted."""
+import collections
 import ctypes
 import os
 import subprocess
@@ -342,3 +343,63 @@ def test_task_assignment_low_level(emu, oracle_mod, ref_tests, bench_instances):
         r = emu_search_ta(emu, m, s, goal, vc, ec, max_exp=cap)
         n += _compare_ta(r, o)
     assert n >= 100
+
+
+def test_small_non_square_maps(oracle_mod):
+    """Random jobs on the small maps that are not 8 x 8 or 32 x 32 — one row, one column, odd sizes, one dimension at the
+    tier's 32, a single cell — through every form of the tier: A*-epsilon in all three, A* in the narrow one, and the
+    task-assignment search.  The cell-linear obstacle bitmap, the y * dimx + x constraint keys and the bounds tests have no
+    other cover at dimx != dimy.  Every search runs under an expansion cap (a goal behind a wall keeps the reference busy
+    forever); what the tier finishes equals the oracle bit for bit, and no access leaves its buffers."""
+    import heuristic_inputs
+    L = _emu_lib()
+    moves = [(0, 0), (1, 0), (-1, 0), (0, 1), (0, -1)]
+    done = collections.Counter()
+    for mi, (dimx, dimy) in enumerate(((1, 32), (32, 1), (31, 17), (17, 31), (32, 5), (5, 32), (31, 32), (32, 31), (2, 2), (1, 1))):
+        m = heuristic_inputs.random_map(dimx, dimy, 40 + mi) if min(dimx, dimy) > 2 else dict(dimx=dimx, dimy=dimy, obstacles=[])
+        free = heuristic_inputs.free_cells(m)
+        inst = dict(m, starts=[], goals=[])
+        rng = np.random.default_rng(900 + mi)
+        tmax = dimx + dimy + 6
+        for trial in range(25):
+            s, g = (free[int(rng.integers(0, len(free)))] for _ in range(2))
+            vc = [[int(rng.integers(0, tmax)), int(rng.integers(0, dimx)), int(rng.integers(0, dimy))]
+                  for _ in range(int(rng.integers(0, 12)))]
+            if trial % 4 == 1:
+                vc.append([int(rng.integers(1, tmax)), g[0], g[1]])  # m_lastGoalConstraint
+            ec = []
+            for _ in range(int(rng.integers(0, 12))):  # some of these moves leave the grid
+                x, y = int(rng.integers(0, dimx)), int(rng.integers(0, dimy))
+                dx, dy = moves[int(rng.integers(0, 5))]
+                ec.append([int(rng.integers(0, tmax)), x, y, x + dx, y + dy])
+            ctx = [[]]
+            for _ in range(int(rng.integers(0, 4))):  # other agents: walks along free cells, waits included
+                p = [free[int(rng.integers(0, len(free)))]]
+                for _ in range(int(rng.integers(0, tmax))):
+                    dx, dy = moves[int(rng.integers(0, 5))]
+                    q = [p[-1][0] + dx, p[-1][1] + dy]
+                    p.append(q if q in free else p[-1])
+                ctx.append(p)
+            cap = 1500
+            for form, eps, w in ((0, True, 1.3), (1, True, 1.3), (2, True, 1.3), (0, False, 1.0)):
+                L._bg, L._wide = form >= 1, form == 2
+                o = oracle_mod.ll_search(oracle_mod.ASTAR_EPS if eps else oracle_mod.ASTAR, m, 0, s, g, vc, ec, ctx if eps else [],
+                                         w=w, cap_expansions=cap)
+                r = emu_search(L, eps, inst, 0, s, g, vc, ec, ctx if eps else [], w, max_exp=cap)
+                assert r["oob_reads"] == 0 and r["oob_writes"] == 0, (dimx, dimy, trial, form, r)
+                if r["status"] == -1:
+                    continue
+                done[(form, eps)] += 1
+                tag = (dimx, dimy, trial, form, eps, r)
+                if o["rc"] == -1:
+                    assert r["status"] == 2, tag
+                    continue
+                assert (r["status"] == 0, r["expanded"]) == (o["success"], o["expanded"]), (tag, o["expanded"])
+                if o["success"]:
+                    assert (r["cost"], r["fmin"], r["states"]) == (o["cost"], o["fmin"], [st[1:] for st in o["states"]]), tag
+            L._bg = L._wide = False
+            goal = None if trial % 5 == 0 else g
+            o = oracle_mod.ta_ll_search(m, s, goal, vc, ec, cap_expansions=cap)
+            done["ta"] += _compare_ta(emu_search_ta(L, m, s, goal, vc, ec, max_exp=cap), o)
+    # (nearly) every job is finished inside the tier, in every form
+    assert all(done[k] >= 225 for k in ((0, True), (1, True), (2, True), (0, False), "ta")), done
