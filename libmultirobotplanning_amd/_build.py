@@ -23,8 +23,8 @@ TARGETS = {
                                "../../include/mrp_ll.h"],
                          extra=[]),
     "libmrp_hl.so": dict(srcs=["hl/mrp_hl.cpp"], deps=["hl/exact_heap.hpp", "hl/grid_mapf.hpp", "hl/ct_solver.hpp",
-                                                       "hl/instance_io.hpp", "../../include/mrp_ll.h",
-                                                       "../../include/mrp_hl.h"],
+                                                       "hl/ct_session.hpp", "hl/grid2d_astar.hpp", "hl/instance_io.hpp",
+                                                       "../../include/mrp_ll.h", "../../include/mrp_hl.h"],
                          extra=["-pthread", "-L", LIBDIR, "-lmrp_ll", "-Wl,-rpath,$ORIGIN"]),
 }
 

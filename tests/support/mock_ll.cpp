@@ -4,6 +4,7 @@
 // The product library has no such path: libmrp_ll.so fails with MRP_LL_E_DEVICE when no HIP device exists.
 #include <algorithm>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -136,6 +137,11 @@ int mrp_ll_search_batch(mrp_ll_ctx* c, int32_t n, const mrp_ll_job* jobs, mrp_ll
   for (int i = 0; i < n; ++i) {
     const mrp_ll_job& j = jobs[i];
     mrp_ll_result& r = res[i];
+    // MRP_MOCK_CHAIN_REJECT=1: an engine that cannot run root chains (mrp_ll.h MRP_LL_JOB_ROOT_CHAIN): nothing is run
+    if ((j.flags & MRP_LL_JOB_ROOT_CHAIN) && std::getenv("MRP_MOCK_CHAIN_REJECT")) {
+      r.status = MRP_LL_BAD_JOB;
+      continue;
+    }
     if ((j.flags & MRP_LL_JOB_ROOT_CHAIN) && j.map_id >= 0 && j.map_id < static_cast<int>(c->maps.size()) && !c->store.empty()) {
       mockChain(c, j, r);
       continue;
@@ -187,7 +193,55 @@ int mrp_ll_search_batch(mrp_ll_ctx* c, int32_t n, const mrp_ll_job* jobs, mrp_ll
   c->stats.launches += 1;
   return MRP_LL_SUCCESS;
 }
+// MRP_MOCK_TRACE=<file>: every submission appends one line, a 64-bit FNV-1a over what the driver asked for — the jobs'
+// values and the arrays they point to, never a pointer or a ticket id — so that a test can pin the ORDER in which a
+// driver publishes its searches (results do not depend on it).
+namespace {
+std::mutex g_traceMu;
+void traceSubmit(int32_t n, const mrp_ll_job* jobs) {
+  const char* file = std::getenv("MRP_MOCK_TRACE");
+  if (!file) return;
+  uint64_t h = 14695981039346656037ull;
+  auto mix = [&h](int64_t v) {
+    for (int b = 0; b < 8; ++b) h = (h ^ ((static_cast<uint64_t>(v) >> (8 * b)) & 0xFFu)) * 1099511628211ull;
+  };
+  auto mixAll = [&mix](const int32_t* p, int64_t cnt) {
+    for (int64_t k = 0; k < cnt; ++k) mix(p[k]);
+  };
+  mix(n);
+  for (int32_t i = 0; i < n; ++i) {
+    const mrp_ll_job& j = jobs[i];
+    int32_t wBits;
+    std::memcpy(&wBits, &j.w, 4);
+    const int64_t head[] = {j.map_id, j.algo, wBits, j.agent_idx, j.start_x, j.start_y, j.goal_x, j.goal_y, j.n_agents,
+                            j.flags, j.chain_count, j.result_path_id, j.max_expansions, j.n_vertex_constraints,
+                            j.n_edge_constraints};
+    for (int64_t v : head) mix(v);
+    mixAll(j.vertex_constraints, 3 * static_cast<int64_t>(j.n_vertex_constraints));
+    mixAll(j.edge_constraints, 5 * static_cast<int64_t>(j.n_edge_constraints));
+    mix(j.path_len ? 1 : 0);
+    if (j.path_len) mixAll(j.path_len, j.n_agents);
+    mix(j.path_ids ? 1 : 0);
+    if (j.path_ids) mixAll(j.path_ids, j.n_agents);
+    mix(j.path_xy ? 1 : 0);
+    mix(j.chain_starts_goals_xy ? 1 : 0);
+    if (j.chain_starts_goals_xy) mixAll(j.chain_starts_goals_xy, 4 * static_cast<int64_t>(j.n_agents));
+  }
+  std::lock_guard<std::mutex> lock(g_traceMu);
+  if (FILE* f = std::fopen(file, "a")) {
+    std::fprintf(f, "%016llx\n", static_cast<unsigned long long>(h));
+    std::fclose(f);
+  }
+}
+// MRP_MOCK_BUSY=N: the job ring is "full" while N finished tickets wait to be polled (0: never)
+bool mockBusy(size_t waiting) {
+  const char* e = std::getenv("MRP_MOCK_BUSY");
+  return e && std::atoi(e) > 0 && waiting >= static_cast<size_t>(std::atoi(e));
+}
+}  // namespace
 int mrp_ll_submit(mrp_ll_ctx* c, int32_t n, const mrp_ll_job* jobs, mrp_ll_result* res, int32_t* ticket) {
+  traceSubmit(n, jobs);
+  if (mockBusy(c->doneTickets.size())) return MRP_LL_E_BUSY;
   *ticket = c->nextTicket++ & 0xFFFF;
   c->doneTickets.push_back(*ticket);
   return mrp_ll_search_batch(c, n, jobs, res);
@@ -202,7 +256,9 @@ std::map<mrp_ll_ctx*, std::vector<int32_t>> g_coDone[4];
 }  // namespace
 int mrp_ll_submit_tagged(mrp_ll_ctx* c, int32_t tag, int32_t n, const mrp_ll_job* jobs, mrp_ll_result* res, int32_t* ticket) {
   if (tag < 0 || tag > 3) return MRP_LL_E_INVALID;
+  traceSubmit(n, jobs);
   std::lock_guard<std::mutex> lock(g_coMu);
+  if (mockBusy(g_coDone[tag][c].size())) return MRP_LL_E_BUSY;
   *ticket = c->nextTicket++ & 0xFFFF;
   g_coDone[tag][c].push_back(*ticket);
   return mrp_ll_search_batch(c, n, jobs, res);

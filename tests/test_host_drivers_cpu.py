@@ -14,6 +14,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "tests", "_build")
 
 
+ROOT_CHAIN_NAMES = ["map_32by32_obst204_agents10_ex%d" % k for k in range(0, 40, 3)] + [
+    "map_32by32_obst204_agents20_ex1", "map_32by32_obst204_agents30_ex2"]
+
+
 def _digest(paths):
     h = hashlib.sha256()
     for p in paths:
@@ -226,8 +230,7 @@ def test_root_chains_on_the_mock(cpu_solver, bench_instances, oracle_expected, m
     through the oracle; with MRP_MOCK_CHAIN_BREAK a search of more than that many expansions ends its chain in front of
     it, as a search that outgrows the LDS tier does on the device — the driver must run it as its own job and chain on."""
     from libmultirobotplanning_amd import hl
-    names = ["map_32by32_obst204_agents10_ex%d" % k for k in range(0, 40, 3)] + ["map_32by32_obst204_agents20_ex1",
-                                                                                "map_32by32_obst204_agents30_ex2"]
+    names = ROOT_CHAIN_NAMES
     lib = os.path.join(BUILD, "libmrp_hl_cpu.so")
     monkeypatch.setenv("MRP_MOCK_PATH_STORE", "1")
     # "chunks": the root step in jobs of three searches (mrp_ll_job.chain_count; the drivers do this from 64 agents on)
@@ -262,3 +265,97 @@ def test_root_chains_on_the_mock(cpu_solver, bench_instances, oracle_expected, m
             assert st["rounds"] > searches
         if brk == "chunks":  # ten agents = four jobs (3 + 3 + 3 + 1) instead of one: more tickets than whole chains, far fewer than searches
             assert st["rounds"] * 2 < searches and st["rounds"] >= 4 * len(names)
+
+
+def _small_cbs_names(bench_instances, oracle_expected):
+    return [n for n in sorted(bench_instances) if "8by8" in n and oracle_expected[n]["cbs"]["rc"] == 1
+            and oracle_expected[n]["cbs"]["ll"] < 60000]
+
+
+def _solver(n_threads, monkeypatch):
+    """A solver of its own (the engines' path stores and the worker count are fixed per solver); five threads share two
+    engines, as in test_co_workers_share_an_engine."""
+    from libmultirobotplanning_amd import hl
+    if n_threads == 5:
+        monkeypatch.setenv("MRP_HL_MAX_ENGINES", "2")
+    return hl.BatchSolver(device=0, n_threads=n_threads, _lib_path=os.path.join(BUILD, "libmrp_hl_cpu.so"))
+
+
+# Branches of the session driver that the mock's defaults never take: a full job ring (mrp_ll_submit answers
+# MRP_LL_E_BUSY), an engine that rejects root chains, the static split, admission control, no root fast path, a shallow
+# device queue with scrambled completions, and the rounds schedule.  (environment, mode)
+SCHEDULE_BRANCHES = {
+    "busy1": ({"MRP_MOCK_BUSY": "1"}, 0),
+    "busy3_store": ({"MRP_MOCK_BUSY": "3", "MRP_MOCK_PATH_STORE": "1"}, 0),
+    "chain_reject_store": ({"MRP_MOCK_CHAIN_REJECT": "1", "MRP_MOCK_PATH_STORE": "1"}, 0),
+    "static_split": ({"MRP_HL_STATIC_SPLIT": "1"}, 0),
+    "static_split_limit2_store": ({"MRP_HL_STATIC_SPLIT": "1", "MRP_HL_ACTIVE_LIMIT": "2", "MRP_MOCK_PATH_STORE": "1"}, 0),
+    "no_root_fast_store": ({"MRP_HL_ROOT_FAST": "0", "MRP_MOCK_PATH_STORE": "1"}, 0),
+    "ring2_limit3_shuffle5": ({"MRP_HL_RING_DEPTH": "2", "MRP_HL_ACTIVE_LIMIT": "3", "MRP_MOCK_SHUFFLE": "5"}, 0),
+    "rounds_mode": ({}, 1),
+}
+
+
+@pytest.mark.parametrize("n_threads", [1, 2, 5])
+@pytest.mark.parametrize("branch", sorted(SCHEDULE_BRANCHES))
+def test_schedule_branches_give_the_oracles_results(cpu_solver, bench_instances, oracle_expected, monkeypatch, branch,
+                                                    n_threads):
+    from libmultirobotplanning_amd import hl
+    env, mode = SCHEDULE_BRANCHES[branch]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    s = _solver(n_threads, monkeypatch)
+    try:
+        for algo, key, names in ((hl.ECBS, "ecbs_w1.3", ROOT_CHAIN_NAMES),
+                                 (hl.CBS, "cbs", _small_cbs_names(bench_instances, oracle_expected))):
+            res, st = s.solve([bench_instances[n] for n in names], algo=algo, w=1.3, mode=mode)
+            for n, r in zip(names, res):
+                e = oracle_expected[n][key]
+                assert (r["status"], r["cost"], r["makespan"], r["hl_expanded"], r["ll_expanded"], _digest(r["paths"])) == (
+                    hl.SOLVED, e["cost"], e["makespan"], e["hl"], e["ll"], e["digest"]), (n, branch, n_threads)
+            if algo == hl.ECBS and branch in ("chain_reject_store", "no_root_fast_store"):
+                assert st["root_solved"] == 0
+            if algo == hl.ECBS and branch == "chain_reject_store":
+                # no chain ran: every ticket carries one root search or the two children of a node, and every instance
+                # had at most one chain rejected (a ticket without a search) — with chains, rounds * 3 < searches
+                assert st["ll_searches"] / 2 <= st["rounds"] <= st["ll_searches"] + len(names)
+                assert st["rounds"] >= sum(len(bench_instances[n]["starts"]) for n in names)
+    finally:
+        s.close()
+
+
+# One engine, one worker, a synchronous mock: the run is deterministic, and the ORDER in which the driver publishes its
+# searches (MRP_MOCK_TRACE: one digest per submission) is pinned together with the schedule's statistics.  Recorded from
+# the driver before it was split into SessionWorker (ct_session.hpp); a change of the publication order, the backlog
+# priority, admission or the chain decisions changes them.
+#   (rounds, ll_searches, speculative_searches, wasted_ll_expansions, root_solved), sha256 of the trace file
+SCHEDULE_TRACES = {
+    "ecbs_store": ("ecbs", {"MRP_MOCK_PATH_STORE": "1"}, (37, 232, 16, 15572, 11),
+                   "3fb5f1c73ad1dc840efdbbc37aa23553a3fd85878c560e22084adf6040a2e090"),
+    "ecbs_store_break150": ("ecbs", {"MRP_MOCK_PATH_STORE": "1", "MRP_MOCK_CHAIN_BREAK": "150"}, (97, 232, 16, 15572, 1),
+                            "1793161edebd7175e3a7b8338f1beade58b427837dd3482ba076d1e40062d51a"),
+    "ecbs_tables_ring4_limit3": ("ecbs", {"MRP_HL_RING_DEPTH": "4", "MRP_HL_ACTIVE_LIMIT": "3"}, (211, 232, 16, 15572, 0),
+                                 "04c8e02b7f8ac1b8b4878e5acb2a524be1d67d0386d20200f2ad8156f2f38bce"),
+    "cbs": ("cbs", {}, (4691, 9532, 8382, 825, 0), "c5c917fc120238068d5c3d9dbc92c4547d3b529b2c30ac5a6efcb26c9717cc34"),
+}
+
+
+@pytest.mark.parametrize("config", sorted(SCHEDULE_TRACES))
+def test_publication_order_is_unchanged(cpu_solver, bench_instances, oracle_expected, monkeypatch, tmp_path, config):
+    from libmultirobotplanning_amd import hl
+    which, env, want_stats, want_trace = SCHEDULE_TRACES[config]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    trace = tmp_path / "trace.txt"
+    monkeypatch.setenv("MRP_MOCK_TRACE", str(trace))
+    names = ROOT_CHAIN_NAMES if which == "ecbs" else _small_cbs_names(bench_instances, oracle_expected)
+    s = _solver(1, monkeypatch)
+    try:
+        _, st = s.solve([bench_instances[n] for n in names], algo=hl.ECBS if which == "ecbs" else hl.CBS, w=1.3)
+    finally:
+        s.close()
+    got = tuple(st[k] for k in ("rounds", "ll_searches", "speculative_searches", "wasted_ll_expansions", "root_solved"))
+    sha = hashlib.sha256(trace.read_bytes()).hexdigest()
+    print(config, got, sha)
+    assert got == want_stats
+    assert sha == want_trace
