@@ -1,7 +1,10 @@
 """MI355X-native low-level search engine for CBS / ECBS (the one hot path of Sartor02/libMultiRobotPlanning).
 
 Layout:
-  csrc/ll_kernel.hip      hand-written gfx950 kernels: A* / focal A*-epsilon over (time, cell) states
+  csrc/ll_kernel.hip      hand-written gfx950 kernels: A* / focal A*-epsilon over (time, cell) states; job loops, launchers
+  csrc/ll_compact.h       the compact (LDS) tier of the CBS / ECBS searches
+  csrc/ll_arena_heap.h, ll_arena_search.h, ll_jobs.h, ll_ta.h, ll_sipp.h
+                          the arena tier, job staging / runJob / runChain, task assignment, SIPP (included by ll_kernel.hip)
   csrc/mrp_ll_host.cpp    C-ABI (include/mrp_ll.h): context, map upload, batch packing, launch, results
   csrc/hl/                host-side C++ conflict-tree drivers (CBS, ECBS) that call the C-ABI (include/mrp_hl.h)
   ll.py / hl.py           ctypes plumbing used by tests and bench.py

@@ -715,7 +715,7 @@ void runSippGroupSession(mrp_ll_ctx* ctx, int32_t horizon, int32_t slots, int32_
   } tableGuard{st};
   // at most one wavefront per instance, and as many over all workers as the device holds (mrp_ll_session_occupancy:
   // sixteen per CU with the kernel's 9.2 KB LDS tier).  Round 2 found that more resident wavefronts only slowed each other
-  // down; that was with cached tables and a fence pair per job — with uncached tables residency pays (ll_kernel.hip,
+  // down; that was with cached tables and a fence pair per job — with uncached tables residency pays (ll_sipp.h,
   // MRP_LL_SIPP_LDS_NODES).
   int32_t occS = 6;
   if (mrp_ll_session_occupancy(ctx, MRP_LL_SIPP, &occS) != MRP_LL_SUCCESS || occS <= 0) occS = 6;

@@ -28,7 +28,7 @@
 //   * The job arrives, and the result leaves, through a block of the LDS window; compactSearch is a real function (not
 //     inlined into the kernels), so nothing of the kernels' own state occupies scalar registers while a search runs.
 // Limits of the tier (a search that would exceed one returns C_OVERFLOW before touching anything of that expansion and is
-// run again by the arena tier, ll_kernel.hip): maps up to 32 x 32, 1023 open entries, t <= 61 for an expanded node,
+// run again by the arena tier, ll_jobs.h runJob): maps up to 32 x 32, 1023 open entries, t <= 61 for an expanded node,
 // focalH <= 511, at most 64 edge constraints, at most 128 agents in the focal context.
 #pragma once
 #include <stddef.h>
@@ -862,7 +862,7 @@ WV_ENTRY int32_t compactSearch(Lds window) {
 // ---- the low level of the task-assignment callers ----------------------------------------------
 // AStar::search (a_star.hpp:63-161) over the Environment of example/cbs_ta.cpp:283-372,483-496 (cbs_ta.hpp:106-109,
 // 155-158,196-199).  CBS-TA only: ecbs_ta.hpp:498-499 runs AStarEpsilon over the same Environment, which is
-// MRP_LL_ASTAR_EPS_TA (ll_kernel.hip runJobTaEps), not this search:
+// MRP_LL_ASTAR_EPS_TA (ll_ta.h runJobTaEps), not this search:
 //   * the task (goal) is optional: without one h = 0, every cell is a goal cell, and the search may end as soon as
 //     time > the time of the agent's LAST vertex constraint of any cell (setLowLevelContext :283-303, isSolution :313-319);
 //   * h = shortest-path distance to the task's cell from an uploaded table (shortest_path_heuristic.hpp:56-60);

@@ -1,0 +1,544 @@
+// From a job descriptor to a search: the LDS window's size, the host / path-store access helpers (hostLoad32, hostStore32,
+// storeLoad), job staging shared by all searches (stageConstraints, fillCtx, putCJob / getCRes), the arena slot's cut
+// (cutHeaps, cutArena), and the two CBS / ECBS job runners: runJob (compact tier, then arena tier) and runChain (the root
+// chain of an ECBS conflict tree).
+// Needs ll_compact.h (ct::), ll_arena_heap.h and ll_arena_search.h.
+#ifndef MRP_LL_JOBS_H
+#define MRP_LL_JOBS_H
+
+namespace mrp {
+
+// ---- LDS layout ------------------------------------------------------------------------------------------------
+// Dynamic LDS of a CBS / ECBS workgroup: the compact tier's window (ll_compact.h: open list, focal list, walk queue,
+// (time, cell) bitmap, obstacle row), then the focal path table.  A search that has left the compact tier keeps the
+// heaps' top entries in the same window (TierHyb).
+// bg: the window of the A*-epsilon-only kernels (ll_compact.h BG: the (time, cell) bitmap lives in the arena slot)
+__host__ __device__ inline uint32_t ldsBytes(uint32_t pathBytes, bool bg) { return ct::windowBytes(bg) + pathBytes; }
+
+// A read of the device path store.  The slot was written by another workgroup (another CU, possibly another XCD) of the
+// same resident launch before its completion was published; an agent-scope load goes past this CU's L1 to the coherent
+// level, so no cache has to be invalidated for it (a per-job acquire fence would drop the whole L1 of the CU under the
+// ten other searches that share it).
+DEVI uint32_t storeLoad(const uint16_t* p) {
+#ifdef MRP_LL_STORE_ACQUIRE_FENCE
+  return *p;
+#else
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+}
+
+// Words the HOST wrote (job descriptors, constraint words, id lists, shipped tables) and words the host READS (result
+// records, paths): system-scope accesses that go past this XCD's L2 in both directions.  The resident loop publishes and
+// consumes jobs without cache-wide fences (residentLoop), so nothing else guarantees that a plain load of a recycled job
+// slot does not find the previous occupant in L2, or that a plain store has left it when the done word is written.
+DEVI uint32_t hostLoad32(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+DEVI void hostStore32(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
+
+// ---- job staging shared by the searches (runJob, runChain, runJobTA, runJobTaEps, runSipp) -----------------------------
+// The job's constraint words leave host memory in one coalesced pass into the arena's copy area; a list of more than
+// kConsLocalWords words is read where the host put it, with plain loads behind one acquire fence.  The vertex words and
+// the edge words are ONE run: the host packer pushes them back to back, ec_off == vc_off + n_vc (mrp_ll_host.cpp packJob).
+DEVI void stageConstraints(const uint32_t* consHost, uint32_t vcOff, uint32_t nVc, uint32_t nEc, uint32_t* consLocal,
+                           const uint32_t*& vc, const uint32_t*& ec) {
+  const uint32_t* src = consHost + vcOff;
+  const uint32_t nWords = nVc + nEc;
+  if (nWords <= kConsLocalWords) {
+    for (uint32_t i = threadIdx.x; i < nWords; i += 64) consLocal[i] = hostLoad32(src + i);
+    vc = consLocal;
+  } else {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+    vc = src;
+  }
+  ec = vc + nVc;
+}
+
+// What a search's Ctx takes from the job descriptor; vc / ec (stageConstraints) and the path table are the caller's.
+// UNI: the descriptor is read through a pointer the compiler cannot prove wave-uniform (runJobTaEps's argument).
+template <bool UNI = false>
+DEVI void fillCtx(Ctx& c, const DevJob& J, const uint32_t* maps, volatile uint32_t* debug) {
+  auto u = [](uint32_t v) { return UNI ? rfl(v) : v; };
+  c.dimx = u(J.dimx); c.dimy = u(J.dimy); c.wpr = u(J.words_per_row);
+  c.gx = u(J.gx); c.gy = u(J.gy); c.sx = u(J.sx); c.sy = u(J.sy);
+  c.lastGoal = (int32_t)u((uint32_t)J.last_goal_constraint);
+  c.w = __builtin_bit_cast(float, u(__builtin_bit_cast(uint32_t, J.w)));
+  c.nVc = u(J.n_vc); c.nEc = u(J.n_ec);
+  c.obst = maps + u(J.map_word_off);
+  c.nAgentsPad = u(J.n_agents_pad); c.tPad = u(J.t_pad);
+  c.maxExp = UNI ? (int64_t)rfl64((uint64_t)J.max_expansions) : J.max_expansions;
+  c.debug = debug;
+}
+
+// A compact-tier job goes into its block of the LDS window (every lane stores the same words) and the result comes back
+// from there: the ct:: searches are real functions with their own register allocation.
+DEVI void putCJob(uint8_t* smem, const ct::CJob& cj) {
+  auto w32 = (__attribute__((address_space(3))) uint32_t*)((wv::Lds)smem + ct::oJob);
+  const uint32_t* src = (const uint32_t*)&cj;
+#pragma unroll
+  for (uint32_t q = 0; q < sizeof(ct::CJob) / 4; ++q) w32[q] = src[q];
+}
+DEVI ct::CRes getCRes(uint8_t* smem) {
+  auto r32 = (__attribute__((address_space(3))) const uint32_t*)((wv::Lds)smem + ct::oRes);
+  ct::CRes cr;
+  cr.status = (int32_t)rfl(r32[0]); cr.cost = (int32_t)rfl(r32[1]); cr.fmin = (int32_t)rfl(r32[2]);
+  cr.nStates = (int32_t)rfl(r32[3]); cr.expanded = rfl(r32[4]); cr.nodes = rfl(r32[5]);
+  return cr;
+}
+// The narrow geometry as mrp_ll_configure_tiers sized it: lds_nodes / 2 = open-list entries, lds_rows = time steps a
+// search may use inside the tier; and the expansion budget in the tier's 32 bits (all ones: unlimited).
+DEVI uint32_t narrowOpenCap(const LaunchParams& P) { return P.lds_nodes / 2u < ct::kCap ? P.lds_nodes / 2u : ct::kCap; }
+DEVI uint32_t narrowMaxT(const LaunchParams& P) {
+  return P.lds_rows >= 3u && P.lds_rows - 2u < ct::kMaxT ? P.lds_rows - 2u : ct::kMaxT;
+}
+DEVI uint32_t clampMaxExp(int64_t maxExp) {
+  return maxExp < 0 ? 0xFFFFFFFFu : (maxExp > 0xFFFFFFFEll ? 0xFFFFFFFEu : (uint32_t)maxExp);
+}
+
+// Three heap arrays (open, focal, walk queue) of `cap` 64-bit entries each from `p` on, every one with the bias slot in
+// front of it; returns the first byte behind them.
+DEVI uint8_t* cutHeaps(Mem<TierHbm>& g, uint8_t* p, uint32_t cap) {
+  g.open = (Mem<TierHbm>::PE)(p + 8);          p += (size_t)cap * 8 + 16;
+  g.focal = (Mem<TierHbm>::PE)(p + 8);         p += (size_t)cap * 8 + 16;
+  g.aux = (Mem<TierHbm>::PE)(p + 8);           p += (size_t)cap * 8 + 16;
+  g.capNodes = cap; g.capHeap = cap;
+  return p;
+}
+// The arena slot as most searches use it: arena_nodes node records, the three heaps, the (time, cell) bitmap.
+DEVI Mem<TierHbm> cutArena(const LaunchParams& P, uint8_t* arenaSlot) {
+  Mem<TierHbm> g = {};
+  g.nodes = (Mem<TierHbm>::PN32)arenaSlot;
+  g.bits = (Mem<TierHbm>::P32)cutHeaps(g, arenaSlot + (size_t)P.arena_nodes * 16, P.arena_nodes);
+  g.capRows = P.arena_rows; g.rowWords = P.arena_row_words;
+  return g;
+}
+
+// Which tiers a kernel carries:
+//   kTiersAll   — compact (narrow) tier, then the arena tier: batch kernels, CBS / mixed sessions, A*-epsilon sessions
+//                 without heavy workgroups;
+//   kTiersFront — the compact (narrow) tier only: a search it cannot hold is handed to the heavy workgroups (runJob returns
+//                 true, nothing of the job has been reported); no arena-tier code in the kernel;
+//   kTiersHeavy — the compact tier in its WIDE geometry (3071 open entries, long horizons, ll_compact.h), then the arena tier.
+enum : int { kTiersAll = 0, kTiersFront = 1, kTiersHeavy = 2 };
+
+// Returns true when the job has to be handed to the heavy workgroups (kTiersFront only).
+template <bool EPS, bool BG, int TIERS>
+DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t* arenaSlot, DevResult& res,
+                 uint16_t* outPath) {
+  typedef typename std::conditional<TIERS == kTiersHeavy, ct::Wide, ct::Narrow>::type Geo;
+  constexpr bool kTableMayBeInLds = TIERS != kTiersHeavy;  // the wide window holds no path table
+  const uint32_t lane = threadIdx.x;
+  const bool heavyHint = (J.ctx_flags & kCtxHeavy) != 0;
+  if (TIERS == kTiersFront) {
+    // not a search of the narrow tier (the caller says so, or the job's shape does): nothing to set up here
+    if (heavyHint || P.lds_nodes == 0 || J.dimx > 32u || J.dimy > 32u || J.n_agents_pad > 128u || J.n_ec > 64u) return true;
+  }
+  Ctx c;
+  fillCtx(c, J, P.maps, P.debug);
+
+  // ---- bulk-copy the job's constraint words and path table out of host memory (one pass, coalesced) ----
+  uint8_t* scratch = arenaSlot + P.arena_scratch_off;
+  uint32_t* consLocal = (uint32_t*)(scratch + (size_t)P.out_stride * 2);
+  uint8_t* pathsArena = (uint8_t*)(consLocal + kConsLocalWords);
+  stageConstraints(P.cons, J.vc_off, c.nVc, c.nEc, consLocal, c.vc, c.ec);
+  {
+    const uint32_t pathBytes = c.tPad * c.nAgentsPad * 2;  // multiple of 32
+    const uint32_t* psrc = (const uint32_t*)(P.paths + J.path_off);
+    uint8_t* ldsPaths = smem + Geo::windowBytes(BG);
+    c.pathsLds = nullptr;
+    if (pathBytes != 0 && (J.ctx_flags & kCtxById)) {
+      // f2: the CT node's paths are named by their slots in the device-resident path store (each was written there by
+      // the search that produced it); the time-major table [t][agent] is built here, on the device, instead of being
+      // packed by the host and read over PCIe.  One coalesced read per agent (lane = time step).
+      const bool inLds = kTableMayBeInLds && P.lds_nodes != 0 && pathBytes <= P.lds_paths_bytes;
+      if (!inLds && pathBytes > P.arena_paths_bytes) {  // (the host packer refuses such a job; never write past the slot)
+        res.status = ST_BAD;
+        res.expanded = 0;
+        res.nodes_created = 0;
+        return false;
+      }
+      uint16_t* dst = inLds ? (uint16_t*)ldsPaths : (uint16_t*)pathsArena;
+      {
+        uint32_t* d32 = (uint32_t*)dst;
+        for (uint32_t i = lane; i < pathBytes / 4; i += 64) d32[i] = 0xFFFFFFFFu;  // kEmptyCell everywhere
+      }
+      // The slots named here were written by OTHER workgroups of this same resident launch (possibly on another XCD,
+      // whose L2 is not coherent with ours), each before its job's completion was published (processJob writes them in
+      // front of residentLoop's system-scope release).  One agent-scope acquire drops whatever stale copies this CU's L1 /
+      // this XCD's L2 may hold from an earlier use of a recycled slot; after it plain, cached, coalesced loads are
+      // correct (MI355X_MICROARCH.md "Valid forms": poll -> ONE acquire -> s_waitcnt -> barrier -> plain loads).
+#ifdef MRP_LL_STORE_ACQUIRE_FENCE  // A/B: one fence + plain loads instead of agent-scope loads
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+      __syncthreads();
+      const uint32_t* ids = P.cons + J.path_off;
+      const uint32_t nCtx = J.n_ctx;
+      for (uint32_t a0 = 0; a0 < nCtx; a0 += 64) {
+        // this chunk's ids and lengths, one agent per lane (one gather for all lengths)
+        uint32_t idL = kNoStoreSlot, lenL = 0;
+        if (a0 + lane < nCtx) idL = hostLoad32(ids + a0 + lane);
+        if (idL < P.path_store_slots) lenL = storeLoad(P.path_store + (size_t)idL * P.path_store_stride);
+        if (lenL > P.path_store_stride - 1) lenL = P.path_store_stride - 1;
+        const uint32_t nHere = nCtx - a0 < 64 ? nCtx - a0 : 64;
+        if (!inLds) {
+          // Table in the arena (global memory): one lane per AGENT, so that a row of the table is one coalesced store
+          // (a lane per time step would scatter 2-byte stores 2 * n_agents_pad bytes apart — measured on agents100: the
+          // longest conflict-tree chain of a batch a third slower).  The reads gather one cell per slot and stay in L2
+          // from row to row; eight rows are in flight at a time.
+          const uint32_t lenA = lenL;
+          const uint16_t* slotA = P.path_store + (size_t)(idL < P.path_store_slots ? idL : 0) * P.path_store_stride + 1;
+          const bool hasA = idL < P.path_store_slots && lenA != 0;
+          for (uint32_t t0 = 0; t0 < c.tPad; t0 += 8) {
+            uint32_t v[8];
+#pragma unroll
+            for (uint32_t u = 0; u < 8; ++u) {
+              const uint32_t t = t0 + u;
+              v[u] = kEmptyCell;
+              if (hasA && t < c.tPad) v[u] = storeLoad(slotA + (t < lenA ? t : lenA - 1));
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < 8; ++u)
+              if (hasA && t0 + u < c.tPad) dst[(t0 + u) * c.nAgentsPad + a0 + lane] = (uint16_t)v[u];
+          }
+          continue;
+        }
+        // table in LDS: a lane per time step (one coalesced read per agent); eight agents' loads are in flight before
+        // the first store
+        for (uint32_t t0 = 0; t0 < c.tPad; t0 += 64) {
+          const uint32_t t = t0 + lane;
+          for (uint32_t q0 = 0; q0 < nHere; q0 += 8) {
+            uint32_t v[8];
+            bool has[8];
+#pragma unroll
+            for (uint32_t u = 0; u < 8; ++u) {
+              uint32_t id = kNoStoreSlot, len = 0;
+              if (q0 + u < nHere) {
+                id = __builtin_amdgcn_readlane(idL, q0 + u);
+                len = __builtin_amdgcn_readlane(lenL, q0 + u);
+              }
+              has[u] = id < P.path_store_slots && len != 0 && t < c.tPad;  // not: empty path / the searching agent itself
+              v[u] = kEmptyCell;
+              if (has[u]) v[u] = storeLoad(P.path_store + (size_t)id * P.path_store_stride + 1 + (t < len ? t : len - 1));
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < 8; ++u)
+              if (has[u]) dst[t * c.nAgentsPad + a0 + q0 + u] = (uint16_t)v[u];
+          }
+        }
+      }
+      c.paths = dst;
+      if (inLds) c.pathsLds = (__attribute__((address_space(3))) const uint16_t*)ldsPaths;
+    } else if (pathBytes == 0) {
+      c.paths = nullptr;
+    } else if (kTableMayBeInLds && P.lds_nodes != 0 && pathBytes <= P.lds_paths_bytes) {
+      uint32_t* dst = (uint32_t*)ldsPaths;
+      for (uint32_t i = lane; i < pathBytes / 4; i += 64) dst[i] = hostLoad32(psrc + i);
+      c.paths = (const uint16_t*)ldsPaths;
+      c.pathsLds = (__attribute__((address_space(3))) const uint16_t*)ldsPaths;
+    } else if (pathBytes <= P.arena_paths_bytes) {
+      uint32_t* dst = (uint32_t*)pathsArena;
+      for (uint32_t i = lane; i < pathBytes / 4; i += 64) dst[i] = hostLoad32(psrc + i);
+      c.paths = (const uint16_t*)pathsArena;
+    } else {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+      c.paths = P.paths + J.path_off;
+    }
+  }
+  __syncthreads();
+
+  SState s;
+  int rc = ST_BAD;
+  res.tier = 0;
+
+  // ---- compact tier (ll_compact.h): the whole search in LDS, a state = its 32-bit heap entry.  Maps up to 32 x 32 and
+  // up to 128 agents in the focal context; a search that outgrows the tier (open list, time steps, focalH field) comes
+  // back as C_OVERFLOW with nothing of it observable, and is run again from the start by the next tier.
+  // the wide geometry: as many time steps as the arena slot's node area has room for (cameFrom table + bitmap), in
+  // chunks of 64, up to the job's horizon
+  uint32_t geoRows = Geo::kRows;
+  if (TIERS == kTiersHeavy) {
+    const uint64_t room = (uint64_t)P.arena_nodes * 16u / (1024u + ct::kRowBytes);
+    geoRows = (uint32_t)(room < P.arena_rows ? room : P.arena_rows) & ~63u;
+  }
+  const bool compactOk = !(TIERS == kTiersAll && heavyHint) && P.lds_nodes != 0 && c.dimx <= 32u && c.dimy <= 32u &&
+                         c.nAgentsPad <= 128u && c.nEc <= 64u && geoRows >= 64u &&
+                         (uint64_t)P.arena_nodes * 16u >= Geo::parentBytes(geoRows) + (BG ? Geo::bitsBytes(geoRows) : 0u);
+  bool done = false;
+  if (compactOk) {
+    ct::CJob cj;
+    cj.dimx = c.dimx; cj.dimy = c.dimy; cj.sx = c.sx; cj.sy = c.sy; cj.gx = c.gx; cj.gy = c.gy;
+    cj.lastGoal = c.lastGoal;
+    cj.w = c.w;
+    cj.nVc = c.nVc; cj.nEc = c.nEc;
+    cj.obstWords = c.wpr;
+    cj.nAgentsPad = EPS ? c.nAgentsPad : 0u; cj.tPad = c.tPad;
+    cj.maxExp = clampMaxExp(c.maxExp);
+    cj.rows = geoRows;
+    if (TIERS == kTiersHeavy) {  // the wide geometry at its full size
+      cj.openCap = Geo::kCap;
+      cj.maxT = Geo::kMaxT < geoRows - 2u ? Geo::kMaxT : geoRows - 2u;
+    } else {
+      cj.openCap = narrowOpenCap(P);
+      cj.maxT = narrowMaxT(P);
+    }
+    cj.taNoGoal = 0;
+    cj.vc = (uint64_t)c.vc; cj.ec = (uint64_t)c.ec;
+    cj.obst = (uint64_t)c.obst;
+    cj.pathsG = (uint64_t)c.paths;
+    cj.parentTab = (uint64_t)arenaSlot;  // the arena's node area: unused while the search is in this tier
+    cj.outPath = (uint64_t)outPath;
+    cj.bitsG = (uint64_t)(arenaSlot + Geo::parentBytes(geoRows));  // (BG) ... and its (time, cell) bitmap behind it
+    putCJob(smem, cj);
+    const bool tableInLds = !EPS || c.nAgentsPad == 0u || c.pathsLds != nullptr;
+#ifndef MRP_LL_TRACE  // (the trace build uses prof[] for its phase counters)
+    const uint64_t tl0 = __builtin_amdgcn_s_memrealtime();
+#endif
+    int32_t crc;
+    if constexpr (TIERS == kTiersHeavy)
+      crc = ct::compactSearch<EPS, false, BG, ct::Wide>((wv::Lds)smem);
+    else
+      crc = tableInLds ? ct::compactSearch<EPS, true, BG>((wv::Lds)smem) : ct::compactSearch<EPS, false, BG>((wv::Lds)smem);
+    const ct::CRes cr = getCRes(smem);
+#ifndef MRP_LL_TRACE
+    // 100 MHz ticks / expansions in the compact tier (of a search that was handed over: until then); the wide geometry
+    // reports into the arena tier's pair — "the searches that outgrew the narrow tier"
+    res.prof[TIERS == kTiersHeavy ? 2 : 0] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - tl0);
+    res.prof[TIERS == kTiersHeavy ? 3 : 1] = cr.expanded;
+#endif
+#ifdef MRP_CT_PROF  // diagnostic build: the compact tier's own phase counters instead of the tier statistics
+    {
+      auto r32 = (__attribute__((address_space(3))) const uint32_t*)((wv::Lds)smem + ct::oRes + 32u);
+      for (uint32_t q = 0; q < 8; ++q) res.prof[q] = rfl(r32[q]);
+    }
+#endif
+    if (crc != ct::C_OVERFLOW) {
+      rc = crc;  // C_OK / C_NO_SOLUTION / C_CAP_EXP == ST_OK / ST_NO_SOLUTION / ST_CAP_EXP
+      res.cost = cr.cost;
+      res.fmin = cr.fmin;
+      res.n_states = cr.nStates;
+      s.expansions = cr.expanded;
+      s.nNodes = cr.nodes;
+      done = true;
+      if (TIERS == kTiersHeavy) res.tier = 2;
+    } else {
+#ifndef MRP_LL_TRACE
+      res.prof[6] = cr.expanded;  // expansions thrown away with the attempt
+      res.prof[7] = 1;
+#endif
+    }
+  }
+  if constexpr (TIERS == kTiersFront) {
+    if (!done) return true;  // the heavy workgroups run it from the start
+  } else {
+    if (!done) {
+      // HBM tier view of this workgroup's arena slot
+      const Mem<TierHbm> g = cutArena(P, arenaSlot);
+      // ... and the view the arena tier actually runs on: the same arrays, the heaps' first nTop entries in this
+      // workgroup's LDS (the compact tier's area, free once a search has left it)
+      Mem<TierHyb> gh = viewAs<TierHyb>(g);
+      {
+        const uint32_t area = Geo::windowBytes(BG) - ct::oOpen;  // (the window's control blocks in front of it stay as they are)
+        // the open list gets half of the area, the focal list five sixteenths, the walk queue the rest (MRP_LL_TOPS_EQUAL:
+        // thirds, as before the A*-epsilon kernels' window shrank)
+#ifdef MRP_LL_TOPS_EQUAL
+        const uint32_t perO = (area / 3u) & ~15u, perF = perO, perA = perO;
+#else
+        const uint32_t perO = (area / 2u) & ~15u, perF = (area * 5u / 16u) & ~15u, perA = (area - perO - perF) & ~15u;
+#endif
+        auto tops = [&](uint32_t per) {
+          uint32_t n = per >= 32u ? ((per - 8u) / 8u) : 0u;
+          if (n > 4095u) n = 4095u;
+          n = n ? ((n - 1u) | 1u) : 0u;  // odd (or 0: no LDS tier configured)
+          return P.lds_nodes == 0 ? 0u : n;
+        };
+        auto l8 = (__attribute__((address_space(3))) uint8_t*)smem + ct::oOpen;
+        gh.open = HybPtr{(__attribute__((address_space(3))) uint64_t*)(l8 + 8), (uint64_t*)g.open, tops(perO)};
+        gh.focal = HybPtr{(__attribute__((address_space(3))) uint64_t*)(l8 + perO + 8), (uint64_t*)g.focal, tops(perF)};
+        gh.aux = HybPtr{(__attribute__((address_space(3))) uint64_t*)(l8 + perO + perF + 8), (uint64_t*)g.aux, tops(perA)};
+      }
+      const bool xyEntries = P.arena_nodes <= 65536u;  // TierHybXy: 16-bit node ids leave room for the cell in the entry
+      Mem<TierHybXy> ghx = viewAs<TierHybXy>(gh);
+      res.tier = 1;
+      __syncthreads();  // previous job's / the compact attempt's LDS accesses are done
+      if (xyEntries)
+        initSearch<TierHybXy, EPS>(ghx, s, c);
+      else
+        initSearch<TierHyb, EPS>(gh, s, c);
+      __syncthreads();
+#ifndef MRP_LL_TRACE
+      const uint64_t th0 = __builtin_amdgcn_s_memrealtime();
+#endif
+      if (xyEntries)
+        rc = runSearch<TierHybXy, EPS>(ghx, s, c, res, outPath);
+      else
+        rc = runSearch<TierHyb, EPS>(gh, s, c, res, outPath);
+#ifndef MRP_LL_TRACE
+      if (TIERS != kTiersHeavy) {
+        res.prof[2] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - th0);
+        res.prof[3] = (uint32_t)s.expansions;
+      }
+#endif
+    }
+  }
+  if (rc == RUN_MIGRATE_NODES) rc = ST_CAP_NODES;
+  if (rc == RUN_MIGRATE_ROWS) rc = ST_CAP_HORIZON;
+  res.status = rc;
+  res.expanded = s.expansions;
+  res.nodes_created = s.nNodes;
+  return false;
+}
+
+// The root chain of one ECBS conflict tree (ecbs.hpp:118-136; ll_device.h kCtxChain): agent a is planned against the
+// paths of the agents in front of it, the focal table [kChainRows][n_agents_pad] stays in the window between the
+// searches and gains one column per path.  Everything runs in the compact tier; a search that outgrows it ends the chain
+// in front of it.  Written for the A*-epsilon-only kernels (BG window).
+DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t* arenaSlot, DevResult& res,
+                   uint16_t* outPath, uint16_t* hostOut) {
+  constexpr bool BG = true;
+  const uint32_t lane = threadIdx.x;
+  const uint32_t n = J.n_ctx, first = J.t_pad, npad = J.n_agents_pad;
+  const uint32_t end = J.reserved > first && J.reserved < n ? J.reserved : n;  // one past the last agent of this job
+  res.tier = 0;
+  res.n_states = 0;
+  res.expanded = 0;
+  if (P.lds_nodes == 0 || J.dimx > 32u || J.dimy > 32u || n > kChainMaxAgents || first >= n || npad < n || npad > 128u ||
+      (npad & 1u) || kChainRows * npad * 2u > P.lds_paths_bytes ||
+      (uint64_t)P.arena_nodes * 16u < ct::kParentBytes + ct::kBitsBytes ||
+      (uint64_t)n * kChainEntryWords * 2u + (uint64_t)n * 64u > (uint64_t)P.out_host_stride) {
+    res.status = ST_BAD;  // (the host packer refuses such a job)
+    return;
+  }
+  const uint32_t* who = P.cons + J.vc_off;   // starts / goals
+  const uint32_t* ids = who + n;             // path-store slots
+  uint16_t* table = (uint16_t*)(smem + ldsBytes(0, BG));
+  for (uint32_t i = lane; i < kChainRows * npad / 2u; i += 64) ((uint32_t*)table)[i] = 0xFFFFFFFFu;  // nobody anywhere
+  __syncthreads();
+  for (uint32_t a = 0; a < first; ++a) {  // the paths that exist already: lane = time step
+    const uint32_t id = rfl(hostLoad32(ids + a));
+    if (id >= P.path_store_slots) continue;
+    const uint16_t* slot = P.path_store + (size_t)id * P.path_store_stride;
+    uint32_t len = rfl(storeLoad(slot));
+    if (len > P.path_store_stride - 1) len = P.path_store_stride - 1;
+    if (len == 0) continue;
+    table[lane * npad + a] = (uint16_t)storeLoad(slot + 1 + (lane < len ? lane : len - 1));
+  }
+  __syncthreads();
+  int64_t budget = J.max_expansions;  // < 0: unlimited
+  uint32_t* hostW = (uint32_t*)hostOut;
+  uint32_t pathOff = n * kChainEntryWords;  // words
+  uint32_t done = 0, maxLen = 0;
+  bool allOk = true;
+  int64_t total = 0;
+  for (uint32_t a = first; a < end; ++a) {
+    const uint32_t sg = rfl(hostLoad32(who + a));
+    ct::CJob cj;
+    cj.dimx = J.dimx; cj.dimy = J.dimy;
+    cj.sx = sg & 0xFFu; cj.sy = (sg >> 8) & 0xFFu; cj.gx = (sg >> 16) & 0xFFu; cj.gy = sg >> 24;
+    cj.lastGoal = -1;
+    cj.w = J.w;
+    cj.nVc = 0; cj.nEc = 0;
+    cj.obstWords = J.words_per_row;
+    cj.nAgentsPad = npad; cj.tPad = kChainRows;
+    cj.maxExp = clampMaxExp(budget);
+    cj.openCap = narrowOpenCap(P);
+    cj.maxT = narrowMaxT(P);
+    cj.taNoGoal = 0;
+    cj.rows = 0;
+    cj.vc = 0; cj.ec = 0;
+    cj.obst = (uint64_t)(P.maps + J.map_word_off);
+    cj.pathsG = 0;
+    cj.parentTab = (uint64_t)arenaSlot;
+    cj.outPath = (uint64_t)outPath;
+    cj.bitsG = (uint64_t)(arenaSlot + ct::kParentBytes);
+    __syncthreads();
+    putCJob(smem, cj);
+#ifndef MRP_LL_TRACE
+    const uint64_t tl0 = __builtin_amdgcn_s_memrealtime();
+#endif
+    const int32_t crc = ct::compactSearch<true, true, BG>((wv::Lds)smem);
+    const ct::CRes cr = getCRes(smem);
+    const int32_t cost = cr.cost, fmin = cr.fmin, nStates = cr.nStates;
+    const uint32_t expanded = cr.expanded;
+#ifndef MRP_LL_TRACE
+    res.prof[0] += (uint32_t)(__builtin_amdgcn_s_memrealtime() - tl0);
+    res.prof[1] += expanded;
+#endif
+    if (crc == ct::C_OVERFLOW) {
+#ifndef MRP_LL_TRACE
+      res.prof[6] += expanded;
+      res.prof[7] += 1;
+#endif
+      allOk = false;
+      break;  // not a search of this tier: the caller runs it as an ordinary job
+    }
+    {  // the agent's entry
+      uint32_t v = 0;
+      v = lane == 0 ? (uint32_t)crc : lane == 1 ? (uint32_t)cost : lane == 2 ? (uint32_t)fmin
+          : lane == 3 ? (crc == ct::C_OK ? (uint32_t)nStates : 0u) : lane == 4 ? expanded : lane == 5 ? pathOff : 0u;
+      if (lane < kChainEntryWords) hostStore32(hostW + (size_t)done * kChainEntryWords + lane, v);
+    }
+    done += 1;
+    total += expanded;
+    if (crc != ct::C_OK) {  // no path / expansion budget: the conflict tree ends with this answer
+      allOk = false;
+      break;
+    }
+    const uint32_t len = (uint32_t)nStates;
+    maxLen = len > maxLen ? len : maxLen;
+    {  // the path: to the host, to its path-store slot, into the table
+      const uint32_t words = (len + 1u) / 2u;
+      const uint32_t* src = (const uint32_t*)outPath;
+      for (uint32_t i = lane; i < words; i += 64) hostStore32(hostW + pathOff + i, src[i]);
+      pathOff += words;
+      const uint32_t sid = rfl(hostLoad32(ids + a));
+      if (sid < P.path_store_slots && len < P.path_store_stride) {
+        uint16_t* slot = P.path_store + (size_t)sid * P.path_store_stride;
+        for (uint32_t i = lane; i < len; i += 64) __hip_atomic_store(slot + 1 + i, outPath[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(slot, (uint16_t)len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      table[lane * npad + a] = outPath[lane < len ? lane : len - 1];
+    }
+    if (budget >= 0) budget = budget > (int64_t)expanded ? budget - (int64_t)expanded : 0;  // Instance::remainingLL()
+  }
+  __syncthreads();
+  res.status = ST_OK;
+  res.n_states = (int32_t)done;
+  res.expanded = total;
+  res.cost = -1;
+  res.fmin = -1;
+  // ---- the root node's conflicts (SURVEY.md §8 f1 on the drivers' path): when the chain has planned EVERY agent of the
+  // instance, the table in the window is the root's whole solution, and this workgroup says at once whether the conflict
+  // tree has anything to do — getFirstConflict (ecbs.cpp:401-452) and focalHeuristic (ecbs.cpp:315-350) over t = 0 ..
+  // max_t - 1 (the final time step is never checked) and all pairs i < j:
+  //   vertex conflict at t: state_i(t) == state_j(t);  edge conflict: state_i(t) == state_j(t+1) && state_i(t+1) == state_j(t)
+  // Lane = time step (every path of this tier has at most 63 states); the first conflict is the smallest
+  // (t, vertex before edge, i, j).  Seven instances in ten of the ten-agent workload end here: HL 1, no conflict.
+  if (first == 0 && end == n && done == n && allOk && maxLen >= 1u && maxLen <= kChainRows) {
+    const uint32_t T = maxLen - 1u;  // <= 62
+    const bool inT = lane < T;
+    const uint32_t rowC = lane * npad, rowN = (lane + 1u < kChainRows ? lane + 1u : kChainRows - 1u) * npad;
+    uint32_t cnt = 0, bestV = 0xFFFFu, bestE = 0xFFFFu;  // this lane's (time step's) first vertex / edge pair: i << 8 | j
+    for (uint32_t i = 0; i + 1u < n; ++i) {
+      const uint32_t ci = table[rowC + i], ni = table[rowN + i];
+      for (uint32_t j = i + 1u; j < n; ++j) {
+        const uint32_t cj = table[rowC + j], nj = table[rowN + j];
+        const bool v = inT && ci == cj, e = inT && ci == nj && ni == cj;
+        cnt += (v ? 1u : 0u) + (e ? 1u : 0u);
+        if (v && bestV == 0xFFFFu) bestV = (i << 8) | j;
+        if (e && bestE == 0xFFFFu) bestE = (i << 8) | j;
+      }
+    }
+    uint32_t key = bestV != 0xFFFFu ? (lane << 24) | bestV : bestE != 0xFFFFu ? (lane << 24) | (1u << 16) | bestE : 0x7FFFFFFFu;
+#pragma unroll
+    for (uint32_t off = 32; off >= 1; off >>= 1) {
+      cnt += (uint32_t)__shfl_xor((int)cnt, (int)off, 64);
+      const uint32_t other = (uint32_t)__shfl_xor((int)key, (int)off, 64);
+      key = other < key ? other : key;
+    }
+    res.cost = (int32_t)rfl(cnt);
+    res.fmin = rfl(key) == 0x7FFFFFFFu ? -1 : (int32_t)rfl(key);
+  }
+}
+
+}  // namespace mrp
+
+#endif  // MRP_LL_JOBS_H

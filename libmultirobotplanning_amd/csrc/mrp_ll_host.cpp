@@ -440,7 +440,7 @@ struct PathSinkSlot {
   }
 };
 
-// SIPP job tables (see runSipp in ll_kernel.hip).  Safe intervals are derived from the collision intervals exactly as
+// SIPP job tables (see runSipp in ll_sipp.h).  Safe intervals are derived from the collision intervals exactly as
 // SIPPEnvironment::setCollisionIntervals does (sipp.hpp:245-284): sort by start; a safe interval [start, ci.start-1]
 // in front of every collision interval when non-empty; a final [start, INT_MAX] unless the last one ends at INT_MAX.
 struct SippScratch {  // reused across jobs of a context: packSipp allocates nothing in the steady state
@@ -800,7 +800,7 @@ bool packJob(mrp_ll_ctx* ctx, const mrp_ll_job& j, ConsSink& cs, PathSink& ps, D
     if (j.algo != MRP_LL_ASTAR_EPS || !ctx->ring.active || ctx->ring.sipp || ctx->ring.kind != 1) return false;
     if (n < 1 || n > static_cast<int>(mrp::kChainMaxAgents) || first < 0 || first >= n) return false;
     if (!j.path_ids || !j.chain_starts_goals_xy || !ctx->pathStore || mp.dimx > 32 || mp.dimy > 32) return false;
-    {  // what runChain (ll_kernel.hip) needs of the session: the compact tier, room for its focal table in the window,
+    {  // what runChain (ll_jobs.h) needs of the session: the compact tier, room for its focal table in the window,
        // an arena slot that holds the cameFrom table and the (time, cell) bitmap, room for the output in the job's host area
       const uint32_t npad = static_cast<uint32_t>((n + 15) & ~15);
       if (ctx->opt.lds_nodes == 0 || ctx->sessionLdsPathBytes == 0 || mrp::kChainRows * npad * 2u > ctx->sessionLdsPathBytes ||
@@ -916,7 +916,7 @@ bool packJob(mrp_ll_ctx* ctx, const mrp_ll_job& j, ConsSink& cs, PathSink& ps, D
                        : mrp::kNoStoreSlot;
   if (storeResult && d.store_out_id == mrp::kNoStoreSlot) return false;  // no such slot (or no store reserved)
   if (j.algo == MRP_LL_ASTAR_EPS && j.n_agents > 0 && j.path_ids) {
-    // f2: the CT node's paths by their path-store slots; the workgroup builds the table (ll_kernel.hip runJob)
+    // f2: the CT node's paths by their path-store slots; the workgroup builds the table (ll_jobs.h runJob)
     if (!j.path_len || !ctx->pathStore) return false;
     int tpad = 0;
     for (int a = 0; a < j.n_agents; ++a)
@@ -1572,7 +1572,7 @@ int mrp_ll_session_occupancy(mrp_ll_ctx* ctx, int32_t algo, int32_t* occOut) {
   if (!ctx || !occOut) return MRP_LL_E_INVALID;
   if (algo != MRP_LL_ASTAR && algo != MRP_LL_ASTAR_EPS && algo != MRP_LL_ASTAR_TA && algo != MRP_LL_SIPP) return MRP_LL_E_INVALID;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (algo == MRP_LL_SIPP) {  // the resident SIPP kernel: a fixed LDS tier (ll_kernel.hip MRP_LL_SIPP_LDS_NODES)
+  if (algo == MRP_LL_SIPP) {  // the resident SIPP kernel: a fixed LDS tier (ll_sipp.h MRP_LL_SIPP_LDS_NODES)
     const int occS = mrp_ll_sipp_persistent_occupancy();
     *occOut = occS > 0 ? std::min(occS, 32) : 6;
     return MRP_LL_SUCCESS;
@@ -2416,7 +2416,7 @@ int mrp_ll_path_store_reserve(mrp_ll_ctx* ctx, int32_t nSlots) {
   // A slot is written by one workgroup of a resident kernel and read by workgroups on other CUs / XCDs of the SAME launch.
   // Ordering is carried by the host (a reader's job is published only after the writer's completion was seen: the
   // writer's stores sit in front of a system-scope release); the reader drops stale cached copies with one agent-scope
-  // acquire per job (ll_kernel.hip runJob), so ordinary cached device memory is enough — and the paths of a conflict-
+  // acquire per job (ll_jobs.h runJob), so ordinary cached device memory is enough — and the paths of a conflict-
   // tree node, read again by job after job, are served from L2.  MRP_LL_STORE_UNCACHED=1: uncached allocation instead
   // (measured: agents100 steps 23 % longer — every table build then reads HBM).
   void* p = nullptr;

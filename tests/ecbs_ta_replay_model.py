@@ -1,4 +1,4 @@
-"""A sequential model of the data structures of MRP_LL_ASTAR_EPS_TA's device search (ll_kernel.hip runJobTaEps), for the
+"""A sequential model of the data structures of MRP_LL_ASTAR_EPS_TA's device search (ll_ta.h runJobTaEps), for the
 CPU tests: heap entries that CARRY their keys (focalH, f, g packed as in ll_device.h) instead of the reference's handles, a
 position per node for the open AND the focal array, and the decrease-key of a_star_epsilon.hpp:254-269 done the way the
 kernel does it — the open entry is re-keyed and sifted up, the focal entry is rewritten in place and nothing is sifted.
