@@ -48,7 +48,37 @@ extern "C" {
 #define MRP_LL_ASTAR_EPS 1 /* a_star_epsilon.hpp AStarEpsilon   (ECBS low level) */
 #define MRP_LL_SIPP 2      /* sipp.hpp SIPP::search over the grid Environment of example/mapf_prioritized_sipp.cpp;  */
                            /* a batch (or a session, mrp_ll_session_begin_sipp) holds either SIPP jobs or A-star     */
-                           /* jobs, not both                                                                         */
+                           /* jobs, not both.                                                                        */
+                           /* Inside the limits below a job comes back with the reference's integers (status, cost,    */
+                           /* fmin, expansions, states, actions, action costs); beyond one it comes back with the named */
+                           /* status and without a path.  Limits:                                                       */
+                           /*   times       every arrival time the search GENERATES is at most 1023 (the 10-bit g field): */
+                           /*               a successor that would arrive later ends the job with MRP_LL_CAP_HORIZON     */
+                           /*               whatever max_horizon is, even when the reference's answer does not use that   */
+                           /*               successor (a neighbour's safe interval that starts at 1024 is enough).        */
+                           /*               initial_cost (the start time) is at most 1023, else MRP_LL_BAD_JOB.           */
+                           /*   path        the raw A* solution — one state per move, before the explicit Waits of       */
+                           /*               sipp.hpp:105-128 are inserted — has at most max_horizon / 2 states           */
+                           /*               -> MRP_LL_CAP_HORIZON.  (With the Waits it has up to max_horizon - 1 states:  */
+                           /*               a smaller states_cap gives MRP_LL_PATH_TRUNCATED.)                            */
+                           /*   nodes       at most arena_nodes (cell, safe interval) states are created, the start      */
+                           /*               included -> MRP_LL_CAP_NODES.                                                 */
+                           /*   table       a table that travels with its job (the collision_* arrays, a sipp_table outside */
+                           /*               a session or one that does not fit the resident layout) with K listed cells    */
+                           /*               and S safe intervals on them in all must satisfy                              */
+                           /*                 4 * ((dimx * dimy + 1) / 2 + K + 1 + 2 * S) <= 131072  (bytes of the slot's  */
+                           /*                 table area) and  dimx * dimy + S <= max_horizon * ((max_cells + 31) / 32)   */
+                           /*               -> MRP_LL_CAP_NODES before the search starts (on 255 x 255: K + 2 * S <= 254). */
+                           /*   resident    a sipp_table stays on the device (mrp_ll_session_begin_sipp) while every cell  */
+                           /*               has at most 15 safe intervals and every finite bound of a safe interval is     */
+                           /*               below 65535; otherwise it travels whole, under the table limit above.  Same   */
+                           /*               results either way.                                                          */
+                           /* result.tier (diagnostic): 1 = run in the arena (every job whose table travels, and a job that  */
+                           /* ended before its search began: no safe interval at the start time); on a resident table 0 =  */
+                           /* finished in the LDS tier (up to 767 nodes), 2 = finished in the middle tier (node records in  */
+                           /* the arena, up to 1152 open entries in LDS), 3 = finished in the arena after both.  A search   */
+                           /* moves on when the next expansion might not fit: 60 free node records and open entries (four   */
+                           /* neighbours x 15 intervals) are wanted before every expansion.                                  */
 
 #define MRP_LL_ASTAR_TA 3  /* a_star.hpp AStar::search over the Environment of example/cbs_ta.cpp:283-372 — the low level of */
                            /* CBS with task assignment ONLY (cbs_ta.hpp:106-109,155-158,196-199; ecbs_ta.hpp runs          */
@@ -204,7 +234,7 @@ typedef struct mrp_ll_result {
   int32_t* states_txy; /* caller buffer [states_cap][3] = time, x, y ; may be NULL                            */
   int32_t* actions;    /* caller buffer [states_cap]    = MRP_LL_ACT_* ; may be NULL                          */
   int32_t states_cap;
-  int32_t tier;     /* 0 = finished in the LDS tier, 1 = run by the arena tier, 2 = by a heavy workgroup's wide LDS tier (diagnostic) */
+  int32_t tier;     /* 0 = finished in the LDS tier, 1 = run by the arena tier, 2 = by a heavy workgroup's wide LDS tier (diagnostic; MRP_LL_SIPP: 0 / 2 / 3 / 1, see MRP_LL_SIPP above) */
   int32_t* action_costs; /* caller buffer [states_cap] or NULL: PlanResult::actions[k].second (always 1 for
                           * MRP_LL_ASTAR / _EPS; 0 for a Wait at the goal with MRP_LL_ASTAR_TA; Wait durations for
                           * MRP_LL_SIPP, sipp.hpp:105-128)                                                     */

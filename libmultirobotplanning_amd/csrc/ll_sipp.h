@@ -50,8 +50,9 @@ struct TierLdsSipp {
   DEVI static E fromLane(E v, uint32_t srcLane) { return __builtin_amdgcn_readlane(v, srcLane); }
   DEVI static E shr1(E v) { return waveShr1(v); }
 };
-// SIPP middle tier, for a search that has outgrown TierLdsSipp's 2047 nodes: the node records go to the arena, the open
-// list stays in LDS as 64-bit entries (the whole fast-tier area: 3072 of them).  Only the open key of the entry is ever
+// SIPP middle tier, for a search that has outgrown TierLdsSipp's kSippLdsCap - 1 = 767 nodes: the node records go to the
+// arena, the open list stays in LDS as 64-bit entries (the whole fast-tier area, (kSippLdsBytes - 16) / 8 = 1152 of them
+// with MRP_LL_SIPP_LDS_NODES = 768).  Only the open key of the entry is ever
 // compared, so the 21 bits around it carry the node's x word (cell 16, interval 4, ends-at-INT_MAX 1): an expansion
 // then needs no node read at all, like in the fast tier.
 template <int HEAP_AS>

@@ -69,6 +69,10 @@ def lib():
         _LIB.oracle_sipp_single_at.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, I32P, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, I32P, ctypes.c_int, I32P,
                                                ctypes.c_int, I64P, I32P]
+        _LIB.oracle_sipp_single_counted.restype = ctypes.c_int
+        _LIB.oracle_sipp_single_counted.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, I32P, ctypes.c_int, ctypes.c_int,
+                                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, I32P, ctypes.c_int, I32P, I32P,
+                                                    I32P, I32P, ctypes.c_int, I64P, I32P, ctypes.c_int64]
         _LIB.oracle_mapf_record.restype = ctypes.c_int64
         _LIB.oracle_mapf_record.argtypes = [ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             I32P, ctypes.c_int, I32P, I32P, ctypes.c_int64, I32P, ctypes.c_int64,
@@ -282,6 +286,36 @@ def sipp_single_at(dimx, dimy, obstacles, start, goal, collision_intervals, star
                                     start_time, states.ctypes.data_as(I32P), cap, expanded.ctypes.data_as(I64P),
                                     cf.ctypes.data_as(I32P))
     return states[:n].tolist(), int(expanded[0]), int(cf[0]), int(cf[1])
+
+
+SIPP_COUNTERS = ("expanded", "created", "decrease_keys", "max_open", "nodes_at_max_open", "max_arrival", "raw_states",
+                 "max_intervals")
+
+
+def sipp_single_counted(dimx, dimy, obstacles, start, goal, collision_intervals, start_time=0, cap=2048, traj_cap=0):
+    """sipp_single_at with the counters of sipp_restated.hpp's Counters.  collision_intervals: [[x, y, start, end], ...];
+    consecutive entries of one location form one list, every list is one setCollisionIntervals call in order (a location
+    given twice keeps the later list, example/sipp.cpp:196-205).  Returns dict(success, cost, fmin, states [[t, x, y]],
+    actions, action_costs, the SIPP_COUNTERS, traj): traj is an int32 array [min(expanded, traj_cap)][2] = nodes created and
+    open-list size at the start of each expansion (open = 1 + discoveries - pops)."""
+    obst, obst_p = _i32(np.asarray(obstacles, dtype=np.int32).reshape(-1, 2))
+    ci, ci_p = _i32(np.asarray(collision_intervals, dtype=np.int64).clip(-2 ** 31, 2 ** 31 - 1).astype(np.int32).reshape(-1, 4))
+    states = np.zeros((cap, 3), dtype=np.int32)
+    actions = np.zeros(cap, dtype=np.int32)
+    costs = np.zeros(cap, dtype=np.int32)
+    out = np.zeros(4, dtype=np.int32)
+    cnt = np.zeros(8, dtype=np.int64)
+    traj = np.zeros((max(traj_cap, 1), 2), dtype=np.int32)
+    n = lib().oracle_sipp_single_counted(dimx, dimy, len(obst), obst_p, start[0], start[1], goal[0], goal[1], len(ci), ci_p,
+                                         start_time, out.ctypes.data_as(I32P), states.ctypes.data_as(I32P),
+                                         actions.ctypes.data_as(I32P), costs.ctypes.data_as(I32P), cap,
+                                         cnt.ctypes.data_as(I64P), traj.ctypes.data_as(I32P) if traj_cap else None, traj_cap)
+    assert n <= cap, ("sipp_single_counted: the path has more states than cap", n, cap)
+    r = dict(success=bool(out[0]), cost=int(out[1]), fmin=int(out[2]), states=[[t, x, y] for x, y, t in states[:n].tolist()],
+             actions=actions[:max(n - 1, 0)].tolist(), action_costs=costs[:max(n - 1, 0)].tolist())
+    r.update(zip(SIPP_COUNTERS, cnt.tolist()))
+    r["traj"] = traj[:min(int(cnt[0]), traj_cap)]
+    return r
 
 
 def mapf_solve_batch(algo, dimx, dimy, obstacles, starts, goals, w=1.0, cap_total=-1, n_threads=1):

@@ -497,6 +497,56 @@ int oracle_sipp_single_at(int dimx, int dimy, int nObst, const int32_t* obstXY, 
   return n;
 }
 
+// The same search with what tests/sipp_cases.py needs to classify a case against the engine's limits.  Differences from
+// oracle_sipp_single_at: consecutive entries of one location form one list and every list is one setCollisionIntervals
+// call, in order, as example/sipp.cpp:196-205 makes them (a location given twice keeps the later list); actions and their
+// durations come back too.  out[0..3] = success, cost, fmin, n_states; counters[0..7] = expanded, created, decreaseKeys,
+// maxOpen, nodesAtMaxOpen, maxArrival (-1: no neighbour), rawStates, maxIntervals; traj [trajCap][2] = nodes created and
+// open-list size at the start of each expansion (may be NULL).
+int oracle_sipp_single_counted(int dimx, int dimy, int nObst, const int32_t* obstXY, int sx, int sy, int gx, int gy, int nCI,
+                               const int32_t* ci, int startTime, int32_t* out, int32_t* statesXYT, int32_t* actions,
+                               int32_t* actionCosts, int cap, int64_t* counters, int32_t* traj, int64_t trajCap) {
+  std::vector<uint8_t> mask(static_cast<std::size_t>(dimx) * dimy, 0);
+  for (int i = 0; i < nObst; ++i) mask[obstXY[2 * i + 1] * dimx + obstXY[2 * i]] = 1;
+  sipp::GridEnv env(dimx, dimy, mask, sipp::Cell{gx, gy});
+  sipp::Sipp planner(env);
+  for (int i = 0; i < nCI;) {
+    const sipp::Cell c{ci[4 * i], ci[4 * i + 1]};
+    std::vector<sipp::Interval> list;
+    for (; i < nCI && ci[4 * i] == c.x && ci[4 * i + 1] == c.y; ++i) list.push_back(sipp::Interval{ci[4 * i + 2], ci[4 * i + 3]});
+    planner.setCollisionIntervals(c, list);
+  }
+  sipp::Counters cnt;
+  cnt.traj = traj;
+  cnt.trajCap = traj ? trajCap : 0;
+  planner.setCounters(&cnt);
+  sipp::TimedPlan sol;
+  const bool ok = planner.search(sipp::Cell{sx, sy}, sol, startTime);
+  const int n = ok ? static_cast<int>(sol.states.size()) : 0;
+  out[0] = ok ? 1 : 0;
+  out[1] = sol.cost;
+  out[2] = sol.fmin;
+  out[3] = n;
+  counters[0] = planner.expanded();
+  counters[1] = cnt.created;
+  counters[2] = cnt.decreaseKeys;
+  counters[3] = cnt.maxOpen;
+  counters[4] = cnt.nodesAtMaxOpen;
+  counters[5] = cnt.maxArrival;
+  counters[6] = cnt.rawStates;
+  counters[7] = cnt.maxIntervals;
+  for (int k = 0; k < n && k < cap; ++k) {
+    statesXYT[3 * k] = sol.states[k].first.x;
+    statesXYT[3 * k + 1] = sol.states[k].first.y;
+    statesXYT[3 * k + 2] = sol.states[k].second;
+    if (k + 1 < n) {
+      actions[k] = static_cast<int32_t>(sol.actions[k].first);
+      actionCosts[k] = sol.actions[k].second;
+    }
+  }
+  return n;
+}
+
 // ---- task-assignment callers' low level (ta_restated.hpp) ------------------------------------------
 // One AStar::search over example/cbs_ta.cpp's Environment.  hasGoal = 0: the agent has no task (cbs_ta.cpp:283-319).
 // out[0..3] = success, cost, fmin, n_states; statesTXY [cap][3], actions [cap], actionCosts [cap] (Wait at the goal: 0).

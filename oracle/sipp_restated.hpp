@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <map>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "search_restated.hpp"
@@ -79,9 +80,31 @@ struct SAction {  // sipp.hpp:164-169
   int time;
 };
 
+// What one search did, as far as SippEnv and AStar's hooks can see it (tests/sipp_cases.py classifies the device test's
+// cases with it).  Filled only when handed to Sipp::setCounters; the search itself never reads it.
+struct Counters {
+  int64_t created = 0;       // nodes: the start + every first discovery
+  int64_t decreaseKeys = 0;  // onDiscover calls for a state that had been discovered before (a_star.hpp:130-146)
+  int64_t maxOpen = 0;       // the largest open-list size at the start of an expansion ...
+  int64_t nodesAtMaxOpen = 0;  // ... and the nodes created by then
+  int64_t maxArrival = -1;   // the largest arrival time of any neighbour getNeighbors emitted (closed ones included)
+  int64_t rawStates = 0;     // states of the A* solution, before the explicit Waits are inserted
+  int64_t maxIntervals = 0;  // the largest safe-interval count of a cell getNeighbors looked at as a neighbour
+  // per expansion, in order: nodes created and open-list size when it began (open = created - expansions before it)
+  int32_t* traj = nullptr;   // [trajCap][2], may be null
+  int64_t trajCap = 0;
+};
+
 class SippEnv {  // sipp.hpp:172-313
  public:
   explicit SippEnv(GridEnv& env) : m_env(env) {}
+  void setCounters(Counters* c) { m_cnt = c; }
+  void countStart(const SState& s) {
+    if (m_cnt) {
+      m_seen.insert(s);
+      m_cnt->created = 1;
+    }
+  }
   int admissibleHeuristic(const SState& s) { return m_env.admissibleHeuristic(s.cell); }
   bool isSolution(const SState& s) {
     return m_env.isSolution(s.cell) && safe(s.cell).at(s.interval).end == INT_MAX;
@@ -94,19 +117,38 @@ class SippEnv {  // sipp.hpp:172-313
       int startT = m_lastG + mTime;
       int endT = safe(s.cell).at(s.interval).end;
       const auto& sis = safe(m.first);
+      if (m_cnt) m_cnt->maxIntervals = std::max<int64_t>(m_cnt->maxIntervals, static_cast<int64_t>(sis.size()));
       for (std::size_t i = 0; i < sis.size(); ++i) {
         const Interval& si = sis[i];
         if (si.start - mTime > endT || si.end < startT) continue;
         int t = std::max<int>(si.start, m_lastG + 1);  // isCommandValid, mapf_prioritized_sipp.cpp:129-142
+        if (m_cnt) m_cnt->maxArrival = std::max<int64_t>(m_cnt->maxArrival, t);
         out.emplace_back(SState{m.first, i}, SAction{m.second, mTime}, t - m_lastG);
       }
     }
   }
   void onExpandNode(const SState&, int, int g) {
     m_lastG = g;
+    if (m_cnt) {
+      const int64_t open = m_cnt->created - expanded;  // every earlier expansion popped one node
+      if (open > m_cnt->maxOpen) {
+        m_cnt->maxOpen = open;
+        m_cnt->nodesAtMaxOpen = m_cnt->created;
+      }
+      if (m_cnt->traj && expanded < m_cnt->trajCap) {
+        m_cnt->traj[2 * expanded] = static_cast<int32_t>(m_cnt->created);
+        m_cnt->traj[2 * expanded + 1] = static_cast<int32_t>(open);
+      }
+    }
     ++expanded;
   }
-  void onDiscover(const SState&, int, int) {}
+  void onDiscover(const SState& s, int, int) {
+    if (!m_cnt) return;
+    if (m_seen.insert(s).second)
+      m_cnt->created += 1;
+    else
+      m_cnt->decreaseKeys += 1;
+  }
 
   void setCollisionIntervals(const Cell& c, const std::vector<Interval>& ivs) {  // :245-284
     m_safe.erase(c);
@@ -144,6 +186,8 @@ class SippEnv {  // sipp.hpp:172-313
   GridEnv& m_env;
   int m_lastG = 0;
   std::unordered_map<Cell, std::vector<Interval>, CellHash> m_safe;
+  Counters* m_cnt = nullptr;
+  std::unordered_set<SState, SStateHash> m_seen;
 };
 
 struct TimedPlan {
@@ -156,12 +200,18 @@ class Sipp {  // sipp.hpp:66-134
  public:
   explicit Sipp(GridEnv& env) : m_env(env), m_astar(m_env) {}
   void setCollisionIntervals(const Cell& c, const std::vector<Interval>& ivs) { m_env.setCollisionIntervals(c, ivs); }
+  void setCounters(Counters* c) {
+    m_cnt = c;
+    m_env.setCounters(c);
+  }
   bool search(const Cell& start, TimedPlan& out, int startTime = 0) {
     PlanResult<SState, SAction, int> raw;
     out = TimedPlan();
     std::size_t idx;
     if (!m_env.findSafeInterval(start, startTime, idx)) return false;
+    m_env.countStart(SState{start, idx});
     bool ok = m_astar.search(SState{start, idx}, raw, startTime);
+    if (m_cnt && ok) m_cnt->rawStates = static_cast<int64_t>(raw.states.size());
     out.cost = raw.cost - startTime;
     out.fmin = raw.fmin;
     for (std::size_t i = 0; i < raw.actions.size(); ++i) {
@@ -184,6 +234,7 @@ class Sipp {  // sipp.hpp:66-134
  private:
   SippEnv m_env;
   AStar<SState, SAction, int, SippEnv, SStateHash> m_astar;
+  Counters* m_cnt = nullptr;
 };
 
 // main() of mapf_prioritized_sipp.cpp:214-270.  stats = {cost, totalExpanded, elapsed_ns}
