@@ -84,6 +84,9 @@ typedef struct mrp_hl_batch_stats {
   /* ECBS sessions: instances whose root node had no conflict — found by the workgroup that ran the root chain
    * (mrp_ll.h MRP_LL_JOB_ROOT_CHAIN) — and whose solution was written without a conflict-tree object */
   int64_t root_solved;
+  /* ECBS sessions with MRP_HL_DEVICE_SCAN=1: conflict-tree nodes whose first conflict and conflict count came back with their
+   * low-level search (mrp_ll.h mrp_ll_submit_scan) instead of being scanned by the driver; 0 otherwise */
+  int64_t device_scans;
 } mrp_hl_batch_stats;
 
 /* One engine context per calling thread is created internally for every worker thread on `device`. */

@@ -222,6 +222,11 @@ typedef struct mrp_ll_job {
 /* MRP_LL_JOB_HEAVY (hint, MRP_LL_ASTAR_EPS): the caller knows that this search outgrows the LDS tier every search starts in
  * (e.g. a root chain ended in front of it): no attempt is made there.  Results never depend on it. */
 #define MRP_LL_JOB_HEAVY 8
+/* MRP_LL_JOB_SCAN_CONFLICTS (mrp_ll_submit_scan below; MRP_LL_ASTAR_EPS jobs whose context names every other agent's path by its
+ * path-store slot): the workgroup that finishes the search also scans the conflict-tree node the job completes — the new
+ * path in place of agent_idx's, path_ids' paths for everybody else — and returns its first conflict and its number of
+ * conflicts with the result.  Combines with MRP_LL_JOB_HEAVY and MRP_LL_JOB_STORE_RESULT; never changes a result. */
+#define MRP_LL_JOB_SCAN_CONFLICTS 16
 #define MRP_LL_JOB_NO_GOAL 2      /* mrp_ll_job.flags, MRP_LL_ASTAR_TA: the agent has no task (cbs_ta.cpp:283-319: h = 0, every
                                    * cell ends the search once time > the agent's last vertex constraint, every Wait is free) */
 
@@ -431,6 +436,30 @@ typedef struct mrp_ll_conflict {
 } mrp_ll_conflict;
 int mrp_ll_conflict_scan(mrp_ll_ctx* ctx, int32_t n_sets, const int32_t* set_first_agent,
                          const int32_t* path_first_state, const int32_t* states_xy, mrp_ll_conflict* out);
+
+/* The same scan for a conflict-tree CHILD, done by the workgroup that ran the child's low-level search: it holds every path
+ * of the node (the focal context it built from the path store, and the path it has just found), so the node's conflicts
+ * come back with the search instead of costing the caller a scan of its own — or, for a caller who keeps the node's paths
+ * in the path store only, a trip of every path back to the host.
+ * Submission: in a session exactly mrp_ll_submit_tagged (same lock, same tag rules; collected by mrp_ll_poll_any[_tagged] /
+ * mrp_ll_poll / mrp_ll_wait); outside a session exactly mrp_ll_submit (`tag` is ignored; collected by mrp_ll_wait).
+ * `conflicts` must stay valid as long as `results` must.  Jobs with and without MRP_LL_JOB_SCAN_CONFLICTS may share the
+ * call; conflicts[i] of a job without the flag is not written.
+ * A flagged job is valid only if: algo == MRP_LL_ASTAR_EPS; path_ids != NULL, a path store is reserved and the context is
+ * accepted by id (the table-size limits of path_ids apply); n_agents >= 1 and 0 <= agent_idx < n_agents; every OTHER agent j
+ * has path_ids[j] >= 0 and path_len[j] >= 1 (getState asserts a non-empty path, ecbs.cpp:491); no MRP_LL_JOB_ROOT_CHAIN;
+ * and it came through THIS call — a flagged job sent through any other entry point is MRP_LL_BAD_JOB, like every other
+ * invalid one, and is not run.
+ * conflicts[i] of a flagged job that ends MRP_LL_OK or MRP_LL_PATH_TRUNCATED is exactly what mrp_ll_conflict_scan returns
+ * for the solution S with S[agent_idx] = the path this search found (all of it, also when the caller's buffer was too
+ * small) and S[j] = the path in slot path_ids[j]; agent numbers are indices into the job's n_agents.  With any other
+ * status found = -1 and the other nine fields are 0.  The job's result — status, cost, fmin, n_states, expanded, path,
+ * tier — is the same with and without the flag.  Works in batches and in every kind of A*-epsilon or mixed session; in a
+ * mrp_ll_session_begin_tiers session the workgroup that FINISHES the search scans (a front workgroup that hands a search
+ * over does not).  The scan is one wavefront's work, quadratic in the agents: about 12 000 ballots for 100 agents and 60
+ * time steps. */
+int mrp_ll_submit_scan(mrp_ll_ctx* ctx, int32_t tag, int32_t n_jobs, const mrp_ll_job* jobs, mrp_ll_result* results,
+                       mrp_ll_conflict* conflicts /* [n_jobs] */, int32_t* ticket);
 
 int mrp_ll_get_stats(const mrp_ll_ctx* ctx, mrp_ll_stats* out);
 int mrp_ll_reset_stats(mrp_ll_ctx* ctx);

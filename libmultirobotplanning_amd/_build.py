@@ -20,7 +20,7 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-f
 TARGETS = {
     "libmrp_ll.so": dict(srcs=["ll_kernel.hip", "conflict_kernel.hip", "heur_kernel.hip", "mrp_ll_host.cpp"],
                          deps=["ll_device.h", "ll_compact.h", "ll_arena_heap.h", "ll_arena_search.h", "ll_jobs.h", "ll_ta.h",
-                               "ll_sipp.h", "wave_dev.h", "wave_dev_bool.h", "heur_bfs.h", "heur_layout.h",
+                               "ll_sipp.h", "ll_node_scan.h", "wave_dev.h", "wave_dev_bool.h", "heur_bfs.h", "heur_layout.h",
                                "../../include/mrp_ll.h"],
                          extra=[]),
     "libmrp_hl.so": dict(srcs=["hl/mrp_hl.cpp"], deps=["hl/exact_heap.hpp", "hl/grid_mapf.hpp", "hl/ct_solver.hpp",

@@ -62,6 +62,7 @@ struct GroupResult {
   int64_t rounds = 0, searches = 0, expansions = 0;  // expansions: of the searches the conflict trees CONSUMED
   int64_t specSearches = 0, specWasted = 0;          // searches issued ahead of their node's pop; expansions that were run but never consumed
   int64_t rootSolved = 0;                            // instances whose root node was conflict-free, written out without a conflict tree
+  int64_t deviceScans = 0;                           // conflict-tree nodes whose conflicts came with their low-level search
   double buildS = 0, llS = 0, consumeS = 0;
   std::string err;
 };
@@ -178,6 +179,11 @@ struct JobBatch {
       }
   }
 };
+
+// mrp_ll_submit_scan through a weak reference: a low-level library without it (an older engine, the CPU tests' stand-in)
+// still loads, and the driver keeps scanning on the host.
+extern "C" __attribute__((weak)) int mrp_ll_submit_scan(mrp_ll_ctx* ctx, int32_t tag, int32_t n_jobs, const mrp_ll_job* jobs,
+                                                        mrp_ll_result* results, mrp_ll_conflict* conflicts, int32_t* ticket);
 
 // Zeroes `n` results and gives each its own `cap` states of `states`.
 inline void bindResults(mrp_ll_result* res, size_t n, std::vector<int32_t>& states, int32_t cap) {
@@ -317,6 +323,9 @@ struct SessionPlan {
   int32_t chainChunkFrom = 64;
   int64_t ringDepth = 0;    // MRP_HL_RING_DEPTH: searches published per worker at a time (0: twice its resident wavefronts)
   int32_t activeLimit = 0;  // MRP_HL_ACTIVE_LIMIT: instances a worker keeps active at a time (0: its fair share of the pool)
+  // MRP_HL_DEVICE_SCAN=1 (ECBS with a path store): a child's conflicts come back with its low-level search
+  // (mrp_ll_submit_scan) instead of being scanned here at commit and at pop time.  Same results; off by default.
+  bool deviceScan = false;
   void readKnobs() {
     auto num = [](const char* name, int64_t dflt) {
       const char* e = std::getenv(name);
@@ -330,6 +339,7 @@ struct SessionPlan {
     chainChunk = static_cast<int32_t>(std::max<int64_t>(1, num("MRP_HL_CHAIN_CHUNK", 8)));
     chainChunkFrom = static_cast<int32_t>(num("MRP_HL_CHAIN_CHUNK_FROM", 64));
     ringDepth = std::max<int64_t>(0, num("MRP_HL_RING_DEPTH", 0));
+    deviceScan = num("MRP_HL_DEVICE_SCAN", 0) != 0;
     activeLimit = std::getenv("MRP_HL_ACTIVE_LIMIT") ? static_cast<int32_t>(std::max<int64_t>(1, num("MRP_HL_ACTIVE_LIMIT", 1))) : 0;
   }
 };
@@ -353,6 +363,7 @@ class SessionWorker {
   SessionWorker(const SessionPlan& plan, const WorkerSeat& seat, GroupResult& out)
       : plan_(plan), seat_(seat), out_(out), tagged_(seat.coCount > 1 && seat.co != nullptr),
         rootChains_(plan.pathSlots > 0 && plan.opt.algo == MRP_HL_ECBS && plan.rootChains),
+        deviceScan_(plan.deviceScan && plan.pathSlots > 0 && plan.opt.algo == MRP_HL_ECBS && &mrp_ll_submit_scan != nullptr),
         // this worker's share of the engine's resident wavefronts
         myWorkgroups_(std::max(1, plan.workgroups / std::max(seat.coCount, 1))),
         source_{plan.view, plan.pool, seat.own, seat.engineIdx} {
@@ -400,6 +411,7 @@ class SessionWorker {
     std::vector<mrp_ll_result> res;
     std::vector<int32_t> states;
     std::vector<int32_t> outSlot;  // per job: the path-store slot its result path also goes to (-1: none)
+    std::vector<mrp_ll_conflict> conf;  // per job, when the ticket went through mrp_ll_submit_scan (else empty): its node's conflicts
     // a root chain (MRP_LL_JOB_ROOT_CHAIN): ONE job whose result fans out into chainRes, one per agent from chainFirst on
     std::vector<mrp_ll_result> chainRes;
     int32_t chainFirst = -1;
@@ -482,6 +494,7 @@ class SessionWorker {
   }
   void releasePending(int32_t pi) {
     pend_[pi].chainFirst = -1;
+    pend_[pi].conf.clear();
     pend_[pi].chainReq.clear();
     pendFree_.push_back(pi);
   }
@@ -494,8 +507,9 @@ class SessionWorker {
   int publish(int32_t pi, int32_t nJobs, const mrp_ll_job* jobs, const char* what) {
     Pending& P = pend_[pi];
     int32_t ticket = -1;
-    const int rc = tagged_ ? mrp_ll_submit_tagged(seat_.ctx, seat_.coIndex, nJobs, jobs, P.res.data(), &ticket)
-                           : mrp_ll_submit(seat_.ctx, nJobs, jobs, P.res.data(), &ticket);
+    const int rc = !P.conf.empty() ? mrp_ll_submit_scan(seat_.ctx, tagged_ ? seat_.coIndex : 0, nJobs, jobs, P.res.data(), P.conf.data(), &ticket)
+                   : tagged_      ? mrp_ll_submit_tagged(seat_.ctx, seat_.coIndex, nJobs, jobs, P.res.data(), &ticket)
+                                  : mrp_ll_submit(seat_.ctx, nJobs, jobs, P.res.data(), &ticket);
     if (rc != MRP_LL_SUCCESS) {
       giveSlots(P);
       releasePending(pi);
@@ -609,6 +623,15 @@ class SessionWorker {
       }
     P.res.assign(jobs.size(), mrp_ll_result());
     bindResults(P.res.data(), jobs.size(), P.states, plan_.horizon);
+    if (deviceScan_ && group != kRootGroup) {  // the children whose whole context is named by slot: their conflicts come back too
+      bool any = false;
+      for (size_t q = 0; q < jobs.size(); ++q)
+        if (batch_.idOk[q]) {
+          jobs[q].flags |= MRP_LL_JOB_SCAN_CONFLICTS;
+          any = true;
+        }
+      if (any) P.conf.assign(jobs.size(), mrp_ll_conflict{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0});
+    }
     const int rc = publish(pi, static_cast<int32_t>(jobs.size()), jobs.data(), "mrp_ll_submit");
     if (rc == 1) {
       L.reqHead = end;
@@ -695,6 +718,7 @@ class SessionWorker {
     Live& L = live_[k];
     if (L.counted || !L.inst->done()) return;
     writeSolution(*L.inst, plan_.view->sol(gidx_[k]));
+    out_.deviceScans += L.inst->deviceScans();
     finishLive(L, L.inst->hlExpanded(), L.inst->llExpanded(), L.inst->specSearches(), L.inst->llSearches());
   }
 
@@ -800,6 +824,7 @@ class SessionWorker {
     for (size_t q = 0; q < P.res.size(); ++q) {
       ranExpansions_ += P.res[q].expanded;
       ans_.push_back(answerOf(P.res[q], P.outSlot[q], &slotPool_));
+      if (!P.conf.empty() && P.res[q].status == MRP_LL_OK) ans_.back().scan = P.conf[q];
     }
     const int32_t group = P.group;
     releasePending(pi);
@@ -873,6 +898,7 @@ class SessionWorker {
         writeSolution(*live_[k].inst, plan_.view->sol(gidx_[k]));
         out_.expansions += live_[k].inst->llExpanded();
         out_.specSearches += live_[k].inst->specSearches();
+        out_.deviceScans += live_[k].inst->deviceScans();
       }
     out_.specWasted += ranExpansions_ - out_.expansions;
     if (tm_.on) {
@@ -889,6 +915,7 @@ class SessionWorker {
   // not const: an engine that cannot run chains — no compact tier, a window too small for the chain's focal table —
   // rejects the first one, and this worker goes on with one job per root search
   bool rootChains_;
+  bool deviceScan_;  // children go out through mrp_ll_submit_scan (SessionPlan::deviceScan, and the engine has the call)
   const int32_t myWorkgroups_;
   // f2: slots of the engine's device-resident path store, handed to the searches of this worker for their result paths.
   // Declared before every member that can hold a Path (live_, pend_ via its tickets' instances, ans_): members are

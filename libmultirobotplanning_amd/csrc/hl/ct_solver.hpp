@@ -42,6 +42,8 @@ struct LLAnswer {
   int32_t cost, fmin;
   int64_t expanded;
   PathPtr path;               // valid when status == MRP_LL_OK
+  // the conflicts of the node this search completes, when the engine scanned it (mrp_ll_submit_scan): found >= 0
+  mrp_ll_conflict scan{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 class Instance {
@@ -68,6 +70,7 @@ class Instance {
   int64_t llExpanded() const { return llExpanded_; }
   int32_t llSearches() const { return llSearches_; }
   int64_t specSearches() const { return specSearches_; }  // searches issued ahead of their node's pop
+  int64_t deviceScans() const { return deviceScans_; }    // committed nodes whose conflicts came with their search
   const PathVec& finalSolution() const { return final_; }
   int64_t remainingLL() const { return capLL_ < 0 ? -1 : std::max<int64_t>(0, capLL_ - llExpanded_); }
   // CT nodes whose children may be computed at the same time (1 = the popped node only, i.e. no speculation)
@@ -165,6 +168,7 @@ class Instance {
     status_ = st;
     branches_.clear();
     nodes_.clear();
+    scanned_.clear();
   }
   int32_t storeNode(const std::shared_ptr<CTNode>& n) {
     nodes_.push_back(n);
@@ -263,7 +267,11 @@ class Instance {
     b.parent = nodes_[pid];
     const CTNode& P = *b.parent;
     Conflict c;
-    if (!firstConflict(P.solution, c, scratch_)) {
+    // a node whose conflicts came with its search (commit) is not scanned again
+    const ScanNote* note = static_cast<size_t>(pid) < scanned_.size() && scanned_[pid].found >= 0 ? &scanned_[pid] : nullptr;
+    const bool any = note ? note->found != 0 : firstConflict(P.solution, c, scratch_);
+    if (note && any) c = note->first;
+    if (!any) {
       b.solved = true;
       b.state = Branch::READY;
       return branches_.emplace(pid, std::move(b)).first;
@@ -302,6 +310,23 @@ class Instance {
       ch.id = nextId_++;  // ++id happens whether or not the child's search succeeded
       if (a.status == MRP_LL_OK) {
         const PathPtr oldPath = ch.solution[ag];  // the parent's path of this agent
+        if (algo_ == MRP_HL_ECBS && a.scan.found >= 0) {
+          // the workgroup that ran the search scanned the child (ll_node_scan.h): focalHeuristic (ecbs.hpp:272) and the
+          // conflict branch() will split on come with the answer
+          ch.solution.set(ag, a.path);
+          ch.cost += a.cost;
+          ch.LB += a.fmin;
+          ch.focalHeuristic = a.scan.count;
+          deviceScans_ += 1;
+          int32_t id = storeNode(chp);
+          if (scanned_.size() <= static_cast<size_t>(id)) scanned_.resize(static_cast<size_t>(id) + 1);
+          scanned_[id] = ScanNote{a.scan.found ? 1 : 0,
+                                  Conflict{a.scan.time, a.scan.agent1, a.scan.agent2, a.scan.type ? Conflict::Edge : Conflict::Vertex,
+                                           a.scan.x1, a.scan.y1, a.scan.x2, a.scan.y2}};
+          open_.push(id);
+          if (static_cast<float>(ch.cost) <= static_cast<float>(bestCost_) * w_) focal_.push(id);
+          continue;
+        }
         // focalHeuristic(child) (ecbs.hpp:272): incremental while the scan horizon is unchanged (grid_mapf.hpp).  One walk
         // over the node's paths serves both horizons and both counts (PackedView: plain arrays of packed cells).
         PackedView& pv = PackedView::local();
@@ -372,6 +397,14 @@ class Instance {
   CTNode root_;
   int32_t rootAgent_ = 0;
   std::vector<std::shared_ptr<CTNode>> nodes_;  // id -> node while it is in the heaps
+  // id -> the node's first conflict as the workgroup that ran its low-level search reported it (mrp_ll_submit_scan):
+  // found -1 unknown (the host scans at pop time), 0 the node has no conflict, 1 it is `first`.  Beside the nodes, not in
+  // them: it stays empty unless answers carry scans, and a CTNode is copied for every child.
+  struct ScanNote {
+    int32_t found = -1;
+    Conflict first{};
+  };
+  std::vector<ScanNote> scanned_;
   OpenLess openLess_;
   FocalLess focalLess_;
   ExactHeap<OpenLess> open_;
@@ -384,7 +417,7 @@ class Instance {
   std::unordered_map<int32_t, Branch> branches_;  // storage index of a CT node -> its expansion
   std::vector<int32_t> cand_;
   PathVec final_;
-  int64_t hlExpanded_ = 0, llExpanded_ = 0, specSearches_ = 0;
+  int64_t hlExpanded_ = 0, llExpanded_ = 0, specSearches_ = 0, deviceScans_ = 0;
   int32_t llSearches_ = 0;
   std::vector<int32_t> scratch_;
 };

@@ -72,6 +72,12 @@ constexpr uint32_t kCtxChain = 32u;
 // front of it): no attempt there — a front workgroup hands it to the heavy workgroups at once, an all-tier kernel starts
 // it in the arena tier.
 constexpr uint32_t kCtxHeavy = 64u;
+// ctx_flags bit 7 (MRP_LL_JOB_SCAN_CONFLICTS, mrp_ll_submit_scan): behind the search the workgroup scans the conflict-tree
+// node it has just completed — the search's focal table plus the new path — for its first conflict and its number of
+// conflicts (ll_node_scan.h) and leaves the ten words of an mrp_ll_conflict in the LAST kScanOutHalfs halfwords of the job's
+// host output area (found = -1, the rest 0, when the search did not end ST_OK).  `reserved` = the searching agent's index.
+constexpr uint32_t kCtxScan = 128u;
+constexpr uint32_t kScanOutHalfs = 32;                             // (64 bytes: the area stays aligned for the path in front of it)
 constexpr uint32_t kChainEntryWords = 8;
 constexpr uint32_t kChainMaxAgents = 128;                          // (what the compact tier's focal context holds: two 64-lane row loads)
 constexpr uint32_t kChainRows = 64;                                // rows of the chain's focal table (the compact tier ends at t = 62)
@@ -136,7 +142,8 @@ struct LaunchParams {
   uint32_t lds_paths_bytes;   // capacity of the path-table copy in LDS
   uint32_t n_jobs;
   uint32_t out_stride;        // halfwords of the path scratch in an arena slot (= max_horizon)
-  uint32_t out_host_stride;   // halfwords per job of out_paths (sessions: room for a root chain's output)
+  uint32_t out_host_stride;   // halfwords per job of out_paths: the path (sessions: or a root chain's output), then, in the
+                              // last kScanOutHalfs of them, the conflicts of a kCtxScan job
   uint32_t arena_nodes;       // node capacity in the HBM tier
   uint32_t arena_rows;        // bitmap rows (time steps) in the HBM tier == max_horizon
   uint32_t arena_row_words;   // words per bitmap row the arena was sized for (>= job.words_per_row)

@@ -119,6 +119,13 @@ DEVI Mem<TierHbm> cutArena(const LaunchParams& P, uint8_t* arenaSlot) {
 //   kTiersHeavy — the compact tier in its WIDE geometry (3071 open entries, long horizons, ll_compact.h), then the arena tier.
 enum : int { kTiersAll = 0, kTiersFront = 1, kTiersHeavy = 2 };
 
+// Where runJob builds the focal table of a job that names its paths by path-store ids: behind the LDS window when it fits
+// there (never behind the wide window), else in the arena slot's path area.  (Also asked by processJob's conflict scan.)
+template <int TIERS>
+DEVI bool idTableInLds(const LaunchParams& P, uint32_t pathBytes) {
+  return TIERS != kTiersHeavy && P.lds_nodes != 0 && pathBytes <= P.lds_paths_bytes;
+}
+
 // Returns true when the job has to be handed to the heavy workgroups (kTiersFront only).
 template <bool EPS, bool BG, int TIERS>
 DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t* arenaSlot, DevResult& res,
@@ -148,7 +155,7 @@ DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t*
       // f2: the CT node's paths are named by their slots in the device-resident path store (each was written there by
       // the search that produced it); the time-major table [t][agent] is built here, on the device, instead of being
       // packed by the host and read over PCIe.  One coalesced read per agent (lane = time step).
-      const bool inLds = kTableMayBeInLds && P.lds_nodes != 0 && pathBytes <= P.lds_paths_bytes;
+      const bool inLds = idTableInLds<TIERS>(P, pathBytes);
       if (!inLds && pathBytes > P.arena_paths_bytes) {  // (the host packer refuses such a job; never write past the slot)
         res.status = ST_BAD;
         res.expanded = 0;

@@ -18,7 +18,8 @@
 //   ll_jobs.h          job staging, the arena slot's cut, runJob (compact, then arena) and runChain (ECBS root chains)
 //   ll_ta.h            TaEnv, runTaArena / runJobTA, runJobTaEps: the task-assignment low levels
 //   ll_sipp.h          SIPP: its tiers, sippLoop, runSipp, processSippJob
-//   here               processJob, batchLoop, publishDone, residentLoop, the ten kernels, the launchers
+//   ll_node_scan.h     nodeScan: the conflicts of the conflict-tree node a search has completed (also compiled for the CPU)
+//   here               scanNode, processJob, batchLoop, publishDone, residentLoop, the ten kernels, the launchers
 //
 // Reference semantics implemented (file:line in the reference project, libMultiRobotPlanning):
 //   AStarEpsilon::search   include/libMultiRobotPlanning/a_star_epsilon.hpp:86-285
@@ -40,8 +41,52 @@
 #include "ll_jobs.h"
 #include "ll_ta.h"
 #include "ll_sipp.h"
+#include "ll_node_scan.h"
 
 namespace mrp {
+
+// The conflicts of the conflict-tree node this workgroup has just completed (ll_device.h kCtxScan): the focal table runJob
+// built from the path store is still where it was — the searches only read it, the compact tier works in the window in
+// front of it and the arena tier keeps its heap tops inside that window — and outPath holds the new path.  The scan
+// (ll_node_scan.h: a function of its own, so that it does not take part in this kernel's register allocation) finds its
+// job in the window's control block, behind the job descriptor and the result record, and leaves its answer behind that:
+// the one part of the window every launch has, also one without the compact tier.
+constexpr uint32_t kScanJobOff = ct::oCtl + sizeof(DevJob) + sizeof(DevResult), kScanOutOff = kScanJobOff + sizeof(ns::NsJob);
+static_assert(kScanJobOff % 8 == 0 && kScanOutOff + ns::kOutWords * 4u <= ct::oJob, "the scan's blocks fit the control block");
+template <bool BG, int TIERS>
+DEVI void scanNode(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t* arenaSlot, int32_t status, uint32_t nStates,
+                   const uint16_t* outPath, uint16_t* pathDst) {
+  typedef typename std::conditional<TIERS == kTiersHeavy, ct::Wide, ct::Narrow>::type Geo;
+  const uint32_t lane = threadIdx.x;
+  uint32_t* dst = (uint32_t*)(pathDst + (P.out_host_stride - kScanOutHalfs));
+  if (status != ST_OK || nStates == 0u) {
+    if (lane < ns::kOutWords) hostStore32(dst + lane, lane == 0 ? 0xFFFFFFFFu : 0u);
+    return;
+  }
+  const bool byId = (J.ctx_flags & kCtxById) != 0;
+  const uint32_t pathBytes = J.t_pad * J.n_agents_pad * 2;
+  const bool inLds = idTableInLds<TIERS>(P, pathBytes);
+  ns::NsJob nj;
+  nj.nAgents = byId ? J.n_ctx : 1u;
+  nj.nPad = J.n_agents_pad; nj.tPad = J.t_pad;
+  nj.agentIdx = J.reserved;
+  nj.nStates = nStates;
+  nj.tabLds = inLds ? Geo::windowBytes(BG) : ns::kTableInGlobal;
+  nj.tabG = (uint64_t)(arenaSlot + P.arena_scratch_off + (size_t)P.out_stride * 2 + (size_t)kConsLocalWords * 4);
+  nj.newPath = (uint64_t)outPath;
+  __syncthreads();
+  {
+    auto w32 = (__attribute__((address_space(3))) uint32_t*)((wv::Lds)smem + kScanJobOff);
+    const uint32_t* src = (const uint32_t*)&nj;
+#pragma unroll
+    for (uint32_t q = 0; q < sizeof(ns::NsJob) / 4; ++q) w32[q] = src[q];
+  }
+  __syncthreads();
+  ns::nodeScan<kScanJobOff, kScanOutOff>((wv::Lds)smem);
+  __syncthreads();
+  auto r32 = (__attribute__((address_space(3))) const uint32_t*)((wv::Lds)smem + kScanOutOff);
+  if (lane < ns::kOutWords) hostStore32(dst + lane, r32[lane]);
+}
 
 // Runs the job whose descriptor is at `jobSrc` (host memory) and writes result + path to host memory.
 // KIND: 0 = the job's own algo field decides (mixed batches / sessions), 1 = A*-epsilon jobs only (ECBS), 2 = A* jobs
@@ -105,6 +150,10 @@ DEVI bool processJob(const LaunchParams& P, const DevJob* jobSrc, DevResult* res
     if (algo == 3) runJobTA(P, J, smem, arenaSlot, res, outPath);
   }
   if (TIERS == kTiersFront && handOver) return true;
+  if constexpr (KIND != 2) {
+    if (rfl(J.ctx_flags) & kCtxScan)
+      scanNode<KIND == 1, TIERS>(P, J, smem, arenaSlot, (int32_t)rfl((uint32_t)res.status), rfl((uint32_t)res.n_states), outPath, pathDst);
+  }
   PROF_ADD(res, 5);
 #if !defined(MRP_LL_TRACE) && !defined(MRP_CT_PROF)
   res.prof[4] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - tj0);  // the whole job on the device (tables, search)

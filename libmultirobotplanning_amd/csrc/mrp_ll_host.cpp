@@ -144,6 +144,8 @@ struct Ticket {
   bool allocFailed = false;
   int32_t nJobs = 0;
   mrp_ll_result* userResults = nullptr;
+  mrp_ll_conflict* userConflicts = nullptr;  // mrp_ll_submit_scan: the caller's array, one entry per job (else null)
+  std::vector<uint8_t> scanJob;   // per job: flagged MRP_LL_JOB_SCAN_CONFLICTS (its entry of userConflicts is filled in)
   std::vector<uint8_t> rejected;  // per job: rejected on the host (MRP_LL_BAD_JOB)
   std::vector<mrp_ll_sipp_table*> commitTab;  // per job: the table a sipp_commit job reports back to (else null)
   bool sipp = false;              // the batch holds MRP_LL_SIPP jobs (own kernel, own result format)
@@ -237,6 +239,8 @@ struct SessTicket {
   int32_t tag = -1;                // mrp_ll_submit_tagged: which of the context's co-workers the ticket belongs to (-1: untagged)
   int32_t n = 0, remaining = 0;
   mrp_ll_result* res = nullptr;
+  mrp_ll_conflict* conf = nullptr; // mrp_ll_submit_scan: the caller's array, one entry per job (else null)
+  std::vector<uint8_t> scanJob;    // per job: flagged MRP_LL_JOB_SCAN_CONFLICTS (its entry of conf is filled in)
   std::vector<uint8_t> state;      // per job: 0 pending, 1 consumed, 2 rejected on the host
   std::vector<uint32_t> slots;     // per job: its job slot
   std::vector<uint32_t> seq;       // per job: the done value that marks it finished
@@ -274,6 +278,7 @@ struct mrp_ll_ctx {
   std::vector<SessTicket> sess;
   std::vector<int32_t> sessFree;   // free session-ticket ids (stack)
   // co-workers (mrp_ll_submit_tagged / mrp_ll_poll_any_tagged): two host threads that share this context's session
+  mrp_ll_conflict* scanOut = nullptr;  // inside mrp_ll_submit_scan: the caller's conflicts array (what admits flagged jobs)
   static constexpr int kMaxTags = 4;
   std::mutex coMu;
   std::vector<int32_t> coStash[kMaxTags];        // finished tickets another co-worker's poll has come across (not released yet)
@@ -795,6 +800,15 @@ bool packJob(mrp_ll_ctx* ctx, const mrp_ll_job& j, ConsSink& cs, PathSink& ps, D
   if (epsTa && (j.initial_cost != 0 || (j.flags & (MRP_LL_JOB_ROOT_CHAIN | MRP_LL_JOB_HEAVY | MRP_LL_JOB_STORE_RESULT)) || j.path_ids))
     return false;
   if (j.initial_cost < 0 || j.initial_cost >= 0x40000000) return false;  // (bit 30 of the per-job word marks MRP_LL_ASTAR_TA, jobInitOf)
+  const bool scan = (j.flags & MRP_LL_JOB_SCAN_CONFLICTS) != 0;
+  if (scan) {
+    // the conflicts of the node come back through mrp_ll_submit_scan's array alone, and the workgroup scans what it holds:
+    // an A*-epsilon search whose context names EVERY other agent's path by its path-store slot (mrp_ll.h)
+    if (!ctx->scanOut || j.algo != MRP_LL_ASTAR_EPS || (j.flags & MRP_LL_JOB_ROOT_CHAIN)) return false;
+    if (!j.path_ids || !j.path_len || !ctx->pathStore || j.n_agents < 1 || j.agent_idx < 0 || j.agent_idx >= j.n_agents) return false;
+    for (int a = 0; a < j.n_agents; ++a)
+      if (a != j.agent_idx && (j.path_ids[a] < 0 || j.path_len[a] < 1)) return false;
+  }
   if (j.flags & MRP_LL_JOB_ROOT_CHAIN) {  // the root step of an ECBS conflict tree as one job (mrp_ll.h; ll_device.h kCtxChain)
     const int n = j.n_agents, first = j.agent_idx;
     if (j.algo != MRP_LL_ASTAR_EPS || !ctx->ring.active || ctx->ring.sipp || ctx->ring.kind != 1) return false;
@@ -972,7 +986,22 @@ bool packJob(mrp_ll_ctx* ctx, const mrp_ll_job& j, ConsSink& cs, PathSink& ps, D
       }
     }
   }
+  if (scan) {
+    if (j.n_agents >= 2 && !(d.ctx_flags & mrp::kCtxById)) return false;
+    d.ctx_flags |= mrp::kCtxScan;
+    d.reserved = static_cast<uint32_t>(j.agent_idx);
+  }
   return true;
+}
+
+// The conflicts of a flagged job (ll_device.h kCtxScan: ten words at the end of the job's output area) -> the caller's
+// mrp_ll_conflict; a job that did not end with a path — or never ran — has none: found = -1, the rest 0.
+void unpackConflicts(const DevResult& d, const uint16_t* outArea, uint32_t outStride, bool rejected, mrp_ll_conflict& c) {
+  static_assert(sizeof(mrp_ll_conflict) == 40 && sizeof(mrp_ll_conflict) <= 2 * mrp::kScanOutHalfs, "ten words");
+  std::memset(&c, 0, sizeof(c));
+  c.found = -1;
+  if (rejected || d.status != mrp::ST_OK) return;
+  std::memcpy(&c, outArea + (outStride - mrp::kScanOutHalfs), sizeof(c));
 }
 
 void unpackResult(mrp_ll_ctx* ctx, const DevResult& d, const uint16_t* p, bool rejected, mrp_ll_result& r, bool sipp, int dimx,
@@ -1030,7 +1059,7 @@ int fillCommonParams(mrp_ll_ctx* ctx, Ticket& t, mrp::LaunchParams& P, uint32_t&
   P.arena_scratch_off = ctx->arenaScratchOff;
   P.arena_paths_bytes = ctx->arenaPathsBytes;
   P.out_stride = static_cast<uint32_t>(ctx->opt.max_horizon);
-  P.out_host_stride = P.out_stride;  // (sessions: the ring's stride, sessionBegin)
+  P.out_host_stride = P.out_stride + mrp::kScanOutHalfs;  // the path, then a flagged job's conflicts (sessions: the ring's stride, sessionBegin)
   P.arena_nodes = static_cast<uint32_t>(ctx->opt.arena_nodes);
   P.arena_rows = static_cast<uint32_t>(ctx->opt.max_horizon);
   P.arena_row_words = ctx->arenaRowWords;
@@ -1611,7 +1640,7 @@ static int sessionBegin(mrp_ll_ctx* ctx, int32_t workgroups, bool sipp, int kind
   const uint32_t R = Ring::kSlots;
   // halfwords per job slot of the host output area: a path, or the output of a root chain (ll_device.h kCtxChain)
   // (a chain of 128 agents: 16 halfwords of header + up to 64 states each)
-  g.outStride = std::max<uint32_t>(static_cast<uint32_t>(ctx->opt.max_horizon), mrp::kChainMaxAgents * 80u);
+  g.outStride = std::max<uint32_t>(static_cast<uint32_t>(ctx->opt.max_horizon) + mrp::kScanOutHalfs, mrp::kChainMaxAgents * 80u);
   if (!g.block) {
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -2000,6 +2029,8 @@ static int sessionSubmit(mrp_ll_ctx* ctx, int32_t lane, int32_t nJobs, const mrp
   st.n = nJobs;
   st.remaining = nJobs;
   st.res = results;
+  st.conf = ctx->scanOut;
+  st.scanJob.assign(nJobs, 0);
   st.state.assign(nJobs, 0);
   st.slots.resize(nJobs);
   st.seq.resize(nJobs);
@@ -2037,6 +2068,7 @@ static int sessionSubmit(mrp_ll_ctx* ctx, int32_t lane, int32_t nJobs, const mrp
       trivialRejectedJob(ctx, d);
       st.state[i] = 2;
     }
+    st.scanJob[i] = (!g.sipp && (jobs[i].flags & MRP_LL_JOB_SCAN_CONFLICTS) && st.conf) ? 1 : 0;
     g.jobs[slot] = d;
     ctx->stats.staged_bytes += static_cast<int64_t>(sizeof(DevJob)) + 4 * static_cast<int64_t>(g.sipp ? sippWords : cs.used) +
                                (g.sipp || (d.ctx_flags & mrp::kCtxById) ? 0 : 2 * static_cast<int64_t>(d.t_pad) * d.n_agents_pad);
@@ -2091,6 +2123,8 @@ int mrp_ll_poll(mrp_ll_ctx* ctx, int32_t ticket, int32_t* doneOut) {
     else
       unpackResult(ctx, g.results[slot], g.outPaths + static_cast<size_t>(slot) * g.outStride, st.state[i] == 2,
                    st.res[i], g.sipp, g.sipp ? g.slotDimx[slot] : 0, g.slotInit[slot]);
+    if (st.scanJob[i])
+      unpackConflicts(g.results[slot], g.outPaths + static_cast<size_t>(slot) * g.outStride, g.outStride, st.state[i] == 2, st.conf[i]);
     if (g.sipp && g.slotTable[slot]) {
       finishSippTableJob(g.slotTable[slot], g.slotSippFlags[slot], g.results[slot],
                          g.outPaths + static_cast<size_t>(slot) * g.outStride);
@@ -2135,6 +2169,8 @@ static int32_t drainCompletions(mrp_ll_ctx* ctx, int32_t tag, int32_t* tickets, 
     else
       unpackResult(ctx, g.results[slot], g.outPaths + static_cast<size_t>(slot) * g.outStride, st.state[i] == 2,
                    st.res[i], g.sipp, g.sipp ? g.slotDimx[slot] : 0, g.slotInit[slot]);
+    if (st.scanJob[i])
+      unpackConflicts(g.results[slot], g.outPaths + static_cast<size_t>(slot) * g.outStride, g.outStride, st.state[i] == 2, st.conf[i]);
     if (g.sipp && g.slotTable[slot]) {
       finishSippTableJob(g.slotTable[slot], g.slotSippFlags[slot], g.results[slot],
                          g.outPaths + static_cast<size_t>(slot) * g.outStride);
@@ -2181,6 +2217,25 @@ int mrp_ll_submit_tagged(mrp_ll_ctx* ctx, int32_t tag, int32_t nJobs, const mrp_
   std::lock_guard<std::mutex> lock(ctx->coMu);
   if (!ctx->ring.active) return MRP_LL_E_INVALID;
   const int rc = sessionSubmit(ctx, 0, nJobs, jobs, results, ticketOut);
+  if (rc == MRP_LL_SUCCESS) ctx->sess[*ticketOut].tag = tag;
+  return rc;
+}
+
+int mrp_ll_submit_scan(mrp_ll_ctx* ctx, int32_t tag, int32_t nJobs, const mrp_ll_job* jobs, mrp_ll_result* results,
+                       mrp_ll_conflict* conflicts, int32_t* ticketOut) {
+  if (!ctx || !ticketOut || nJobs < 0 || (nJobs > 0 && (!jobs || !results || !conflicts))) return MRP_LL_E_INVALID;
+  if (!ctx->ring.active) {  // batch mode: mrp_ll_submit; the tag names nobody
+    ctx->scanOut = conflicts;
+    const int rc = mrp_ll_submit(ctx, nJobs, jobs, results, ticketOut);
+    ctx->scanOut = nullptr;
+    return rc;
+  }
+  if (tag < 0 || tag >= mrp_ll_ctx::kMaxTags) return MRP_LL_E_INVALID;
+  std::lock_guard<std::mutex> lock(ctx->coMu);
+  if (!ctx->ring.active) return MRP_LL_E_INVALID;
+  ctx->scanOut = conflicts;
+  const int rc = sessionSubmit(ctx, 0, nJobs, jobs, results, ticketOut);
+  ctx->scanOut = nullptr;
   if (rc == MRP_LL_SUCCESS) ctx->sess[*ticketOut].tag = tag;
   return rc;
 }
@@ -2259,6 +2314,8 @@ int mrp_ll_submit(mrp_ll_ctx* ctx, int32_t nJobs, const mrp_ll_job* jobs, mrp_ll
   auto packT0 = std::chrono::steady_clock::now();
   t.nJobs = nJobs;
   t.userResults = results;
+  t.userConflicts = ctx->scanOut;
+  t.scanJob.assign(nJobs, 0);
   t.rejected.assign(nJobs, 0);
   t.allocFailed = false;
   {
@@ -2284,6 +2341,7 @@ int mrp_ll_submit(mrp_ll_ctx* ctx, int32_t nJobs, const mrp_ll_job* jobs, mrp_ll
     ConsSinkBuf cs{t.cons};
     PathSinkBuf ps{t.paths};
     bool ok = packJob(ctx, jobs[i], cs, ps, t.jobs.host[i]);
+    t.scanJob[i] = (!t.sipp && (jobs[i].flags & MRP_LL_JOB_SCAN_CONFLICTS) && t.userConflicts) ? 1 : 0;
     if (t.sipp) {
       if (static_cast<int>(t.jobDimx.size()) < nJobs) t.jobDimx.resize(nJobs);
       t.jobDimx[i] = ok ? static_cast<int32_t>(t.jobs.host[i].dimx) : 1;
@@ -2311,7 +2369,7 @@ int mrp_ll_submit(mrp_ll_ctx* ctx, int32_t nJobs, const mrp_ll_job* jobs, mrp_ll
   *ticketOut = ti;
   t.inFlight = true;
   if (nJobs == 0) return MRP_LL_SUCCESS;
-  const uint32_t outStride = static_cast<uint32_t>(ctx->opt.max_horizon);
+  const uint32_t outStride = static_cast<uint32_t>(ctx->opt.max_horizon) + mrp::kScanOutHalfs;
   HIPCHK(ctx, t.cons.reserve(16));
   HIPCHK(ctx, t.paths.reserve(16));
   HIPCHK(ctx, t.results.resize(nJobs));
@@ -2381,11 +2439,14 @@ int mrp_ll_wait(mrp_ll_ctx* ctx, int32_t ticket) {
   if (t.nJobs == 0) return MRP_LL_SUCCESS;
   float ms = 0.f;
   if (hipEventElapsedTime(&ms, t.evK0, t.evK1) == hipSuccess) ctx->stats.kernel_ms += ms;
-  const uint32_t outStride = static_cast<uint32_t>(ctx->opt.max_horizon);
+  const uint32_t outStride = static_cast<uint32_t>(ctx->opt.max_horizon) + mrp::kScanOutHalfs;
   auto unpackT0 = std::chrono::steady_clock::now();
   for (int i = 0; i < t.nJobs; ++i) {
     unpackResult(ctx, t.results.host[i], t.outPaths.host + static_cast<size_t>(i) * outStride, t.rejected[i] != 0,
                  t.userResults[i], t.sipp, t.sipp ? t.jobDimx[i] : 0, t.jobInit[i]);
+    if (t.scanJob[i])
+      unpackConflicts(t.results.host[i], t.outPaths.host + static_cast<size_t>(i) * outStride, outStride, t.rejected[i] != 0,
+                      t.userConflicts[i]);
     if (t.sipp && t.commitTab[i])  // batch mode never uses the device-resident copies: the host adds the stays
       finishSippTableJob(t.commitTab[i], 2u, t.results.host[i], t.outPaths.host + static_cast<size_t>(i) * outStride);
   }

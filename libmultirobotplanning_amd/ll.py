@@ -17,6 +17,8 @@ _LIB_PATH = os.environ.get("MRP_LL_LIB") or os.path.join(_PKG, "lib", "libmrp_ll
 
 ASTAR, ASTAR_EPS, SIPP, ASTAR_TA, ASTAR_EPS_TA = 0, 1, 2, 3, 4
 JOB_STORE_RESULT, JOB_NO_GOAL, JOB_ROOT_CHAIN, JOB_HEAVY = 1, 2, 4, 8  # mrp_ll_job.flags (include/mrp_ll.h)
+JOB_SCAN_CONFLICTS = 16  # mrp_ll_job.flags: mrp_ll_submit_scan also returns the conflicts of the node the job completes
+SCAN_UNTOUCHED = -2      # search_batch_scan: what every field of an entry the engine did not write still holds
 OK, NO_SOLUTION, CAP_EXPANSIONS, CAP_NODES, CAP_HORIZON, BAD_JOB, PATH_TRUNCATED, CAP_FOCAL = range(8)
 ACTION_NAMES = ["Up", "Down", "Left", "Right", "Wait"]  # example/ecbs.cpp:49-55
 
@@ -72,7 +74,7 @@ EXPORTS = ["mrp_ll_create", "mrp_ll_destroy", "mrp_ll_last_error", "mrp_ll_uploa
            "mrp_ll_sipp_table_create", "mrp_ll_sipp_table_add", "mrp_ll_sipp_table_destroy", "mrp_ll_path_store_reserve",
            "mrp_ll_upload_heuristic", "mrp_ll_session_begin_tiers", "mrp_ll_session_tiers_geometry",
            "mrp_ll_session_begin_tiers_gated", "mrp_ll_submit_tagged", "mrp_ll_poll_any_tagged",
-           "mrp_ll_compute_heuristics", "mrp_ll_read_heuristic", "mrp_ll_heuristic_lookup"]
+           "mrp_ll_compute_heuristics", "mrp_ll_read_heuristic", "mrp_ll_heuristic_lookup", "mrp_ll_submit_scan"]
 
 _lib = None
 
@@ -148,6 +150,9 @@ def load_library(path: Optional[str] = None):
     lib.mrp_ll_sipp_table_destroy.argtypes = [ctypes.c_void_p]
     lib.mrp_ll_poll_any.restype = ctypes.c_int
     lib.mrp_ll_poll_any.argtypes = [ctypes.c_void_p, I32P, ctypes.c_int32, I32P]
+    lib.mrp_ll_submit_scan.restype = ctypes.c_int
+    lib.mrp_ll_submit_scan.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(mrp_ll_job),
+                                       ctypes.POINTER(mrp_ll_result), ctypes.POINTER(mrp_ll_conflict), I32P]
     if path is None:
         _lib = lib
     return lib
@@ -174,6 +179,7 @@ class LLJob:
     result_path_id: int = -1                  # f2: path-store slot that also receives the result path
     heuristic_id: int = -1                    # ASTAR_TA / ASTAR_EPS_TA: LowLevelEngine.upload_heuristic of the goal cell
     heavy: bool = False                       # MRP_LL_JOB_HEAVY: the search is known to outgrow the LDS tier (a hint)
+    scan_conflicts: bool = False              # MRP_LL_JOB_SCAN_CONFLICTS: the node's conflicts come back too (search_batch_scan)
 
 
 @dataclass
@@ -259,7 +265,7 @@ class LowLevelEngine:
                 cj.sipp_commit = 1 if j.sipp_commit else 0
             cj.result_path_id = j.result_path_id
             cj.flags = (JOB_STORE_RESULT if j.result_path_id >= 0 else 0) | (JOB_NO_GOAL if j.goal is None else 0) | \
-                (JOB_HEAVY if j.heavy else 0)
+                (JOB_HEAVY if j.heavy else 0) | (JOB_SCAN_CONFLICTS if j.scan_conflicts else 0)
             cj.heuristic_id = j.heuristic_id
             if j.path_ids is not None:
                 ids = np.ascontiguousarray(np.asarray(j.path_ids, dtype=np.int32))
@@ -293,6 +299,27 @@ class LowLevelEngine:
         cap = states_cap or self.max_horizon
         cjobs, cres, (keep, states, actions, costs) = self._marshal(jobs, cap)
         self._check(self._lib.mrp_ll_search_batch(self._h, n, cjobs, cres), "mrp_ll_search_batch")
+        return self._results(n, cap, cres, states, actions, costs)
+
+    def search_batch_scan(self, jobs: Sequence[LLJob], states_cap: Optional[int] = None, tag: int = 0):
+        """mrp_ll_submit_scan + mrp_ll_wait, in a batch or inside any session: returns (results, conflicts).  conflicts[i] is
+        a dict as conflict_scan returns for a job with scan_conflicts (found = -1, the rest 0, when the job did not end
+        with a path); every field of a job without the flag keeps SCAN_UNTOUCHED, the value the array was filled with."""
+        n = len(jobs)
+        cap = states_cap or self.max_horizon
+        cjobs, cres, (keep, states, actions, costs) = self._marshal(jobs, cap)
+        conf = (mrp_ll_conflict * max(n, 1))()
+        for c in conf:
+            for k, _ in mrp_ll_conflict._fields_:
+                setattr(c, k, SCAN_UNTOUCHED)
+        ticket = ctypes.c_int32(-1)
+        self._check(self._lib.mrp_ll_submit_scan(self._h, tag, n, cjobs, cres, conf, ctypes.byref(ticket)), "mrp_ll_submit_scan")
+        self._check(self._lib.mrp_ll_wait(self._h, ticket.value), "mrp_ll_wait")
+        return (self._results(n, cap, cres, states, actions, costs),
+                [{k: getattr(conf[i], k) for k, _ in mrp_ll_conflict._fields_} for i in range(n)])
+
+    @staticmethod
+    def _results(n, cap, cres, states, actions, costs) -> List[LLResult]:
         out = []
         for i in range(n):
             r = cres[i]
