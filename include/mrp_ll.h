@@ -461,6 +461,42 @@ int mrp_ll_conflict_scan(mrp_ll_ctx* ctx, int32_t n_sets, const int32_t* set_fir
 int mrp_ll_submit_scan(mrp_ll_ctx* ctx, int32_t tag, int32_t n_jobs, const mrp_ll_job* jobs, mrp_ll_result* results,
                        mrp_ll_conflict* conflicts /* [n_jobs] */, int32_t* ticket);
 
+/* ---- device-resident constraint store ------------------------------------------------------------------------
+ * A conflict-tree child differs from its parent in one constraint (cbs.hpp:139-161, ecbs.hpp:243-270 copy the whole set and
+ * add one).  With this store the agent's set stays on the device: the parent's search left it in a slot, the child's job
+ * names that slot and ships only what it adds — instead of the whole set being scanned, re-encoded and written to pinned
+ * host memory by the packer and read over PCIe by the workgroup for every job, O(tree depth) each.
+ * n_slots sets of up to words_per_slot packed constraint words each (vertex + edge together).
+ * words_per_slot <= 2048 (the union is assembled in the arena slot's copy area), else MRP_LL_E_INVALID.
+ * MRP_LL_E_BUSY while a batch or a session is in flight; calling it again re-allocates (contents are lost);
+ * n_slots == 0 frees the store.  mrp_ll_release_maps forgets every set (the slots stay allocated). */
+int mrp_ll_constraint_store_reserve(mrp_ll_ctx* ctx, int32_t n_slots, int32_t words_per_slot);
+
+typedef struct mrp_ll_constraint_ref {
+  int32_t base_set_id;    /* -1: none; else the set this job's agent has at the PARENT node */
+  int32_t result_set_id;  /* -1: none; else the slot that receives  base + the job's own constraint arrays */
+} mrp_ll_constraint_ref;
+
+#define MRP_LL_JOB_CONSTRAINT_SET 32   /* mrp_ll_job.flags: sets[i] of mrp_ll_submit_sets is honoured for this job */
+
+/* mrp_ll_submit_scan plus `sets`; conflicts may be NULL when no job has MRP_LL_JOB_SCAN_CONFLICTS, sets may be NULL when no
+ * job has MRP_LL_JOB_CONSTRAINT_SET.  Same lock, tag rules and collection calls as mrp_ll_submit_scan, in and outside a
+ * session.
+ * The set a flagged job's search sees is the contents of base_set_id, if any, followed by the job's vertex_constraints /
+ * edge_constraints — now the ADDITIONS, typically one or none; with result_set_id >= 0 that union is left in the slot for
+ * later jobs to name (whenever the job ran, whatever its status).  Every field of the result — status, cost, fmin, n_states,
+ * expanded, path, tier, a scan's conflicts — is exactly what the same job returns with the whole union shipped in its
+ * arrays.  Nothing is de-duplicated: a constraint added twice costs a word and changes no result.  An unflagged job of the
+ * same call ignores sets[i]: a zero-initialised job touches no slot.
+ * A set belongs to the map and the goal cell of the job that wrote it (m_lastGoalConstraint, ecbs.cpp:268-273, is kept with
+ * the set).  Slot ids are the caller's to hand out; a slot may be reused once no unfinished job names it.
+ * A flagged job comes back MRP_LL_BAD_JOB, not run and with no set created or changed, when: no store is reserved; an id is
+ * out of range; the base was never written, or the ticket of the job that writes it has not been collected yet; the base
+ * belongs to another map or another goal cell; base_set_id == result_set_id; the union exceeds words_per_slot; algo is not
+ * MRP_LL_ASTAR or MRP_LL_ASTAR_EPS; MRP_LL_JOB_ROOT_CHAIN is set; or it came through any other entry point. */
+int mrp_ll_submit_sets(mrp_ll_ctx* ctx, int32_t tag, int32_t n_jobs, const mrp_ll_job* jobs, mrp_ll_result* results,
+                       mrp_ll_conflict* conflicts, const mrp_ll_constraint_ref* sets, int32_t* ticket);
+
 int mrp_ll_get_stats(const mrp_ll_ctx* ctx, mrp_ll_stats* out);
 int mrp_ll_reset_stats(mrp_ll_ctx* ctx);
 

@@ -185,6 +185,18 @@ struct JobBatch {
 extern "C" __attribute__((weak)) int mrp_ll_submit_scan(mrp_ll_ctx* ctx, int32_t tag, int32_t n_jobs, const mrp_ll_job* jobs,
                                                         mrp_ll_result* results, mrp_ll_conflict* conflicts, int32_t* ticket);
 
+// mrp_ll_submit_sets likewise: without it (or without mrp_ll_constraint_store_reserve, mrp_hl.cpp) every job ships its whole
+// constraint set, as before.
+extern "C" __attribute__((weak)) int mrp_ll_submit_sets(mrp_ll_ctx* ctx, int32_t tag, int32_t n_jobs, const mrp_ll_job* jobs,
+                                                        mrp_ll_result* results, mrp_ll_conflict* conflicts,
+                                                        const mrp_ll_constraint_ref* sets, int32_t* ticket);
+extern "C" __attribute__((weak)) int mrp_ll_constraint_store_reserve(mrp_ll_ctx* ctx, int32_t n_slots, int32_t words_per_slot);
+inline bool engineHasConstraintStore() { return &mrp_ll_submit_sets != nullptr && &mrp_ll_constraint_store_reserve != nullptr; }
+// mrp_ll_constraint_store_reserve, or MRP_LL_E_INVALID on an engine without it
+inline int reserveConstraintStore(mrp_ll_ctx* ctx, int32_t nSlots, int32_t wordsPerSlot) {
+  return engineHasConstraintStore() ? mrp_ll_constraint_store_reserve(ctx, nSlots, wordsPerSlot) : MRP_LL_E_INVALID;
+}
+
 // Zeroes `n` results and gives each its own `cap` states of `states`.
 inline void bindResults(mrp_ll_result* res, size_t n, std::vector<int32_t>& states, int32_t cap) {
   states.resize(n * static_cast<size_t>(cap) * 3);
@@ -326,6 +338,11 @@ struct SessionPlan {
   // MRP_HL_DEVICE_SCAN=1 (ECBS with a path store): a child's conflicts come back with its low-level search
   // (mrp_ll_submit_scan) instead of being scanned here at commit and at pop time.  Same results; off by default.
   bool deviceScan = false;
+  // MRP_HL_DEVICE_CONSTRAINTS=1 (CBS and ECBS): an agent's constraint set stays in the engine's constraint store — a child's
+  // search names its parent's set by slot and ships the one constraint it adds (mrp_ll_submit_sets) instead of the whole
+  // set.  Same results; off by default.  consSlots / consWords: the store every engine reserved (0: none, the switch is off).
+  bool deviceCons = false;
+  int32_t consSlots = 0, consWords = 0;
   void readKnobs() {
     auto num = [](const char* name, int64_t dflt) {
       const char* e = std::getenv(name);
@@ -340,6 +357,7 @@ struct SessionPlan {
     chainChunkFrom = static_cast<int32_t>(num("MRP_HL_CHAIN_CHUNK_FROM", 64));
     ringDepth = std::max<int64_t>(0, num("MRP_HL_RING_DEPTH", 0));
     deviceScan = num("MRP_HL_DEVICE_SCAN", 0) != 0;
+    deviceCons = num("MRP_HL_DEVICE_CONSTRAINTS", 0) != 0;
     activeLimit = std::getenv("MRP_HL_ACTIVE_LIMIT") ? static_cast<int32_t>(std::max<int64_t>(1, num("MRP_HL_ACTIVE_LIMIT", 1))) : 0;
   }
 };
@@ -364,6 +382,7 @@ class SessionWorker {
       : plan_(plan), seat_(seat), out_(out), tagged_(seat.coCount > 1 && seat.co != nullptr),
         rootChains_(plan.pathSlots > 0 && plan.opt.algo == MRP_HL_ECBS && plan.rootChains),
         deviceScan_(plan.deviceScan && plan.pathSlots > 0 && plan.opt.algo == MRP_HL_ECBS && &mrp_ll_submit_scan != nullptr),
+        deviceCons_(plan.deviceCons && plan.consSlots > 0 && plan.consWords > 0 && engineHasConstraintStore()),
         // this worker's share of the engine's resident wavefronts
         myWorkgroups_(std::max(1, plan.workgroups / std::max(seat.coCount, 1))),
         source_{plan.view, plan.pool, seat.own, seat.engineIdx} {
@@ -371,6 +390,9 @@ class SessionWorker {
     const int32_t share = plan.pathSlots / seat.coCount;  // co-workers split the engine's path store
     slotPool_.next = tagged_ ? seat.coIndex * share : 0;
     slotPool_.cap = tagged_ ? slotPool_.next + share : plan.pathSlots;
+    const int32_t consShare = plan.consSlots / seat.coCount;  // ... and its constraint store
+    consPool_.next = tagged_ ? seat.coIndex * consShare : 0;
+    consPool_.cap = !deviceCons_ ? 0 : tagged_ ? consPool_.next + consShare : plan.consSlots;
     ringTarget_ = plan.ringDepth > 0 ? plan.ringDepth : std::max<int64_t>(2 * static_cast<int64_t>(myWorkgroups_), 32);
     // Admission control: at most `activeLimit_` instances of this worker are active at a time; the rest wait in the pool.
     // With the job slots recycled in completion order it costs nothing (measured 1536..3584 at the bench shape: same step
@@ -412,6 +434,10 @@ class SessionWorker {
     std::vector<int32_t> states;
     std::vector<int32_t> outSlot;  // per job: the path-store slot its result path also goes to (-1: none)
     std::vector<mrp_ll_conflict> conf;  // per job, when the ticket went through mrp_ll_submit_scan (else empty): its node's conflicts
+    // per job, when some job of the ticket names its constraint set by slot (mrp_ll_submit_sets; else empty) — and the sets
+    // those jobs name: a set (and with it its slot) outlives every unfinished job that reads or writes the slot
+    std::vector<mrp_ll_constraint_ref> sets;
+    std::vector<ConsPtr> consHold;
     // a root chain (MRP_LL_JOB_ROOT_CHAIN): ONE job whose result fans out into chainRes, one per agent from chainFirst on
     std::vector<mrp_ll_result> chainRes;
     int32_t chainFirst = -1;
@@ -495,6 +521,8 @@ class SessionWorker {
   void releasePending(int32_t pi) {
     pend_[pi].chainFirst = -1;
     pend_[pi].conf.clear();
+    pend_[pi].sets.clear();
+    pend_[pi].consHold.clear();
     pend_[pi].chainReq.clear();
     pendFree_.push_back(pi);
   }
@@ -507,7 +535,9 @@ class SessionWorker {
   int publish(int32_t pi, int32_t nJobs, const mrp_ll_job* jobs, const char* what) {
     Pending& P = pend_[pi];
     int32_t ticket = -1;
-    const int rc = !P.conf.empty() ? mrp_ll_submit_scan(seat_.ctx, tagged_ ? seat_.coIndex : 0, nJobs, jobs, P.res.data(), P.conf.data(), &ticket)
+    const int rc = !P.sets.empty() ? mrp_ll_submit_sets(seat_.ctx, tagged_ ? seat_.coIndex : 0, nJobs, jobs, P.res.data(),
+                                                        P.conf.empty() ? nullptr : P.conf.data(), P.sets.data(), &ticket)
+                   : !P.conf.empty() ? mrp_ll_submit_scan(seat_.ctx, tagged_ ? seat_.coIndex : 0, nJobs, jobs, P.res.data(), P.conf.data(), &ticket)
                    : tagged_      ? mrp_ll_submit_tagged(seat_.ctx, seat_.coIndex, nJobs, jobs, P.res.data(), &ticket)
                                   : mrp_ll_submit(seat_.ctx, nJobs, jobs, P.res.data(), &ticket);
     if (rc != MRP_LL_SUCCESS) {
@@ -632,8 +662,19 @@ class SessionWorker {
         }
       if (any) P.conf.assign(jobs.size(), mrp_ll_conflict{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0});
     }
+    if (deviceCons_ && group != kRootGroup) nameSets(L, P, jobs);
     const int rc = publish(pi, static_cast<int32_t>(jobs.size()), jobs.data(), "mrp_ll_submit");
+    if (rc != 1) {  // the sets that were given a slot for this attempt give it back (the ticket is gone: publish)
+      for (const ConstraintSet* S : slotted_) {
+        consPool_.give(S->devSlot);
+        S->devSlot = -1;
+        S->pool = nullptr;
+        S->devWords = 0;
+      }
+    }
+    slotted_.clear();
     if (rc == 1) {
+      for (size_t q = L.reqHead; q < end; ++q) L.req[q].constraints->parent.reset();  // (the ticket holds what its jobs name)
       L.reqHead = end;
       if (L.reqHead == L.req.size()) {
         L.req.clear();
@@ -642,6 +683,40 @@ class SessionWorker {
       out_.searches += static_cast<int64_t>(jobs.size());
     }
     return rc;
+  }
+
+  // MRP_HL_DEVICE_CONSTRAINTS: the jobs of a conflict-tree node's children name their agents' constraint sets in the engine's
+  // store.  A child's set S was made from its parent's set by one addition (ConstraintSet::parent, addVertex / addEdge):
+  // the job names the parent's slot as its base, ships the addition and leaves the union in a fresh slot, which becomes
+  // S's.  A parent without a slot (the root's empty set, a set that went flat) is no base: the job ships S whole, as today,
+  // and still leaves it in a slot for S's own children.  The job goes flat, and S gets no slot, when the pool is empty or S
+  // would not fit a slot (counted with duplicates, which the store keeps: an upper bound of the packed words).
+  void nameSets(const Live& L, Pending& P, std::vector<mrp_ll_job>& jobs) {
+    for (size_t q = 0; q < jobs.size(); ++q) {
+      const ConstraintSet& S = *L.req[L.reqHead + q].constraints;
+      if (S.devSlot >= 0) continue;  // (its search has been submitted before)
+      const ConstraintSet* base = S.parent && S.parent->devSlot >= 0 ? S.parent.get() : nullptr;
+      const int32_t words = base ? base->devWords + static_cast<int32_t>(S.addVertex.size() / 3 + S.addEdge.size() / 5)
+                                 : static_cast<int32_t>(S.vertex.size() / 3 + S.edge.size() / 5);
+      if (words > plan_.consWords) continue;
+      const int32_t slot = consPool_.take();
+      if (slot < 0) continue;
+      S.devSlot = slot;
+      S.pool = &consPool_;
+      S.devWords = words;
+      slotted_.push_back(&S);
+      if (P.sets.empty()) P.sets.assign(jobs.size(), mrp_ll_constraint_ref{-1, -1});
+      P.sets[q] = mrp_ll_constraint_ref{base ? base->devSlot : -1, slot};
+      P.consHold.push_back(L.req[L.reqHead + q].constraints);
+      jobs[q].flags |= MRP_LL_JOB_CONSTRAINT_SET;
+      if (base) {
+        P.consHold.push_back(S.parent);
+        jobs[q].n_vertex_constraints = static_cast<int32_t>(S.addVertex.size() / 3);
+        jobs[q].vertex_constraints = S.addVertex.data();
+        jobs[q].n_edge_constraints = static_cast<int32_t>(S.addEdge.size() / 5);
+        jobs[q].edge_constraints = S.addEdge.data();
+      }
+    }
   }
 
   // Scheduling.  The device queue is kept SHALLOW — at most `ringTarget_` searches published per worker, enough to hand
@@ -692,6 +767,7 @@ class SessionWorker {
     live_.emplace_back();  // (a deque: the references to the other instances stay valid)
     gidx_.push_back(it.g);
     live_.back().inst.reset(new Instance(*it.inst, it.mapId, plan_.opt));
+    live_.back().inst->setLinkSets(deviceCons_);
     if (tm_.on) live_.back().tAdmit = tm_.sinceStart();
     return true;
   }
@@ -916,11 +992,14 @@ class SessionWorker {
   // rejects the first one, and this worker goes on with one job per root search
   bool rootChains_;
   bool deviceScan_;  // children go out through mrp_ll_submit_scan (SessionPlan::deviceScan, and the engine has the call)
+  const bool deviceCons_;  // children name their constraint sets by slot (SessionPlan::deviceCons, and the engine has the call)
   const int32_t myWorkgroups_;
   // f2: slots of the engine's device-resident path store, handed to the searches of this worker for their result paths.
   // Declared before every member that can hold a Path (live_, pend_ via its tickets' instances, ans_): members are
   // destroyed in reverse order, so the pool outlives every Path that returns its slot to it.
   SlotPool slotPool_;
+  SlotPool consPool_;  // slots of the engine's constraint store, likewise (it outlives every ConstraintSet)
+  std::vector<const ConstraintSet*> slotted_;  // submitJobs: the sets that were given a slot for the ticket being published
   InstanceSource source_;
   std::deque<Live> live_;        // grows as instances are admitted; references stay valid
   std::vector<int32_t> gidx_;    // live entry -> global instance index

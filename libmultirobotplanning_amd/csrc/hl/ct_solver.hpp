@@ -75,6 +75,9 @@ class Instance {
   int64_t remainingLL() const { return capLL_ < 0 ? -1 : std::max<int64_t>(0, capLL_ - llExpanded_); }
   // CT nodes whose children may be computed at the same time (1 = the popped node only, i.e. no speculation)
   void setSpecWidth(int32_t k) { specWidth_ = std::max(1, k); }
+  // a child's constraint set remembers its parent's set and its own addition (grid_mapf.hpp ConstraintSet::parent): for a
+  // driver that names sets by their slots in the engine's constraint store
+  void setLinkSets(bool on) { linkSets_ = on; }
 
   // First call.  Appends the searches to run to `next` (nothing when done()).
   void start(std::vector<LLRequest>& next) {
@@ -283,7 +286,7 @@ class Instance {
     for (int k = 0; k < 2; ++k) {
       auto ch = std::make_shared<CTNode>(P);  // shares every path / constraint set with the parent
       const int32_t ag = ags[k];
-      ch->constraints.set(ag, withAdded(P.constraints[ag], *adds[k]));
+      ch->constraints.set(ag, withAdded(P.constraints[ag], *adds[k], linkSets_));
       ch->cost -= P.solution[ag]->cost;
       if (algo_ == MRP_HL_ECBS) ch->LB -= P.solution[ag]->fmin;
       b.child[k] = ch;
@@ -414,6 +417,7 @@ class Instance {
   bool popped_ = false;     // a node has been popped and its children are not committed yet
   int32_t current_ = -1;    // that node (storage index)
   int32_t specWidth_ = 1;
+  bool linkSets_ = false;
   std::unordered_map<int32_t, Branch> branches_;  // storage index of a CT node -> its expansion
   std::vector<int32_t> cand_;
   PathVec final_;

@@ -53,6 +53,22 @@ typedef std::shared_ptr<const Path> PathPtr;
 struct ConstraintSet {        // Constraints of one agent (ecbs.cpp:180-214) as flat arrays for the C-ABI
   std::vector<int32_t> vertex;  // [n][3] time, x, y
   std::vector<int32_t> edge;    // [n][5] time, x1, y1, x2, y2
+  // The engine's device-resident constraint store (mrp_ll_submit_sets): the search that first used this set also left it in
+  // a store slot, and a child's search names that slot and ships only what the child adds.  Filled in by the session driver
+  // when it submits the set's search (hence mutable: the sets of a conflict tree are shared, const objects); the slot goes
+  // back to its pool with the last conflict-tree node that shares the set, as a Path's does.
+  mutable int32_t devSlot = -1;
+  mutable SlotPool* pool = nullptr;
+  mutable int32_t devWords = 0;  // constraints in the slot, duplicates included (an upper bound of its packed words)
+  // withAdded(..., link = true) only, until the set's search has been submitted: the parent's set and what was added to it
+  mutable std::shared_ptr<const ConstraintSet> parent;
+  std::vector<int32_t> addVertex, addEdge;
+  ConstraintSet() = default;
+  ConstraintSet(const ConstraintSet&) = delete;
+  ConstraintSet& operator=(const ConstraintSet&) = delete;
+  ~ConstraintSet() {
+    if (pool) pool->give(devSlot);
+  }
 };
 typedef std::shared_ptr<const ConstraintSet> ConsPtr;
 
@@ -461,9 +477,18 @@ inline void splitConflict(const Conflict& c, ConstraintSet& forAgent1, Constrain
   }
 }
 
-inline ConsPtr withAdded(const ConsPtr& base, const ConstraintSet& extra) {  // Constraints::add (ecbs.cpp:184-189)
+// link: the new set remembers its parent and the addition (ConstraintSet::parent), for a driver that keeps sets on the device
+inline ConsPtr withAdded(const ConsPtr& base, const ConstraintSet& extra, bool link = false) {  // Constraints::add (ecbs.cpp:184-189)
   auto out = std::make_shared<ConstraintSet>();
-  if (base) *out = *base;
+  if (base) {
+    out->vertex = base->vertex;
+    out->edge = base->edge;
+  }
+  if (link) {
+    out->parent = base;
+    out->addVertex = extra.vertex;
+    out->addEdge = extra.edge;
+  }
   // unordered_set semantics: inserting an element that is already present changes nothing
   auto hasV = [&](const int32_t* v) {
     for (size_t k = 0; k < out->vertex.size(); k += 3)

@@ -44,6 +44,7 @@ struct mrp_hl_solver {
   int32_t nWorkers = 0;    // host worker threads the caller asked for (>= engines.size(): two may share an engine)
   int32_t nPreloaded = 0;  // live mrp_hl_preloaded objects (their maps are released with the last one)
   int32_t pathSlots = 0;   // slots of the engines' device path stores (0: not allocated)
+  int32_t consSlots = 0, consWords = 0;  // the engines' device constraint stores (MRP_HL_DEVICE_CONSTRAINTS; 0: not allocated)
 };
 
 namespace {
@@ -417,6 +418,28 @@ int mrp_hl_solver_solve_stream(mrp_hl_solver* s, const mrp_hl_options* optIn, in
       s->pathSlots = pathSlots;
     }
   }
+  // MRP_HL_DEVICE_CONSTRAINTS=1 (session mode, CBS and ECBS): the engines' device-resident constraint stores.  A live
+  // conflict-tree node holds one set slot per constraint it added, as it holds one path slot per path it replaced, so the
+  // store has as many slots as the path store would; a set of more than MRP_HL_CONS_WORDS constraints (default 64: 256
+  // bytes a slot, 64 MiB to 1 GiB per engine) ships flat.  Engines without the calls (weak references) leave the switch off.
+  int32_t consSlots = 0, consWords = 0;
+  if (opt.mode != 1 && std::getenv("MRP_HL_DEVICE_CONSTRAINTS") && std::atoi(std::getenv("MRP_HL_DEVICE_CONSTRAINTS")) != 0 &&
+      engineHasConstraintStore()) {
+    consSlots = std::max(1 << 18, std::min(1 << 22, (1 << 22) / std::max(nThreads, 1)));
+    consWords = 64;
+    if (const char* e = std::getenv("MRP_HL_CONS_SLOTS")) consSlots = std::max(0, std::atoi(e));
+    if (const char* e = std::getenv("MRP_HL_CONS_WORDS")) consWords = std::max(1, std::min(2048, std::atoi(e)));
+    if (consSlots != s->consSlots || consWords != s->consWords) {
+      for (int32_t t = 0; t < static_cast<int32_t>(s->engines.size()); ++t)
+        if (reserveConstraintStore(s->engines[t], consSlots, consWords) != MRP_LL_SUCCESS) {
+          for (int32_t u = 0; u <= t; ++u) (void)reserveConstraintStore(s->engines[u], 0, 0);
+          consSlots = consWords = 0;  // every job ships its set, as with the switch off
+          break;
+        }
+      s->consSlots = consSlots;
+      s->consWords = consWords;
+    }
+  }
   std::atomic<int32_t> nextInstance(0);
   int32_t sessionGate = 0;
   auto t0 = std::chrono::steady_clock::now();
@@ -436,6 +459,8 @@ int mrp_hl_solver_solve_stream(mrp_hl_solver* s, const mrp_hl_options* optIn, in
     plan.workgroups = sessionWgs;
     plan.heavyWgs = heavyPer;
     plan.pathSlots = pathSlots;
+    plan.consSlots = consSlots;
+    plan.consWords = consWords;
     plan.gate = &sessionGate;
     plan.nEngines = nRun;
     plan.nWorkers = nWork;

@@ -54,6 +54,9 @@ struct DevJob {            // 112 bytes, 16-byte aligned
   uint32_t reserved;
   uint32_t heur_off;       // MRP_LL_ASTAR_EPS_TA: word offset of the goal's heuristic table in the maps buffer (path_off is
                            // taken by its focal path table; MRP_LL_ASTAR_TA keeps the table's offset in path_off)
+  // ---- device-resident constraint store (mrp_ll_submit_sets; LaunchParams::cons_store) ----
+  // pad_[0] = base slot + 1 (0: none), pad_[1] = the base's vertex words | its edge words << 16, pad_[2] = result slot + 1
+  // (0: none).  n_vc / n_ec above count the UNION; cons[vc_off] holds only the job's additions, vertex words then edge words.
   uint32_t pad_[3];
 };
 constexpr uint32_t kNoStoreSlot = 0xFFFFFFFFu;
@@ -168,6 +171,10 @@ struct LaunchParams {
   uint16_t* path_store;       // device (uncached allocation: written by one workgroup, read by others of a resident kernel)
   uint32_t path_store_stride; // halfwords per slot (0 = no store)
   uint32_t path_store_slots;
+  // ---- device-resident constraint store: slot = [vertex words][edge words], the counts travel in the job (DevJob::pad_) ----
+  uint32_t* cons_store;       // device (allocated like the path store)
+  uint32_t cons_store_stride; // words per slot (<= kConsLocalWords; 0 = no store)
+  uint32_t cons_store_slots;
   // ---- heavy workgroups (A*-epsilon sessions): a second resident launch with the WIDE window (ll_compact.h) that takes
   // over the searches the front workgroups' compact tier cannot hold.  Device-side queue, device memory:
   //   heavy_ctr[0] = entries written so far (front workgroups: fetch-add), heavy_ctr[16] = tickets taken (heavy workgroups),

@@ -52,6 +52,56 @@ DEVI void stageConstraints(const uint32_t* consHost, uint32_t vcOff, uint32_t nV
   ec = vc + nVc;
 }
 
+// The same for a job that names its set in the device-resident constraint store (DevJob::pad_, mrp_ll_submit_sets): the union
+// is put together in the copy area in the order  base vertex words, added vertex words, base edge words, added edge words
+// — ec == vc + nVc as above —, base words from the store, added words from host memory, and, with a result slot, written
+// out to it before the search starts (a front workgroup and the heavy workgroup it hands the search to both do, with the
+// same words).  Store accesses follow the path store's discipline (storeLoad): agent-scope loads and stores, complete
+// before the job's completion is published (publishDone waits for vmcnt), no cache-wide fence.
+// A word read from the store is checked against the job's map before anybody indexes with it (buildRows / ensureRows use
+// the vertex words unguarded): one that does not fit becomes 0xFFFFFFFF, which no tier matches or indexes with.
+// A function of its own, called by processJob before anything of the search is live: the resident kernels' register
+// allocation is the searches', not this loop's.
+// Returns false when the descriptor does not fit the store or the copy area (the host packer refuses such a job).
+__device__ __attribute__((noinline)) bool stageConstraintSet(const DevJob* job, const uint32_t* cons, uint32_t* store, uint32_t stride,
+                                                             uint32_t slots, uint32_t* consLocal) {
+  const uint32_t nVc = rfl(job->n_vc), nEc = rfl(job->n_ec), dimx = rfl(job->dimx), dimy = rfl(job->dimy);
+  const uint32_t baseP1 = rfl(job->pad_[0]), baseCounts = rfl(job->pad_[1]), resP1 = rfl(job->pad_[2]);
+  const uint32_t* added = cons + rfl(job->vc_off);
+  stride = rfl(stride); slots = rfl(slots);
+  const uint32_t bVc = baseP1 ? (baseCounts & 0xFFFFu) : 0u, bEc = baseP1 ? (baseCounts >> 16) : 0u;
+  const uint32_t nWords = nVc + nEc;
+  if (store == nullptr || baseP1 > slots || resP1 > slots || bVc > nVc || bEc > nEc || nVc > kConsLocalWords ||
+      nEc > kConsLocalWords || nWords > kConsLocalWords || nWords > stride)
+    return false;
+  const uint32_t aVc = nVc - bVc;
+  const uint32_t cells = dimx * dimy;
+  const uint32_t* base = store + (size_t)(baseP1 ? baseP1 - 1u : 0u) * stride;
+  uint32_t* out = store + (size_t)(resP1 ? resP1 - 1u : 0u) * stride;
+  for (uint32_t i = threadIdx.x; i < nWords; i += 64) {
+    uint32_t w;
+    if (i < nVc) {
+      if (i < bVc) {
+        w = __hip_atomic_load(base + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // t << 16 | y << 8 | x
+        if ((w & 0xFFu) >= dimx || ((w >> 8) & 0xFFu) >= dimy) w = 0xFFFFFFFFu;
+      } else {
+        w = hostLoad32(added + (i - bVc));
+      }
+    } else {
+      const uint32_t k = i - nVc;
+      if (k < bEc) {
+        w = __hip_atomic_load(base + bVc + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // t << 19 | cell << 3 | k
+        if (((w >> 3) & 0xFFFFu) >= cells) w = 0xFFFFFFFFu;
+      } else {
+        w = hostLoad32(added + aVc + (k - bEc));
+      }
+    }
+    consLocal[i] = w;
+    if (resP1) __hip_atomic_store(out + i, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  return true;
+}
+
 // What a search's Ctx takes from the job descriptor; vc / ec (stageConstraints) and the path table are the caller's.
 // UNI: the descriptor is read through a pointer the compiler cannot prove wave-uniform (runJobTaEps's argument).
 template <bool UNI = false>
@@ -127,6 +177,11 @@ DEVI bool idTableInLds(const LaunchParams& P, uint32_t pathBytes) {
 }
 
 // Returns true when the job has to be handed to the heavy workgroups (kTiersFront only).
+// A front workgroup hands these searches over without looking at them (runJob's first test, kTiersFront).
+DEVI bool frontHandsOver(const LaunchParams& P, const DevJob& J) {
+  return (J.ctx_flags & kCtxHeavy) != 0 || P.lds_nodes == 0 || J.dimx > 32u || J.dimy > 32u || J.n_agents_pad > 128u || J.n_ec > 64u;
+}
+
 template <bool EPS, bool BG, int TIERS>
 DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t* arenaSlot, DevResult& res,
                  uint16_t* outPath) {
@@ -136,7 +191,7 @@ DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t*
   const bool heavyHint = (J.ctx_flags & kCtxHeavy) != 0;
   if (TIERS == kTiersFront) {
     // not a search of the narrow tier (the caller says so, or the job's shape does): nothing to set up here
-    if (heavyHint || P.lds_nodes == 0 || J.dimx > 32u || J.dimy > 32u || J.n_agents_pad > 128u || J.n_ec > 64u) return true;
+    if (frontHandsOver(P, J)) return true;
   }
   Ctx c;
   fillCtx(c, J, P.maps, P.debug);
@@ -145,7 +200,12 @@ DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t*
   uint8_t* scratch = arenaSlot + P.arena_scratch_off;
   uint32_t* consLocal = (uint32_t*)(scratch + (size_t)P.out_stride * 2);
   uint8_t* pathsArena = (uint8_t*)(consLocal + kConsLocalWords);
-  stageConstraints(P.cons, J.vc_off, c.nVc, c.nEc, consLocal, c.vc, c.ec);
+  if ((J.pad_[0] | J.pad_[2]) != 0u) {  // the union is in the copy area already (processJob, stageConstraintSet)
+    c.vc = consLocal;
+    c.ec = consLocal + c.nVc;
+  } else {
+    stageConstraints(P.cons, J.vc_off, c.nVc, c.nEc, consLocal, c.vc, c.ec);
+  }
   {
     const uint32_t pathBytes = c.tPad * c.nAgentsPad * 2;  // multiple of 32
     const uint32_t* psrc = (const uint32_t*)(P.paths + J.path_off);

@@ -116,8 +116,17 @@ DEVI bool processJob(const LaunchParams& P, const DevJob* jobSrc, DevResult* res
   const uint64_t tj0 = __builtin_amdgcn_s_memrealtime();
 #endif
   uint16_t* outPath = (uint16_t*)(arenaSlot + P.arena_scratch_off);  // device scratch; copied out below
-  const uint32_t algo = rfl(J.algo);
+  uint32_t algo = rfl(J.algo);
   bool handOver = false;
+  // A job that names its constraint set in the device store (ll_device.h DevJob::pad_): the union goes into the arena slot's
+  // copy area — and into the result slot — here, in front of runJob; a descriptor that does not fit stays ST_BAD.  (Not in a
+  // front workgroup that hands the search over unseen: the heavy workgroup that runs it stages, and writes the result slot.)
+  if ((rfl(J.pad_[0]) | rfl(J.pad_[2])) != 0u && !(TIERS == kTiersFront && frontHandsOver(P, J))) {
+    uint32_t* consLocal = (uint32_t*)(arenaSlot + P.arena_scratch_off + (size_t)P.out_stride * 2);
+    if (algo > 1u || (rfl(J.ctx_flags) & kCtxChain) ||
+        !stageConstraintSet(&jobS, P.cons, P.cons_store, P.cons_store_stride, P.cons_store_slots, consLocal))
+      algo = 0xFFFFFFFFu;  // no search below takes it
+  }
   if constexpr (KIND == 0) {
     if (algo == 1)
       runJob<true, false, kTiersAll>(P, J, smem, arenaSlot, res, outPath);
@@ -135,7 +144,7 @@ DEVI bool processJob(const LaunchParams& P, const DevJob* jobSrc, DevResult* res
       res.tier = rfl(resS.tier);
       res.prof[2] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - th0);
       res.prof[3] = (uint32_t)res.expanded;
-    } else
+    } else if (algo == 0)
       runJob<false, false, kTiersAll>(P, J, smem, arenaSlot, res, outPath);
   } else if constexpr (KIND == 1) {  // the A*-epsilon-only kernels: the small window (mrp_ll_lds_bytes(kind = 1))
     if (algo == 1) {

@@ -152,6 +152,8 @@ struct Ticket {
   int kind = 0;                   // A* batches: 0 = mixed, 1 = all A*-epsilon, 2 = all A*
   std::vector<int32_t> jobDimx;   // SIPP: grid width per job (cell -> x, y when unpacking)
   std::vector<int32_t> jobInit;   // per job: initial_cost (A*) / start_time (SIPP), applied when unpacking
+  std::vector<int32_t> setSlot;   // per job: the constraint-store slot it writes (-1: none) and the mirror's sequence number
+  std::vector<uint32_t> setSeq;   //          of that write (setCollected)
 };
 
 // ---- session mode: job ring in coherent pinned host memory --------------------------------------------------
@@ -227,12 +229,24 @@ struct Ring {
   std::vector<uint8_t> slotSippFlags;         //       bit 0: it runs on the device-resident copy, bit 1: sipp_commit
   std::vector<int32_t> slotInit;   // initial_cost (A*) / start_time (SIPP) of the slot's job
   std::vector<int32_t> slotChain;  // MRP_LL_JOB_ROOT_CHAIN: results the slot's job fills (n_agents - agent_idx), else 0
+  std::vector<int32_t> slotSet;    // the constraint-store slot the job slot's occupant writes (-1: none) ...
+  std::vector<uint32_t> slotSetSeq;  // ... and the mirror's sequence number of that write (setCollected)
 };
 // The host's stores into the push block are write-combined when it is device memory: everything written so far leaves
 // the core's buffers, in order, before whatever is stored next (x86 SFENCE; a no-op price for pinned host memory).
 static inline void pushFence(const Ring& g) {
   if (g.pushInDevice) __builtin_ia32_sfence();
 }
+// Host mirror of one slot of the device-resident constraint store (mrp_ll_constraint_store_reserve): what the packer needs
+// of a set without reading device memory.  Updated when a job that writes the slot is accepted, under the submit lock.
+struct ConsSetRec {
+  uint32_t nVc = 0, nEc = 0;   // packed vertex / edge words in the slot
+  int32_t lastGoal = -1;       // m_lastGoalConstraint of the set (ecbs.cpp:268-273)
+  int32_t mapId = -1, gx = 0, gy = 0;  // the map and the goal cell it was built for
+  bool written = false;        // some accepted job has this slot as its result
+  bool inFlight = false;       // ... and that job's result has not been collected yet
+  uint32_t seq = 0;            // which write (a recycled slot's earlier writer must not clear inFlight)
+};
 struct SessTicket {
   bool used = false;
   int32_t lane = 0;
@@ -292,6 +306,15 @@ struct mrp_ll_ctx {
   int32_t sippTabsPerChunk = 64;
   uint16_t* pathStore = nullptr;   // device-resident path store (mrp_ll_path_store_reserve)
   uint32_t pathStoreStride = 0, pathStoreSlots = 0;
+  // device-resident constraint store (mrp_ll_constraint_store_reserve) and its host mirror
+  uint32_t* consStore = nullptr;
+  uint32_t consStoreStride = 0, consStoreSlots = 0;
+  std::vector<ConsSetRec> consSets;
+  uint32_t consSetSeq = 0;
+  const mrp_ll_constraint_ref* setsIn = nullptr;   // inside mrp_ll_submit_sets: its `sets` array, and the entry of the job being
+  const mrp_ll_constraint_ref* curRef = nullptr;   // packed (what admits MRP_LL_JOB_CONSTRAINT_SET jobs: null in every other call)
+  int32_t pendingSet = -1;                         // packJob: the slot the job just packed writes (-1: none) and what the
+  ConsSetRec pendingRec;                           // mirror holds for it once the job has been accepted (commitSet)
   uint8_t* scanDev = nullptr;      // mrp_ll_conflict_scan: device staging (grown on demand)
   size_t scanDevCap = 0;
   hipStream_t scanStream = nullptr;  // ... and its own stream: a session's resident kernel occupies tickets[0].stream
@@ -800,6 +823,24 @@ bool packJob(mrp_ll_ctx* ctx, const mrp_ll_job& j, ConsSink& cs, PathSink& ps, D
   if (epsTa && (j.initial_cost != 0 || (j.flags & (MRP_LL_JOB_ROOT_CHAIN | MRP_LL_JOB_HEAVY | MRP_LL_JOB_STORE_RESULT)) || j.path_ids))
     return false;
   if (j.initial_cost < 0 || j.initial_cost >= 0x40000000) return false;  // (bit 30 of the per-job word marks MRP_LL_ASTAR_TA, jobInitOf)
+  // The agent's set by its slot in the constraint store (mrp_ll.h mrp_ll_submit_sets): the arrays are the additions.
+  ctx->pendingSet = -1;
+  const bool bySet = (j.flags & MRP_LL_JOB_CONSTRAINT_SET) != 0;
+  const ConsSetRec* baseSet = nullptr;
+  if (bySet) {
+    const mrp_ll_constraint_ref* ref = ctx->curRef;
+    if (!ref || !ctx->consStore || (j.algo != MRP_LL_ASTAR && j.algo != MRP_LL_ASTAR_EPS) || (j.flags & MRP_LL_JOB_ROOT_CHAIN))
+      return false;
+    const int32_t nSets = static_cast<int32_t>(ctx->consStoreSlots);
+    if (ref->base_set_id < -1 || ref->base_set_id >= nSets || ref->result_set_id < -1 || ref->result_set_id >= nSets) return false;
+    // (a search that a front workgroup hands to a heavy one stages twice and must find the same base both times)
+    if (ref->base_set_id >= 0 && ref->base_set_id == ref->result_set_id) return false;
+    if (ref->base_set_id >= 0) {
+      baseSet = &ctx->consSets[ref->base_set_id];
+      if (!baseSet->written || baseSet->inFlight || baseSet->mapId != j.map_id || baseSet->gx != j.goal_x || baseSet->gy != j.goal_y)
+        return false;
+    }
+  }
   const bool scan = (j.flags & MRP_LL_JOB_SCAN_CONFLICTS) != 0;
   if (scan) {
     // the conflicts of the node come back through mrp_ll_submit_scan's array alone, and the workgroup scans what it holds:
@@ -910,6 +951,26 @@ bool packJob(mrp_ll_ctx* ctx, const mrp_ll_job& j, ConsSink& cs, PathSink& ps, D
   }
   d.n_ec = static_cast<uint32_t>(cs.size()) - d.ec_off;
   if (cs.failed) return false;
+  if (bySet) {
+    // n_vc / n_ec become the UNION's counts (the tier choices keep working), the last goal constraint the larger of the
+    // base's and the additions'; base slot, base counts and result slot travel in pad_ (ll_device.h)
+    const mrp_ll_constraint_ref& ref = *ctx->curRef;
+    const uint32_t bVc = baseSet ? baseSet->nVc : 0u, bEc = baseSet ? baseSet->nEc : 0u;
+    if (static_cast<uint64_t>(bVc) + bEc + d.n_vc + d.n_ec > ctx->consStoreStride) return false;
+    d.n_vc += bVc;
+    d.n_ec += bEc;
+    if (baseSet) d.last_goal_constraint = std::max(d.last_goal_constraint, baseSet->lastGoal);
+    d.pad_[0] = baseSet ? static_cast<uint32_t>(ref.base_set_id) + 1u : 0u;
+    d.pad_[1] = bVc | (bEc << 16);
+    d.pad_[2] = ref.result_set_id >= 0 ? static_cast<uint32_t>(ref.result_set_id) + 1u : 0u;
+    if (ref.result_set_id >= 0) {
+      ConsSetRec& r = ctx->pendingRec;
+      r.nVc = d.n_vc; r.nEc = d.n_ec;
+      r.lastGoal = d.last_goal_constraint;
+      r.mapId = j.map_id; r.gx = j.goal_x; r.gy = j.goal_y;
+      ctx->pendingSet = ref.result_set_id;  // (the job may still be rejected below: the caller commits, commitSet)
+    }
+  }
   if (j.algo == MRP_LL_ASTAR_TA) {
     d.n_agents_pad = 0;
     d.t_pad = 0;
@@ -992,6 +1053,29 @@ bool packJob(mrp_ll_ctx* ctx, const mrp_ll_job& j, ConsSink& cs, PathSink& ps, D
     d.reserved = static_cast<uint32_t>(j.agent_idx);
   }
   return true;
+}
+
+// The job packed last has been accepted (ok) or not: only an accepted one creates its result set in the mirror.  slot /
+// seq: what the collection of its result hands to setCollected.
+void commitSet(mrp_ll_ctx* ctx, bool ok, int32_t& slot, uint32_t& seq) {
+  slot = -1;
+  seq = 0;
+  if (ok && ctx->pendingSet >= 0) {
+    ConsSetRec& r = ctx->consSets[ctx->pendingSet];
+    r = ctx->pendingRec;
+    r.written = true;
+    r.inFlight = true;
+    r.seq = ++ctx->consSetSeq;
+    slot = ctx->pendingSet;
+    seq = r.seq;
+  }
+  ctx->pendingSet = -1;
+}
+// The result of the job that wrote `slot` has been collected: later jobs may name the set as their base.
+void setCollected(mrp_ll_ctx* ctx, int32_t slot, uint32_t seq) {
+  if (slot < 0 || slot >= static_cast<int32_t>(ctx->consSets.size())) return;
+  ConsSetRec& r = ctx->consSets[slot];
+  if (r.seq == seq) r.inFlight = false;
 }
 
 // The conflicts of a flagged job (ll_device.h kCtxScan: ten words at the end of the job's output area) -> the caller's
@@ -1083,6 +1167,9 @@ int fillCommonParams(mrp_ll_ctx* ctx, Ticket& t, mrp::LaunchParams& P, uint32_t&
   P.path_store = ctx->pathStore;
   P.path_store_stride = ctx->pathStoreStride;
   P.path_store_slots = ctx->pathStore ? ctx->pathStoreSlots : 0;
+  P.cons_store = ctx->consStore;
+  P.cons_store_stride = ctx->consStore ? ctx->consStoreStride : 0;
+  P.cons_store_slots = ctx->consStore ? ctx->consStoreSlots : 0;
   P.lds_nodes = ldsNodes;
   P.lds_rows = rows;
   P.lds_row_words = rowWords;
@@ -1318,6 +1405,7 @@ void mrp_ll_destroy(mrp_ll_ctx* ctx) {
   if (ctx->heurEv1) (void)hipEventDestroy(ctx->heurEv1);
   if (ctx->scanStream) (void)hipStreamDestroy(ctx->scanStream);
   if (ctx->pathStore) (void)hipFree(ctx->pathStore);
+  if (ctx->consStore) (void)hipFree(ctx->consStore);
   for (uint8_t* c : ctx->sippTabChunks) (void)hipFree(c);
   delete ctx;
 }
@@ -1739,6 +1827,8 @@ static int sessionBegin(mrp_ll_ctx* ctx, int32_t workgroups, bool sipp, int kind
   }
   g.slotInit.assign(R, 0);
   g.slotChain.assign(R, 0);
+  g.slotSet.assign(R, -1);
+  g.slotSetSeq.assign(R, 0);
   ctx->sess.clear();
   ctx->sessFree.clear();
   for (int q = 0; q < mrp_ll_ctx::kMaxTags; ++q) {
@@ -1967,6 +2057,9 @@ int mrp_ll_session_end(mrp_ll_ctx* ctx) {
       tb->devFresh = true;  // (a sipp_commit job that was abandoned leaves no trace: its result never reached the caller)
       tb = nullptr;
     }
+  // a constraint set whose writer was abandoned: nobody will collect it, and what its slot holds is unknown
+  for (ConsSetRec& r : ctx->consSets)
+    if (r.inFlight) r = ConsSetRec();
   // the device counter is past the published tickets: the next batch-mode launch starts from a clean base
   Ticket& t = ctx->tickets[0];
   HIPCHK(ctx, hipMemset(t.queueHead, 0, 256));
@@ -2059,6 +2152,7 @@ static int sessionSubmit(mrp_ll_ctx* ctx, int32_t lane, int32_t nJobs, const mrp
         g.slotSippFlags[slot] = static_cast<uint8_t>(fl);
       }
     } else {
+      ctx->curRef = ctx->setsIn ? ctx->setsIn + i : nullptr;
       ok = jobs[i].algo != MRP_LL_SIPP &&
            (g.kind == 0 || (g.kind == 1 ? jobs[i].algo == MRP_LL_ASTAR_EPS
                                         : (jobs[i].algo == MRP_LL_ASTAR || jobs[i].algo == MRP_LL_ASTAR_TA))) &&
@@ -2068,6 +2162,7 @@ static int sessionSubmit(mrp_ll_ctx* ctx, int32_t lane, int32_t nJobs, const mrp
       trivialRejectedJob(ctx, d);
       st.state[i] = 2;
     }
+    commitSet(ctx, ok && !g.sipp, g.slotSet[slot], g.slotSetSeq[slot]);
     st.scanJob[i] = (!g.sipp && (jobs[i].flags & MRP_LL_JOB_SCAN_CONFLICTS) && st.conf) ? 1 : 0;
     g.jobs[slot] = d;
     ctx->stats.staged_bytes += static_cast<int64_t>(sizeof(DevJob)) + 4 * static_cast<int64_t>(g.sipp ? sippWords : cs.used) +
@@ -2125,6 +2220,8 @@ int mrp_ll_poll(mrp_ll_ctx* ctx, int32_t ticket, int32_t* doneOut) {
                    st.res[i], g.sipp, g.sipp ? g.slotDimx[slot] : 0, g.slotInit[slot]);
     if (st.scanJob[i])
       unpackConflicts(g.results[slot], g.outPaths + static_cast<size_t>(slot) * g.outStride, g.outStride, st.state[i] == 2, st.conf[i]);
+    setCollected(ctx, g.slotSet[slot], g.slotSetSeq[slot]);
+    g.slotSet[slot] = -1;
     if (g.sipp && g.slotTable[slot]) {
       finishSippTableJob(g.slotTable[slot], g.slotSippFlags[slot], g.results[slot],
                          g.outPaths + static_cast<size_t>(slot) * g.outStride);
@@ -2171,6 +2268,8 @@ static int32_t drainCompletions(mrp_ll_ctx* ctx, int32_t tag, int32_t* tickets, 
                    st.res[i], g.sipp, g.sipp ? g.slotDimx[slot] : 0, g.slotInit[slot]);
     if (st.scanJob[i])
       unpackConflicts(g.results[slot], g.outPaths + static_cast<size_t>(slot) * g.outStride, g.outStride, st.state[i] == 2, st.conf[i]);
+    setCollected(ctx, g.slotSet[slot], g.slotSetSeq[slot]);
+    g.slotSet[slot] = -1;
     if (g.sipp && g.slotTable[slot]) {
       finishSippTableJob(g.slotTable[slot], g.slotSippFlags[slot], g.results[slot],
                          g.outPaths + static_cast<size_t>(slot) * g.outStride);
@@ -2236,6 +2335,29 @@ int mrp_ll_submit_scan(mrp_ll_ctx* ctx, int32_t tag, int32_t nJobs, const mrp_ll
   ctx->scanOut = conflicts;
   const int rc = sessionSubmit(ctx, 0, nJobs, jobs, results, ticketOut);
   ctx->scanOut = nullptr;
+  if (rc == MRP_LL_SUCCESS) ctx->sess[*ticketOut].tag = tag;
+  return rc;
+}
+
+int mrp_ll_submit_sets(mrp_ll_ctx* ctx, int32_t tag, int32_t nJobs, const mrp_ll_job* jobs, mrp_ll_result* results,
+                       mrp_ll_conflict* conflicts, const mrp_ll_constraint_ref* sets, int32_t* ticketOut) {
+  if (!ctx || !ticketOut || nJobs < 0 || (nJobs > 0 && (!jobs || !results))) return MRP_LL_E_INVALID;
+  if (!ctx->ring.active) {  // batch mode: mrp_ll_submit; the tag names nobody
+    ctx->scanOut = conflicts;
+    ctx->setsIn = sets;
+    const int rc = mrp_ll_submit(ctx, nJobs, jobs, results, ticketOut);
+    ctx->scanOut = nullptr;
+    ctx->setsIn = ctx->curRef = nullptr;
+    return rc;
+  }
+  if (tag < 0 || tag >= mrp_ll_ctx::kMaxTags) return MRP_LL_E_INVALID;
+  std::lock_guard<std::mutex> lock(ctx->coMu);
+  if (!ctx->ring.active) return MRP_LL_E_INVALID;
+  ctx->scanOut = conflicts;
+  ctx->setsIn = sets;
+  const int rc = sessionSubmit(ctx, 0, nJobs, jobs, results, ticketOut);
+  ctx->scanOut = nullptr;
+  ctx->setsIn = ctx->curRef = nullptr;
   if (rc == MRP_LL_SUCCESS) ctx->sess[*ticketOut].tag = tag;
   return rc;
 }
@@ -2340,7 +2462,13 @@ int mrp_ll_submit(mrp_ll_ctx* ctx, int32_t nJobs, const mrp_ll_job* jobs, mrp_ll
     size_t c0 = t.cons.size, p0 = t.paths.size;
     ConsSinkBuf cs{t.cons};
     PathSinkBuf ps{t.paths};
+    ctx->curRef = ctx->setsIn ? ctx->setsIn + i : nullptr;
     bool ok = packJob(ctx, jobs[i], cs, ps, t.jobs.host[i]);
+    if (static_cast<int>(t.setSlot.size()) < nJobs) {
+      t.setSlot.resize(nJobs);
+      t.setSeq.resize(nJobs);
+    }
+    commitSet(ctx, ok && !cs.failed && !ps.failed, t.setSlot[i], t.setSeq[i]);
     t.scanJob[i] = (!t.sipp && (jobs[i].flags & MRP_LL_JOB_SCAN_CONFLICTS) && t.userConflicts) ? 1 : 0;
     if (t.sipp) {
       if (static_cast<int>(t.jobDimx.size()) < nJobs) t.jobDimx.resize(nJobs);
@@ -2363,6 +2491,8 @@ int mrp_ll_submit(mrp_ll_ctx* ctx, int32_t nJobs, const mrp_ll_job* jobs, mrp_ll
     }
   }
   if (t.allocFailed) {
+    for (int i = 0; i < nJobs; ++i)  // nothing of this call runs: the sets it would have written do not exist
+      if (t.setSlot[i] >= 0 && ctx->consSets[t.setSlot[i]].seq == t.setSeq[i]) ctx->consSets[t.setSlot[i]] = ConsSetRec();
     ctx->err = "mrp_ll_submit: pinned staging allocation failed";
     return MRP_LL_E_NOMEM;
   }
@@ -2447,6 +2577,7 @@ int mrp_ll_wait(mrp_ll_ctx* ctx, int32_t ticket) {
     if (t.scanJob[i])
       unpackConflicts(t.results.host[i], t.outPaths.host + static_cast<size_t>(i) * outStride, outStride, t.rejected[i] != 0,
                       t.userConflicts[i]);
+    setCollected(ctx, t.setSlot[i], t.setSeq[i]);
     if (t.sipp && t.commitTab[i])  // batch mode never uses the device-resident copies: the host adds the stays
       finishSippTableJob(t.commitTab[i], 2u, t.results.host[i], t.outPaths.host + static_cast<size_t>(i) * outStride);
   }
@@ -2490,6 +2621,39 @@ int mrp_ll_path_store_reserve(mrp_ll_ctx* ctx, int32_t nSlots) {
   ctx->pathStore = static_cast<uint16_t*>(p);
   ctx->pathStoreSlots = static_cast<uint32_t>(nSlots);
   HIPCHK(ctx, hipMemset(ctx->pathStore, 0, bytes));
+  return MRP_LL_SUCCESS;
+}
+
+int mrp_ll_constraint_store_reserve(mrp_ll_ctx* ctx, int32_t nSlots, int32_t wordsPerSlot) {
+  if (!ctx || nSlots < 0 || wordsPerSlot < 0 || wordsPerSlot > static_cast<int32_t>(mrp::kConsLocalWords) ||
+      (nSlots > 0 && wordsPerSlot == 0))
+    return MRP_LL_E_INVALID;
+  if (ctx->ring.active) return MRP_LL_E_BUSY;
+  for (const Ticket& t : ctx->tickets)
+    if (t.inFlight) return MRP_LL_E_BUSY;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->consStore) HIPCHK(ctx, hipFree(ctx->consStore));
+  ctx->consStore = nullptr;
+  ctx->consStoreSlots = 0;
+  ctx->consStoreStride = 0;
+  ctx->consSets.clear();
+  if (nSlots == 0) return MRP_LL_SUCCESS;
+  // Allocated as the path store is (mrp_ll_path_store_reserve): ordinary device memory.  A slot is written by one workgroup
+  // and read by others of the same launch with agent-scope stores and loads; the host orders them (a reader's job is
+  // accepted only after the writer's result has been collected).
+  const size_t bytes = static_cast<size_t>(nSlots) * static_cast<size_t>(wordsPerSlot) * sizeof(uint32_t);
+  void* p = nullptr;
+  hipError_t e = std::getenv("MRP_LL_STORE_UNCACHED") ? hipExtMallocWithFlags(&p, bytes, hipDeviceMallocUncached)
+                                                      : hipMalloc(&p, bytes);
+  if (e != hipSuccess) {
+    ctx->err = std::string("mrp_ll_constraint_store_reserve: ") + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? MRP_LL_E_NOMEM : MRP_LL_E_DEVICE;
+  }
+  ctx->consStore = static_cast<uint32_t*>(p);
+  ctx->consStoreSlots = static_cast<uint32_t>(nSlots);
+  ctx->consStoreStride = static_cast<uint32_t>(wordsPerSlot);
+  ctx->consSets.assign(static_cast<size_t>(nSlots), ConsSetRec());
+  HIPCHK(ctx, hipMemset(ctx->consStore, 0xFF, bytes));
   return MRP_LL_SUCCESS;
 }
 
@@ -2636,6 +2800,7 @@ int mrp_ll_release_maps(mrp_ll_ctx* ctx) {
   ctx->heurs.clear();
   ctx->mapWords.clear();
   ctx->mapsBase = 0;  // nothing to copy; the device buffer (and its capacity) is kept for the next uploads
+  ctx->consSets.assign(ctx->consSets.size(), ConsSetRec());  // every constraint set belonged to one of those maps
   return MRP_LL_SUCCESS;
 }
 

@@ -18,6 +18,7 @@ _LIB_PATH = os.environ.get("MRP_LL_LIB") or os.path.join(_PKG, "lib", "libmrp_ll
 ASTAR, ASTAR_EPS, SIPP, ASTAR_TA, ASTAR_EPS_TA = 0, 1, 2, 3, 4
 JOB_STORE_RESULT, JOB_NO_GOAL, JOB_ROOT_CHAIN, JOB_HEAVY = 1, 2, 4, 8  # mrp_ll_job.flags (include/mrp_ll.h)
 JOB_SCAN_CONFLICTS = 16  # mrp_ll_job.flags: mrp_ll_submit_scan also returns the conflicts of the node the job completes
+JOB_CONSTRAINT_SET = 32  # mrp_ll_job.flags: mrp_ll_submit_sets' sets[i] names the agent's set in the device constraint store
 SCAN_UNTOUCHED = -2      # search_batch_scan: what every field of an entry the engine did not write still holds
 OK, NO_SOLUTION, CAP_EXPANSIONS, CAP_NODES, CAP_HORIZON, BAD_JOB, PATH_TRUNCATED, CAP_FOCAL = range(8)
 ACTION_NAMES = ["Up", "Down", "Left", "Right", "Wait"]  # example/ecbs.cpp:49-55
@@ -57,6 +58,10 @@ class mrp_ll_conflict(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int32) for k in ("found", "time", "agent1", "agent2", "type", "x1", "y1", "x2", "y2", "count")]
 
 
+class mrp_ll_constraint_ref(ctypes.Structure):
+    _fields_ = [("base_set_id", ctypes.c_int32), ("result_set_id", ctypes.c_int32)]
+
+
 class mrp_ll_stats(ctypes.Structure):
     _fields_ = [("launches", ctypes.c_int64), ("jobs", ctypes.c_int64), ("expansions", ctypes.c_int64),
                 ("nodes_created", ctypes.c_int64), ("migrated", ctypes.c_int64), ("kernel_ms", ctypes.c_double),
@@ -74,7 +79,8 @@ EXPORTS = ["mrp_ll_create", "mrp_ll_destroy", "mrp_ll_last_error", "mrp_ll_uploa
            "mrp_ll_sipp_table_create", "mrp_ll_sipp_table_add", "mrp_ll_sipp_table_destroy", "mrp_ll_path_store_reserve",
            "mrp_ll_upload_heuristic", "mrp_ll_session_begin_tiers", "mrp_ll_session_tiers_geometry",
            "mrp_ll_session_begin_tiers_gated", "mrp_ll_submit_tagged", "mrp_ll_poll_any_tagged",
-           "mrp_ll_compute_heuristics", "mrp_ll_read_heuristic", "mrp_ll_heuristic_lookup", "mrp_ll_submit_scan"]
+           "mrp_ll_compute_heuristics", "mrp_ll_read_heuristic", "mrp_ll_heuristic_lookup", "mrp_ll_submit_scan",
+           "mrp_ll_constraint_store_reserve", "mrp_ll_submit_sets"]
 
 _lib = None
 
@@ -153,6 +159,12 @@ def load_library(path: Optional[str] = None):
     lib.mrp_ll_submit_scan.restype = ctypes.c_int
     lib.mrp_ll_submit_scan.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(mrp_ll_job),
                                        ctypes.POINTER(mrp_ll_result), ctypes.POINTER(mrp_ll_conflict), I32P]
+    lib.mrp_ll_constraint_store_reserve.restype = ctypes.c_int
+    lib.mrp_ll_constraint_store_reserve.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
+    lib.mrp_ll_submit_sets.restype = ctypes.c_int
+    lib.mrp_ll_submit_sets.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(mrp_ll_job),
+                                       ctypes.POINTER(mrp_ll_result), ctypes.POINTER(mrp_ll_conflict),
+                                       ctypes.POINTER(mrp_ll_constraint_ref), I32P]
     if path is None:
         _lib = lib
     return lib
@@ -180,6 +192,11 @@ class LLJob:
     heuristic_id: int = -1                    # ASTAR_TA / ASTAR_EPS_TA: LowLevelEngine.upload_heuristic of the goal cell
     heavy: bool = False                       # MRP_LL_JOB_HEAVY: the search is known to outgrow the LDS tier (a hint)
     scan_conflicts: bool = False              # MRP_LL_JOB_SCAN_CONFLICTS: the node's conflicts come back too (search_batch_scan)
+    # device constraint store (constraint_store_reserve): the agent's set at the parent node by its slot, and the slot that
+    # receives base + vertex_constraints / edge_constraints (then the ADDITIONS); -1 = none.  Either one makes the job a
+    # MRP_LL_JOB_CONSTRAINT_SET job, and the call that carries it goes through mrp_ll_submit_sets.
+    base_set_id: int = -1
+    result_set_id: int = -1
 
 
 @dataclass
@@ -265,7 +282,8 @@ class LowLevelEngine:
                 cj.sipp_commit = 1 if j.sipp_commit else 0
             cj.result_path_id = j.result_path_id
             cj.flags = (JOB_STORE_RESULT if j.result_path_id >= 0 else 0) | (JOB_NO_GOAL if j.goal is None else 0) | \
-                (JOB_HEAVY if j.heavy else 0) | (JOB_SCAN_CONFLICTS if j.scan_conflicts else 0)
+                (JOB_HEAVY if j.heavy else 0) | (JOB_SCAN_CONFLICTS if j.scan_conflicts else 0) | \
+                (JOB_CONSTRAINT_SET if (j.base_set_id >= 0 or j.result_set_id >= 0) else 0)
             cj.heuristic_id = j.heuristic_id
             if j.path_ids is not None:
                 ids = np.ascontiguousarray(np.asarray(j.path_ids, dtype=np.int32))
@@ -297,9 +315,43 @@ class LowLevelEngine:
     def search_batch(self, jobs: Sequence[LLJob], states_cap: Optional[int] = None) -> List[LLResult]:
         n = len(jobs)
         cap = states_cap or self.max_horizon
+        if any(j.base_set_id >= 0 or j.result_set_id >= 0 for j in jobs):
+            return self.wait_sets(self.submit_sets(jobs, states_cap=cap), want_conflicts=False)[0]
         cjobs, cres, (keep, states, actions, costs) = self._marshal(jobs, cap)
         self._check(self._lib.mrp_ll_search_batch(self._h, n, cjobs, cres), "mrp_ll_search_batch")
         return self._results(n, cap, cres, states, actions, costs)
+
+    def submit_sets(self, jobs: Sequence[LLJob], states_cap: Optional[int] = None, tag: int = 0):
+        """mrp_ll_submit_sets, in a batch or inside any session: returns a handle for wait_sets.  Jobs with base_set_id /
+        result_set_id name their constraint sets in the device store; jobs with scan_conflicts get their conflicts (the
+        conflicts array is NULL when no job asks for them)."""
+        n = len(jobs)
+        cap = states_cap or self.max_horizon
+        cjobs, cres, bufs = self._marshal(jobs, cap)
+        conf = None
+        if any(j.scan_conflicts for j in jobs):
+            conf = (mrp_ll_conflict * max(n, 1))()
+            for c in conf:
+                for k, _ in mrp_ll_conflict._fields_:
+                    setattr(c, k, SCAN_UNTOUCHED)
+        sets = (mrp_ll_constraint_ref * max(n, 1))()
+        for i, j in enumerate(jobs):
+            sets[i].base_set_id, sets[i].result_set_id = j.base_set_id, j.result_set_id
+        ticket = ctypes.c_int32(-1)
+        self._check(self._lib.mrp_ll_submit_sets(self._h, tag, n, cjobs, cres, conf, sets, ctypes.byref(ticket)),
+                    "mrp_ll_submit_sets")
+        return (ticket.value, n, cap, cjobs, cres, conf, sets, bufs)
+
+    def wait_sets(self, handle, want_conflicts: bool = True):
+        """mrp_ll_wait for a submit_sets handle: (results, conflicts) as search_batch_scan returns them (conflicts is None
+        when they are not wanted; every entry is SCAN_UNTOUCHED when no job of the call asked for a scan)."""
+        ticket, n, cap, cjobs, cres, conf, sets, (keep, states, actions, costs) = handle
+        self._check(self._lib.mrp_ll_wait(self._h, ticket), "mrp_ll_wait")
+        res = self._results(n, cap, cres, states, actions, costs)
+        if not want_conflicts:
+            return res, None
+        names = [k for k, _ in mrp_ll_conflict._fields_]
+        return res, [{k: (getattr(conf[i], k) if conf is not None else SCAN_UNTOUCHED) for k in names} for i in range(n)]
 
     def search_batch_scan(self, jobs: Sequence[LLJob], states_cap: Optional[int] = None, tag: int = 0):
         """mrp_ll_submit_scan + mrp_ll_wait, in a batch or inside any session: returns (results, conflicts).  conflicts[i] is
@@ -307,6 +359,8 @@ class LowLevelEngine:
         with a path); every field of a job without the flag keeps SCAN_UNTOUCHED, the value the array was filled with."""
         n = len(jobs)
         cap = states_cap or self.max_horizon
+        if any(j.base_set_id >= 0 or j.result_set_id >= 0 for j in jobs):
+            return self.wait_sets(self.submit_sets(jobs, states_cap=cap, tag=tag))
         cjobs, cres, (keep, states, actions, costs) = self._marshal(jobs, cap)
         conf = (mrp_ll_conflict * max(n, 1))()
         for c in conf:
@@ -410,6 +464,11 @@ class LowLevelEngine:
     def path_store_reserve(self, n_slots: int) -> None:
         """Allocate the device-resident path store (f2): slots 0..n_slots-1 are the caller's to hand out."""
         self._check(self._lib.mrp_ll_path_store_reserve(self._h, n_slots), "mrp_ll_path_store_reserve")
+
+    def constraint_store_reserve(self, n_slots: int, words_per_slot: int) -> None:
+        """Allocate the device-resident constraint store: n_slots sets of up to words_per_slot (<= 2048) packed words."""
+        self._check(self._lib.mrp_ll_constraint_store_reserve(self._h, n_slots, words_per_slot),
+                    "mrp_ll_constraint_store_reserve")
 
     def sipp_table_create(self, map_id: int) -> int:
         h = ctypes.c_void_p()
