@@ -5,7 +5,11 @@ Layout:
   csrc/ll_compact.h       the compact (LDS) tier of the CBS / ECBS searches
   csrc/ll_arena_heap.h, ll_arena_search.h, ll_jobs.h, ll_ta.h, ll_sipp.h
                           the arena tier, job staging / runJob / runChain, task assignment, SIPP (included by ll_kernel.hip)
-  csrc/mrp_ll_host.cpp    C-ABI (include/mrp_ll.h): context, map upload, batch packing, launch, results
+  csrc/ll_launch.h        the one declaration of everything the host launches (kernel parameter records, launchers)
+  csrc/mrp_ll_host.cpp    C-ABI (include/mrp_ll.h), the one host translation unit: create / destroy, tiers, statistics
+  csrc/host/              its subjects as headers: ll_pack.h + ll_sipp_table.h + ll_unpack.h (HIP-free packer / unpacker),
+                          ll_ctx.h (context, job record, collection), ll_maps.h, ll_heur_host.h, ll_stores.h, ll_batch.h,
+                          ll_session.h, ll_session_jobs.h, ll_submit.h
   csrc/hl/                host-side C++ conflict-tree drivers (CBS, ECBS) that call the C-ABI (include/mrp_hl.h)
   ll.py / hl.py           ctypes plumbing used by tests and bench.py
 

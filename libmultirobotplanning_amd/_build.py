@@ -21,7 +21,9 @@ TARGETS = {
     "libmrp_ll.so": dict(srcs=["ll_kernel.hip", "conflict_kernel.hip", "heur_kernel.hip", "mrp_ll_host.cpp"],
                          deps=["ll_device.h", "ll_compact.h", "ll_arena_heap.h", "ll_arena_search.h", "ll_jobs.h", "ll_ta.h",
                                "ll_sipp.h", "ll_node_scan.h", "wave_dev.h", "wave_dev_bool.h", "heur_bfs.h", "heur_layout.h",
-                               "../../include/mrp_ll.h"],
+                               "ll_launch.h", "host/ll_pack.h", "host/ll_sipp_table.h", "host/ll_unpack.h", "host/ll_ctx.h",
+                               "host/ll_maps.h", "host/ll_heur_host.h", "host/ll_stores.h", "host/ll_batch.h",
+                               "host/ll_session.h", "host/ll_session_jobs.h", "host/ll_submit.h", "../../include/mrp_ll.h"],
                          extra=[]),
     "libmrp_hl.so": dict(srcs=["hl/mrp_hl.cpp"], deps=["hl/exact_heap.hpp", "hl/grid_mapf.hpp", "hl/ct_solver.hpp",
                                                        "hl/ct_session.hpp", "hl/grid2d_astar.hpp", "hl/instance_io.hpp",

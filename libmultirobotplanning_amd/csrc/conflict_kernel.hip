@@ -16,19 +16,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ll_launch.h"  // ConflictOut, ConflictParams, mrp_ll_launch_conflict
+
 namespace mrp {
-
-struct ConflictOut {  // mirrors mrp_ll_conflict of include/mrp_ll.h (10 x int32)
-  int32_t found, time, agent1, agent2, type, x1, y1, x2, y2, count;
-};
-
-struct ConflictParams {
-  const uint32_t* setFirstAgent;   // [nSets + 1]
-  const uint32_t* pathFirstState;  // [totalAgents + 1]
-  const uint16_t* states;          // [totalStates]  x | y << 8
-  ConflictOut* out;                // [nSets]
-  uint32_t nSets;
-};
 
 __device__ __forceinline__ uint32_t posAt(const uint16_t* st, uint32_t first, uint32_t len, uint32_t t) {
   return st[first + (t < len ? t : len - 1)];

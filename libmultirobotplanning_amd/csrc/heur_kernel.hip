@@ -5,20 +5,9 @@
 
 #include "wave_dev.h"
 #include "heur_bfs.h"
+#include "ll_launch.h"  // HeurParams, LookupParams, the launchers' prototypes
 
 namespace mrp {
-
-struct HeurParams {
-  uint32_t* maps;           // the maps buffer: bitmaps are read, tables written
-  const hb::HeurJob* jobs;  // [n]
-  uint32_t n;
-};
-struct LookupParams {
-  const uint32_t* maps;
-  const hb::LookupJob* jobs;  // [n]
-  int32_t* out;               // [n]: the entry, INT32_MAX where the table says 0xFFFF
-  uint32_t n;
-};
 
 // No static LDS: the dynamic window starts at LDS address 0 (wave_dev.h windowBase).  Its size is the largest
 // hb::ldsBytes of the launch's tables.

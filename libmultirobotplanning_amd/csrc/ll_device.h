@@ -1,4 +1,4 @@
-// Device-side job/result records shared by the HIP kernels (ll_kernel.hip and its ll_*.h) and the host packer (mrp_ll_host.cpp).
+// Device-side job/result records shared by the HIP kernels (ll_kernel.hip and its ll_*.h) and the host packer (host/ll_pack.h).
 #pragma once
 #include <stdint.h>
 

@@ -37,7 +37,7 @@ DEVI void hostStore32(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOM
 // ---- job staging shared by the searches (runJob, runChain, runJobTA, runJobTaEps, runSipp) -----------------------------
 // The job's constraint words leave host memory in one coalesced pass into the arena's copy area; a list of more than
 // kConsLocalWords words is read where the host put it, with plain loads behind one acquire fence.  The vertex words and
-// the edge words are ONE run: the host packer pushes them back to back, ec_off == vc_off + n_vc (mrp_ll_host.cpp packJob).
+// the edge words are ONE run: the host packer pushes them back to back, ec_off == vc_off + n_vc (host/ll_pack.h packJob).
 DEVI void stageConstraints(const uint32_t* consHost, uint32_t vcOff, uint32_t nVc, uint32_t nEc, uint32_t* consLocal,
                            const uint32_t*& vc, const uint32_t*& ec) {
   const uint32_t* src = consHost + vcOff;

@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "ll_device.h"
+#include "ll_launch.h"
 #include "wave_dev.h"
 #include "ll_compact.h"
 
@@ -588,7 +589,7 @@ static int occupancyOf(const KernelRef& k, uint32_t ldsBytes) {
 
 }  // namespace mrp
 
-// ---- host-callable launchers (used by mrp_ll_host.cpp) -----------------------------------------------------------
+// ---- host-callable launchers (declared in ll_launch.h) -----------------------------------------------------------
 extern "C" uint32_t mrp_ll_lds_bytes(int kind, uint32_t capNodes, uint32_t rows, uint32_t rowWords, uint32_t pathBytes) {
   (void)rows; (void)rowWords;
   // without the compact tier a workgroup still stages its job descriptor and result through the window's control block

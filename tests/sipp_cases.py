@@ -17,7 +17,7 @@ classify() adds ref (oracle.sipp_single_counted: the reference's answer and its 
 intervals on them), travels, cls, expect, tier and why.  Every class follows from the reference's counters alone; the
 limits are the ones include/mrp_ll.h states for MRP_LL_SIPP (csrc/ll_sipp.h is where they are enforced):
 
-  start time  t0 > G_MAX                                                        -> BAD_JOB      (packSipp*, mrp_ll_host.cpp)
+  start time  t0 > G_MAX                                                        -> BAD_JOB      (packSipp*, host/ll_pack.h)
   table       a travelling table with 4 * ((cells + 1) / 2 + K + 1 + 2 * S) > TABLE_BYTES or
               cells + S > max_horizon * ((max_cells + 31) / 32)                 -> CAP_NODES    (runSipp, before the search)
   arrival     the largest arrival time of any neighbour getNeighbors emitted (closed ones included: the kernel tests the
@@ -56,7 +56,7 @@ for _p in (ROOT, os.path.join(ROOT, "tests")):
 import limit_cases as lc  # noqa: E402
 
 INT_MAX = 2 ** 31 - 1
-# ---- the constants of the engine the classes rest on, named once (csrc/ll_sipp.h, csrc/ll_device.h, mrp_ll_host.cpp) ----
+# ---- the constants of the engine the classes rest on, named once (csrc/ll_sipp.h, csrc/ll_device.h, csrc/host/ll_pack.h) ----
 G_MAX = 1023            # kGMask: the 10-bit g field of every open key
 LDS_NODES = 768         # MRP_LL_SIPP_LDS_NODES = kSippLdsCap: node records (ids 0 .. 766) and 32-bit open entries of TierLdsSipp
 MIX_OPEN = 1152         # (kSippLdsBytes - 16) / 8: 64-bit open entries of TierMix

@@ -9,16 +9,18 @@
 
 #include "wave_emu.h"
 #include "../../libmultirobotplanning_amd/csrc/ll_compact.h"
+#include "../../libmultirobotplanning_amd/csrc/host/ll_pack.h"
 
 namespace {
-int neighborIndexFromDelta(int dx, int dy) {  // Wait, Left, Right, Up, Down (ecbs.cpp:365-398)
-  if (dx == 0 && dy == 0) return 0;
-  if (dx == -1 && dy == 0) return 1;
-  if (dx == 1 && dy == 0) return 2;
-  if (dx == 0 && dy == 1) return 3;
-  if (dx == 0 && dy == -1) return 4;
-  return -1;
-}
+using mrp::host::fillFocalTable;
+using mrp::host::focalTableRows;
+using mrp::host::packEdgeWords;
+using mrp::host::packVertexWords;
+constexpr int kHorizon = 1024;  // mrp_ll_options.max_horizon at its largest: the packer drops constraints at or beyond it
+struct VecSink {                // where the packer's words go here
+  std::vector<uint32_t>& v;
+  void push(uint32_t w) { v.push_back(w); }
+};
 }  // namespace
 
 extern "C" {
@@ -45,49 +47,29 @@ int emu_compact_search(int eps, int dimx, int dimy, int n_obst, const int32_t* o
     const uint32_t c = (uint32_t)(y * dimx + x);
     obst[c >> 5] |= 1u << (c & 31);
   }
-  // packer: the same words libmultirobotplanning_amd/csrc/mrp_ll_host.cpp packJob writes
+  // the packer's own functions (libmultirobotplanning_amd/csrc/host/ll_pack.h): the words packJob writes
   std::vector<uint32_t> vcw, ecw;
-  int lastGoal = -1;
-  for (int i = 0; i < n_vc; ++i) {
-    const int32_t* v = vc + 3 * i;
-    if (v[1] == gx && v[2] == gy) lastGoal = std::max(lastGoal, v[0]);
-    if (v[0] < 0 || v[0] >= 1024 || v[1] < 0 || v[1] >= dimx || v[2] < 0 || v[2] >= dimy) continue;
-    vcw.push_back(((uint32_t)v[0] << 16) | ((uint32_t)v[2] << 8) | (uint32_t)v[1]);
-  }
-  for (int i = 0; i < n_ec; ++i) {
-    const int32_t* e = ec + 5 * i;
-    const int k = neighborIndexFromDelta(e[3] - e[1], e[4] - e[2]);
-    if (k < 0 || e[0] < 0 || e[0] >= 1024 || e[1] < 0 || e[1] >= dimx || e[2] < 0 || e[2] >= dimy) continue;
-    ecw.push_back(((uint32_t)e[0] << 19) | ((uint32_t)(e[2] * dimx + e[1]) << 3) | (uint32_t)k);
-  }
+  VecSink vcs{vcw}, ecs{ecw};
+  const int lastGoal = packVertexWords(vc, n_vc, dimx, dimy, kHorizon, gx, gy, false, vcs);
+  packEdgeWords(ec, n_ec, dimx, dimy, kHorizon, ecs);
   vcw.push_back(0);
   ecw.push_back(0);
   // focal context: time-major table of the other agents' cells (x | y << 8), each path extended by its last cell
   std::vector<uint16_t> table;
   uint32_t npad = 0, tpad = 0;
   if (eps && n_agents > 0) {
-    int tp = 0;
-    for (int a = 0; a < n_agents; ++a)
-      if (a != agent_idx && path_len[a] > 0) tp = std::max(tp, path_len[a]);
+    std::vector<const int32_t*> pathOf((size_t)n_agents);  // the flattened paths as mrp_ll_job::path_xy has them
+    size_t off = 0;
+    for (int a = 0; a < n_agents; ++a) {
+      pathOf[a] = path_xy + 2 * off;
+      off += (size_t)std::max(path_len[a], 0);
+    }
+    const int tp = focalTableRows(n_agents, agent_idx, path_len);
     if (tp > 0) {
       npad = ((uint32_t)n_agents + 15u) & ~15u;
       tpad = (uint32_t)tp;
-      table.assign((size_t)tpad * npad, 0xFFFFu);
-      size_t off = 0;
-      for (int a = 0; a < n_agents; ++a) {
-        const int len = path_len[a];
-        if (a != agent_idx && len > 0) {
-          uint16_t cell = 0xFFFFu;
-          for (uint32_t tt = 0; tt < tpad; ++tt) {
-            if ((int)tt < len) {
-              const int x = path_xy[2 * (off + tt)], y = path_xy[2 * (off + tt) + 1];
-              cell = (x >= 0 && x < dimx && y >= 0 && y < dimy) ? (uint16_t)(x | (y << 8)) : 0xFFFFu;
-            }
-            table[(size_t)tt * npad + a] = cell;
-          }
-        }
-        off += (size_t)std::max(len, 0);
-      }
+      table.resize((size_t)tpad * npad);
+      fillFocalTable(table.data(), tp, npad, n_agents, agent_idx, path_len, pathOf.data(), dimx, dimy);
     }
   }
   if (npad > 128) return -2;  // (the kernel starts such a job in the arena tier)
@@ -162,19 +144,9 @@ int emu_compact_search_ta(int dimx, int dimy, int n_obst, const int32_t* obst_xy
     obst[c >> 5] |= 1u << (c & 31);
   }
   std::vector<uint32_t> vcw, ecw;
-  int lastGoal = -1;
-  for (int i = 0; i < n_vc; ++i) {
-    const int32_t* v = vc + 3 * i;
-    if (!has_goal || (v[1] == gx && v[2] == gy)) lastGoal = std::max(lastGoal, v[0]);  // cbs_ta.cpp:290-301
-    if (v[0] < 0 || v[0] >= 1024 || v[1] < 0 || v[1] >= dimx || v[2] < 0 || v[2] >= dimy) continue;
-    vcw.push_back(((uint32_t)v[0] << 16) | ((uint32_t)v[2] << 8) | (uint32_t)v[1]);
-  }
-  for (int i = 0; i < n_ec; ++i) {
-    const int32_t* e = ec + 5 * i;
-    const int k = neighborIndexFromDelta(e[3] - e[1], e[4] - e[2]);
-    if (k < 0 || e[0] < 0 || e[0] >= 1024 || e[1] < 0 || e[1] >= dimx || e[2] < 0 || e[2] >= dimy) continue;
-    ecw.push_back(((uint32_t)e[0] << 19) | ((uint32_t)(e[2] * dimx + e[1]) << 3) | (uint32_t)k);
-  }
+  VecSink vcs{vcw}, ecs{ecw};
+  const int lastGoal = packVertexWords(vc, n_vc, dimx, dimy, kHorizon, gx, gy, !has_goal, vcs);  // (no task: any cell, cbs_ta.cpp:290-301)
+  packEdgeWords(ec, n_ec, dimx, dimy, kHorizon, ecs);
   if (vcw.size() > 64 || ecw.size() > 64) return -2;
   vcw.push_back(0);
   ecw.push_back(0);

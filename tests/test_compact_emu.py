@@ -27,6 +27,10 @@ def _emu_lib(force_walk=False):
                                                       "_fw" if force_walk else ""))
     deps = [os.path.join(ROOT, "tests", "support", "emu_ll.cpp"), os.path.join(ROOT, "tests", "support", "wave_emu.h"),
             os.path.join(ROOT, "libmultirobotplanning_amd", "csrc", "ll_compact.h")]
+    # ... and the packer emu_ll.cpp calls, with everything it includes
+    deps += [os.path.join(ROOT, "libmultirobotplanning_amd", "csrc", f) for f in
+             ("host/ll_pack.h", "host/ll_sipp_table.h", "host/ll_unpack.h", "ll_device.h", "heur_layout.h")]
+    deps.append(os.path.join(ROOT, "include", "mrp_ll.h"))
     if not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps):
         san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] if sanitize else []
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-g", "-ffp-contract=off", "-fPIC", "-shared", "-Wall"] + san +
