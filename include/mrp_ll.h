@@ -217,7 +217,12 @@ typedef struct mrp_ll_job {
  * it for conflicts (Environment::getFirstConflict ecbs.cpp:401-452, focalHeuristic ecbs.cpp:315-350): the job's own
  * cost = number of conflicts (0: the root node is the solution, the conflict tree has nothing to do) and fmin = the first
  * one as  time << 24 | type << 16 | agent1 << 8 | agent2  (type 0 vertex / 1 edge), or -1 if there is none; both are -1
- * when the scan did not take place. */
+ * when the scan did not take place (a chain that is cut by chain_count or starts behind agent 0 does not scan).
+ * A budget that has nothing left does not end the chain by itself: the next search starts with max_expansions = 0, like an
+ * ordinary job, and comes back MRP_LL_CAP_EXPANSIONS with expanded = 1 (the expansion that exceeded it).
+ * A chain that is refused — outside such a session (a batch, a mixed session), on a larger map, with a slot id outside the
+ * store, ... — runs nothing and touches no slot: status MRP_LL_BAD_JOB, n_states = 0, expanded = 0, cost = fmin = -1, and
+ * every entry of chain_results MRP_LL_NOT_RUN with its other fields 0. */
 #define MRP_LL_JOB_ROOT_CHAIN 4
 /* MRP_LL_JOB_HEAVY (hint, MRP_LL_ASTAR_EPS): the caller knows that this search outgrows the LDS tier every search starts in
  * (e.g. a root chain ended in front of it): no attempt is made there.  Results never depend on it. */
@@ -336,9 +341,10 @@ int mrp_ll_release_maps(mrp_ll_ctx* ctx);
  * (open list, focal list, walk queue, a (time, cell) bitmap of 64 time steps) in a window of fixed size, plus
  * lds_path_bytes for the focal path table of a search (a larger table is read from the search's arena slot); it serves
  * maps up to 32 x 32 and focal contexts of up to 128 agents.  lds_nodes / 2 = open-list entries a search may hold inside
- * the tier (at most 1023), lds_rows = time steps it may use (at most 64); a search that outgrows a limit is run by the
- * arena tier instead.  0 = keep the current value; lds_nodes < 0 disables the tier.  Results never depend on any of
- * this.  *occupancy_out (may be NULL) receives the resident searches per CU (160 KiB / window + table).  MRP_LL_E_BUSY
+ * the tier (at most 1023), lds_rows = time steps it may use (8 .. 64: a search leaves the tier when it is about to expand a
+ * node that is no goal at a time beyond lds_rows - 2, and beyond 61 in any case); a search that outgrows a limit is run by the
+ * arena tier instead (a root chain ends in front of it).  0 = keep the current value; lds_nodes < 0 disables the tier.
+ * Results never depend on any of this.  *occupancy_out (may be NULL) receives the resident searches per CU (160 KiB / window + table).  MRP_LL_E_BUSY
  * while a batch or a session is in flight. */
 int mrp_ll_configure_tiers(mrp_ll_ctx* ctx, int32_t lds_nodes, int32_t lds_rows, int32_t lds_path_bytes,
                            int32_t* occupancy_out);

@@ -88,7 +88,9 @@ int fillCommonParams(mrp_ll_ctx* ctx, Ticket& t, mrp::LaunchParams& P, uint32_t&
   P.cons_store_stride = env.consStoreStride;
   P.cons_store_slots = env.consStoreSlots;
   P.lds_nodes = ldsNodes;
-  P.lds_rows = rows;
+  // the window is sized for 64 time steps whatever the caller asked for; what mrp_ll_configure_tiers' lds_rows sets is how many
+  // of them a search may use before it leaves the tier (ll_jobs.h narrowMaxT, the only reader)
+  P.lds_rows = std::min(rows, ctx->tierRows);
   P.lds_row_words = rowWords;
   P.lds_paths_bytes = ldsNodes ? ldsPaths : 0;
   if (kDebug) {
@@ -163,6 +165,8 @@ int batchSubmit(mrp_ll_ctx* ctx, const SubmitArgs& a, int32_t* ticketOut) {
       }
     }
     note.init = jobInitOf(jobs[i], ok);
+    // (a root chain needs a session: the packer has refused it, and its results come back as a refused chain's do)
+    note.chain = t.sipp ? 0 : chainResultsOf(jobs[i]);
     if (cs.failed || ps.failed) allocFailed = true;
     if (!ok) {
       // rejected: give the device a trivially capped job and remember the rejection

@@ -85,7 +85,7 @@ int sessionSubmit(mrp_ll_ctx* ctx, const SubmitArgs& a, int32_t* ticketOut) {
     commitSet(ctx->env, ok && !S.sipp, pending, note.setSlot, note.setSeq);
     note.scan = (!S.sipp && (job.flags & MRP_LL_JOB_SCAN_CONFLICTS) && st.conf) ? 1 : 0;
     note.init = jobInitOf(job, ok);
-    note.chain = ((job.flags & MRP_LL_JOB_ROOT_CHAIN) && !S.sipp) ? std::max(1, job.n_agents - job.agent_idx) : 0;
+    note.chain = S.sipp ? 0 : chainResultsOf(job);
     g.jobs[slot] = d;
     ctx->stats.staged_bytes += static_cast<int64_t>(sizeof(DevJob)) + 4 * static_cast<int64_t>(cs.used) +
                                (S.sipp || (d.ctx_flags & mrp::kCtxById) ? 0 : 2 * static_cast<int64_t>(d.t_pad) * d.n_agents_pad);

@@ -137,6 +137,12 @@ static inline void unpackResult(mrp_ll_stats& stats, const DevResult& d, const u
   }
 }
 
+// Entries of mrp_ll_result::chain_results that a job's collection fills in (JobNote::chain): n_agents - agent_idx for a
+// root chain — accepted or rejected, in a session or in a batch —, 0 for every other job.
+static inline int32_t chainResultsOf(const mrp_ll_job& j) {
+  return (j.flags & MRP_LL_JOB_ROOT_CHAIN) ? std::max(1, j.n_agents - j.agent_idx) : 0;
+}
+
 // The output of a root chain (ll_device.h kCtxChain) -> the caller's per-agent results; `count` = results the job may fill,
 // `outWords` = words of the job's host area.
 static inline void unpackChain(mrp_ll_stats& stats, const DevResult& d, const uint16_t* out, bool rejected, mrp_ll_result& r,
