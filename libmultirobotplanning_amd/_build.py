@@ -27,6 +27,8 @@ TARGETS = {
                          extra=[]),
     "libmrp_hl.so": dict(srcs=["hl/mrp_hl.cpp"], deps=["hl/exact_heap.hpp", "hl/grid_mapf.hpp", "hl/ct_solver.hpp",
                                                        "hl/ct_session.hpp", "hl/grid2d_astar.hpp", "hl/instance_io.hpp",
+                                                       "hl/solve_knobs.hpp", "hl/launch_plan.hpp", "hl/rounds_driver.hpp",
+                                                       "hl/sipp_drivers.hpp", "hl/ct_stepped.hpp",
                                                        "../../include/mrp_ll.h", "../../include/mrp_hl.h"],
                          extra=["-pthread", "-L", LIBDIR, "-lmrp_ll", "-Wl,-rpath,$ORIGIN"]),
 }

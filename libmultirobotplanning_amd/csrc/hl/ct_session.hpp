@@ -1,7 +1,8 @@
 // The CBS / ECBS session driver (mrp_hl.h mrp_hl_solver_solve_stream, mode 0) and the helpers it shares with the other
-// drivers of mrp_hl.cpp.  One SessionWorker per host thread: it keeps its engine's resident kernel fed through the job
-// ring, draws instances from an InstanceSource and publishes an instance's next searches the moment its previous ones
-// are back.  What one solve call fixes for every worker is a SessionPlan, what differs per thread a WorkerSeat.
+// drivers (rounds_driver.hpp, sipp_drivers.hpp, ct_stepped.hpp; mrp_hl.cpp includes them all).  One SessionWorker per host
+// thread: it keeps its engine's resident kernel fed through the job ring, draws instances from an InstanceSource and
+// publishes an instance's next searches the moment its previous ones are back.  What one solve call fixes for every
+// worker is a SessionPlan (sized by launch_plan.hpp, knobs from solve_knobs.hpp), what differs per thread a WorkerSeat.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -18,6 +19,7 @@
 
 #include "../../../include/mrp_hl.h"
 #include "ct_solver.hpp"
+#include "solve_knobs.hpp"
 
 namespace mrp_hl {
 
@@ -57,6 +59,9 @@ struct CoSync {
   std::atomic<int32_t> begun{0};     // 1: the session runs, -1: it could not be started
   std::atomic<int32_t> finished{0};  // co-workers that have left their loops
 };
+
+// "<call>: <the engine's last error>", what every driver reports when a call of the low-level engine fails
+inline std::string llError(const char* call, const mrp_ll_ctx* ctx) { return std::string(call) + ": " + mrp_ll_last_error(ctx); }
 
 struct GroupResult {
   int64_t rounds = 0, searches = 0, expansions = 0;  // expansions: of the searches the conflict trees CONSUMED
@@ -185,7 +190,7 @@ struct JobBatch {
 extern "C" __attribute__((weak)) int mrp_ll_submit_scan(mrp_ll_ctx* ctx, int32_t tag, int32_t n_jobs, const mrp_ll_job* jobs,
                                                         mrp_ll_result* results, mrp_ll_conflict* conflicts, int32_t* ticket);
 
-// mrp_ll_submit_sets likewise: without it (or without mrp_ll_constraint_store_reserve, mrp_hl.cpp) every job ships its whole
+// mrp_ll_submit_sets likewise: without it (or without mrp_ll_constraint_store_reserve) every job ships its whole
 // constraint set, as before.
 extern "C" __attribute__((weak)) int mrp_ll_submit_sets(mrp_ll_ctx* ctx, int32_t tag, int32_t n_jobs, const mrp_ll_job* jobs,
                                                         mrp_ll_result* results, mrp_ll_conflict* conflicts,
@@ -307,59 +312,20 @@ inline int64_t writeRootSolution(const std::vector<mrp_ll_result>& r, mrp_hl_sol
   return s.low_level_expanded;
 }
 
-// What one solve call fixes for all of its session workers.  The environment knobs are read here, once per call.
+// What one solve call fixes for all of its session workers (launch_plan.hpp decides the sizes, mrp_hl.cpp fills this in).
 struct SessionPlan {
   mrp_hl_options opt;
   int32_t horizon = 0;     // states a result path may have
   int32_t workgroups = 0;  // resident (front) wavefronts per engine
   int32_t heavyWgs = 0;    // ECBS: heavy workgroups per engine, which take over the searches that outgrow the LDS tier
   int32_t pathSlots = 0;   // slots of every engine's device path store (0: jobs ship their context as tables)
+  int32_t consSlots = 0, consWords = 0;  // the constraint store every engine reserved (0: none, sets ship flat)
   int32_t* gate = nullptr;  // mrp_ll_session_begin_tiers_gated: every worker's heavy launch before anybody's front launch
   int32_t nEngines = 1, nWorkers = 1;
   const StreamView* view = nullptr;
   std::atomic<int32_t>* pool = nullptr;  // the instance counter all workers draw from (nullptr: static split)
   TimePoint epoch;                       // MRP_HL_TIMING only: the moment the solve call started
-  // MRP_HL_SPEC=k, speculation width of the conflict-tree machines (ct_solver.hpp).  Default 2: measured on the shipped
-  // 8x8 CBS inputs (scripts/spec_probe.py) one node of look-ahead halves the time of a small batch (agents8 0.74 -> 0.37 s,
-  // agents10-12 1.78 -> 0.91 s) and wider windows give it back (their searches queue in front of the popped node's own);
-  // ECBS pops a fresh child next almost every time, so looking ahead buys it 0-6 %.
-  int32_t specWidth = 2;
-  bool chainDebug = false;  // MRP_HL_CHAIN_DEBUG: one line per chain answer on stderr
-  bool timing = false;      // MRP_HL_TIMING: where every worker's time went, on stderr
-  bool rootChains = true;   // MRP_HL_ROOT_CHAIN=0: every root search is its own job (A/B; results are the same)
-  bool rootFast = true;     // MRP_HL_ROOT_FAST=0: every instance goes through its conflict-tree machine (A/B; same results)
-  int32_t chainChunk = 8;   // MRP_HL_CHAIN_CHUNK: searches per root-chain job of an instance with many agents
-  // MRP_HL_CHAIN_CHUNK_FROM.  Between 33 and 63 agents the root step goes out one job per search: measured at fifty agents
-  // every form of chain (whole, or in jobs of 4 / 8 / 16 searches) is 5-25 % slower than that, at a hundred agents jobs of
-  // eight are 15 % faster (scripts/r4_run19.sh, r4_run20.sh)
-  int32_t chainChunkFrom = 64;
-  int64_t ringDepth = 0;    // MRP_HL_RING_DEPTH: searches published per worker at a time (0: twice its resident wavefronts)
-  int32_t activeLimit = 0;  // MRP_HL_ACTIVE_LIMIT: instances a worker keeps active at a time (0: its fair share of the pool)
-  // MRP_HL_DEVICE_SCAN=1 (ECBS with a path store): a child's conflicts come back with its low-level search
-  // (mrp_ll_submit_scan) instead of being scanned here at commit and at pop time.  Same results; off by default.
-  bool deviceScan = false;
-  // MRP_HL_DEVICE_CONSTRAINTS=1 (CBS and ECBS): an agent's constraint set stays in the engine's constraint store — a child's
-  // search names its parent's set by slot and ships the one constraint it adds (mrp_ll_submit_sets) instead of the whole
-  // set.  Same results; off by default.  consSlots / consWords: the store every engine reserved (0: none, the switch is off).
-  bool deviceCons = false;
-  int32_t consSlots = 0, consWords = 0;
-  void readKnobs() {
-    auto num = [](const char* name, int64_t dflt) {
-      const char* e = std::getenv(name);
-      return e ? std::atoll(e) : dflt;
-    };
-    specWidth = static_cast<int32_t>(std::max<int64_t>(1, num("MRP_HL_SPEC", 2)));
-    chainDebug = std::getenv("MRP_HL_CHAIN_DEBUG") != nullptr;
-    timing = std::getenv("MRP_HL_TIMING") != nullptr;
-    rootChains = num("MRP_HL_ROOT_CHAIN", 1) != 0;
-    rootFast = num("MRP_HL_ROOT_FAST", 1) != 0;
-    chainChunk = static_cast<int32_t>(std::max<int64_t>(1, num("MRP_HL_CHAIN_CHUNK", 8)));
-    chainChunkFrom = static_cast<int32_t>(num("MRP_HL_CHAIN_CHUNK_FROM", 64));
-    ringDepth = std::max<int64_t>(0, num("MRP_HL_RING_DEPTH", 0));
-    deviceScan = num("MRP_HL_DEVICE_SCAN", 0) != 0;
-    deviceCons = num("MRP_HL_DEVICE_CONSTRAINTS", 0) != 0;
-    activeLimit = std::getenv("MRP_HL_ACTIVE_LIMIT") ? static_cast<int32_t>(std::max<int64_t>(1, num("MRP_HL_ACTIVE_LIMIT", 1))) : 0;
-  }
+  SolveKnobs knobs;                      // the environment knobs, read once per call (solve_knobs.hpp)
 };
 
 // One worker thread's place in the call: its engine and, when two workers share that engine, which of the two it is.
@@ -380,20 +346,20 @@ class SessionWorker {
  public:
   SessionWorker(const SessionPlan& plan, const WorkerSeat& seat, GroupResult& out)
       : plan_(plan), seat_(seat), out_(out), tagged_(seat.coCount > 1 && seat.co != nullptr),
-        rootChains_(plan.pathSlots > 0 && plan.opt.algo == MRP_HL_ECBS && plan.rootChains),
-        deviceScan_(plan.deviceScan && plan.pathSlots > 0 && plan.opt.algo == MRP_HL_ECBS && &mrp_ll_submit_scan != nullptr),
-        deviceCons_(plan.deviceCons && plan.consSlots > 0 && plan.consWords > 0 && engineHasConstraintStore()),
+        rootChains_(plan.pathSlots > 0 && plan.opt.algo == MRP_HL_ECBS && plan.knobs.rootChains),
+        deviceScan_(plan.knobs.deviceScan && plan.pathSlots > 0 && plan.opt.algo == MRP_HL_ECBS && &mrp_ll_submit_scan != nullptr),
+        deviceCons_(plan.consSlots > 0 && plan.consWords > 0),  // (reserved only with MRP_HL_DEVICE_CONSTRAINTS on an engine that has the store)
         // this worker's share of the engine's resident wavefronts
         myWorkgroups_(std::max(1, plan.workgroups / std::max(seat.coCount, 1))),
         source_{plan.view, plan.pool, seat.own, seat.engineIdx} {
-    tm_.on = plan.timing;
+    tm_.on = plan.knobs.timing;
     const int32_t share = plan.pathSlots / seat.coCount;  // co-workers split the engine's path store
     slotPool_.next = tagged_ ? seat.coIndex * share : 0;
     slotPool_.cap = tagged_ ? slotPool_.next + share : plan.pathSlots;
     const int32_t consShare = plan.consSlots / seat.coCount;  // ... and its constraint store
     consPool_.next = tagged_ ? seat.coIndex * consShare : 0;
     consPool_.cap = !deviceCons_ ? 0 : tagged_ ? consPool_.next + consShare : plan.consSlots;
-    ringTarget_ = plan.ringDepth > 0 ? plan.ringDepth : std::max<int64_t>(2 * static_cast<int64_t>(myWorkgroups_), 32);
+    ringTarget_ = plan.knobs.ringDepth > 0 ? plan.knobs.ringDepth : std::max<int64_t>(2 * static_cast<int64_t>(myWorkgroups_), 32);
     // Admission control: at most `activeLimit_` instances of this worker are active at a time; the rest wait in the pool.
     // With the job slots recycled in completion order it costs nothing (measured 1536..3584 at the bench shape: same step
     // time as "everything at once"), and with a shared pool it is what lets the workers balance: no worker may hold more
@@ -401,7 +367,7 @@ class SessionWorker {
     const size_t nW = static_cast<size_t>(std::max(plan.nWorkers, 1));
     activeLimit_ = plan.pool ? std::max<size_t>(1, std::min<size_t>(16384, (static_cast<size_t>(plan.view->total()) + nW - 1) / nW))
                              : seat.own->size();
-    if (plan.activeLimit > 0) activeLimit_ = static_cast<size_t>(plan.activeLimit);
+    if (plan.knobs.activeLimit > 0) activeLimit_ = static_cast<size_t>(plan.knobs.activeLimit);
   }
 
   void run() {
@@ -487,7 +453,7 @@ class SessionWorker {
     out_.err = what;
     return false;
   }
-  bool failLL(const char* call) { return fail(std::string(call) + ": " + mrp_ll_last_error(seat_.ctx)); }
+  bool failLL(const char* call) { return fail(llError(call, seat_.ctx)); }
 
   // ECBS: front workgroups (the LDS tier alone) + heavy workgroups that take over the searches that outgrow it; all
   // workers' heavy launches go first (the gate), then the front ones (mrp_ll.h mrp_ll_session_begin_tiers_gated).  The
@@ -556,12 +522,12 @@ class SessionWorker {
   }
 
   // The root step of an ECBS tree goes out as a chain when the engine takes chains, the request is the only one waiting
-  // and the agent count is one at which chains pay (SessionPlan::chainChunkFrom).
+  // and the agent count is one at which chains pay (SolveKnobs::chainChunkFrom).
   bool chainable(const Live& L) const {
     const Instance& I = *L.inst;
     const LLRequest& r = L.req[L.reqHead];
     return rootChains_ && r.group == kRootGroup && I.algo() == MRP_HL_ECBS && r.context && L.reqHead + 1 == L.req.size() &&
-           I.nAgents() >= 2 && I.nAgents() <= 128 && (I.nAgents() <= 32 || I.nAgents() >= plan_.chainChunkFrom) &&
+           I.nAgents() >= 2 && I.nAgents() <= 128 && (I.nAgents() <= 32 || I.nAgents() >= plan_.knobs.chainChunkFrom) &&
            r.agent != L.noChainAgent;
   }
   // The root step of an ECBS tree as ONE job (MRP_LL_JOB_ROOT_CHAIN): the workgroup plans this agent and every later one
@@ -610,7 +576,7 @@ class SessionWorker {
     // many agents: jobs of at most eight searches — a root step of fifty searches in ONE job holds its wavefront for
     // tens of milliseconds, and the two-search rounds of deep conflict trees queue behind such jobs (measured at fifty
     // agents: the step 26 % longer than with one job per root search)
-    j.chain_count = nA >= plan_.chainChunkFrom ? plan_.chainChunk : 0;
+    j.chain_count = nA >= plan_.knobs.chainChunkFrom ? plan_.knobs.chainChunk : 0;
     const int32_t pi = acquirePending(k, kRootGroup);
     Pending& P = pend_[pi];
     const int32_t cnt = nA - first;
@@ -756,7 +722,7 @@ class SessionWorker {
   }
 
   // look ahead only while the engine has idle wavefronts: speculative searches must not queue in front of real ones
-  int32_t specNow() const { return jobsOut_ < static_cast<int64_t>(myWorkgroups_) ? plan_.specWidth : 1; }
+  int32_t specNow() const { return jobsOut_ < static_cast<int64_t>(myWorkgroups_) ? plan_.knobs.specWidth : 1; }
 
   bool admit() {  // next instance of the pool, false when it is empty
     InstanceSource::Item it;
@@ -848,7 +814,7 @@ class SessionWorker {
     const size_t cnt = P.chainRes.size();
     // The chain planned every agent and its workgroup found no conflict among the paths: the root node is the
     // solution.  Seven ten-agent instances in ten end here, without a path object, a conflict-tree node or a scan.
-    if (plan_.rootFast && P.chainFirst == 0 && L.inst && !L.counted && static_cast<size_t>(P.res[0].n_states) == cnt &&
+    if (plan_.knobs.rootFast && P.chainFirst == 0 && L.inst && !L.counted && static_cast<size_t>(P.res[0].n_states) == cnt &&
         P.res[0].cost == 0 && static_cast<int32_t>(cnt) == L.inst->nAgents() && L.inst->llSearches() == 0 &&
         (plan_.opt.max_hl_expansions < 0 || plan_.opt.max_hl_expansions >= 1)) {
       const int64_t ll = writeRootSolution(P.chainRes, plan_.view->sol(gidx_[k]));
@@ -863,7 +829,7 @@ class SessionWorker {
     size_t q = 0;
     for (; q < cnt; ++q) {
       const mrp_ll_result& r = P.chainRes[q];
-      if (plan_.chainDebug)
+      if (plan_.knobs.chainDebug)
         std::fprintf(stderr, "[chain] inst %d agent %d: status %d cost %d fmin %d n %d expanded %lld\n", gidx_[k],
                      P.chainFirst + static_cast<int>(q), r.status, r.cost, r.fmin, r.n_states, (long long)r.expanded);
       if (r.status == MRP_LL_NOT_RUN || !L.inst) break;
@@ -991,8 +957,8 @@ class SessionWorker {
   // not const: an engine that cannot run chains — no compact tier, a window too small for the chain's focal table —
   // rejects the first one, and this worker goes on with one job per root search
   bool rootChains_;
-  bool deviceScan_;  // children go out through mrp_ll_submit_scan (SessionPlan::deviceScan, and the engine has the call)
-  const bool deviceCons_;  // children name their constraint sets by slot (SessionPlan::deviceCons, and the engine has the call)
+  bool deviceScan_;  // children go out through mrp_ll_submit_scan (SolveKnobs::deviceScan, and the engine has the call)
+  const bool deviceCons_;  // children name their constraint sets by slot (the call reserved a constraint store: SolveKnobs::deviceCons)
   const int32_t myWorkgroups_;
   // f2: slots of the engine's device-resident path store, handed to the searches of this worker for their result paths.
   // Declared before every member that can hold a Path (live_, pend_ via its tickets' instances, ans_): members are

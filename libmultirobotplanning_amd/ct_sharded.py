@@ -25,7 +25,7 @@ import numpy as np
 
 from . import hl
 
-_FAILED_ROUND = -(2 ** 31)  # group id of a failure row (mrp_hl.cpp kFailedRound): no conflict-tree group uses it
+_FAILED_ROUND = -(2 ** 31)  # group id of a failure row (csrc/hl/ct_stepped.hpp kFailedRound): no conflict-tree group uses it
 _HDR = 8  # int32 words in front of the path: group, slot, status, cost, fmin, expanded lo, expanded hi, n_states
 
 

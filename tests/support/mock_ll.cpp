@@ -1,20 +1,26 @@
 // TEST INFRASTRUCTURE ONLY — never shipped, never built into libmultirobotplanning_amd/lib.
-// Implements the C-ABI of include/mrp_ll.h on top of the ORACLE's low-level search (oracle_ll_search) so that the
-// host-side conflict-tree drivers (csrc/hl/) can be exercised on a machine without a GPU (`-m "not gpu"` tests).
+// Implements the C-ABI of include/mrp_ll.h on top of the ORACLE's low-level searches (oracle_ll_search; oracle_sipp_single_at
+// for MRP_LL_SIPP jobs) so that the host-side drivers (csrc/hl/) can be exercised on a machine without a GPU (`-m "not gpu"`
+// tests).
 // The product library has no such path: libmrp_ll.so fails with MRP_LL_E_DEVICE when no HIP device exists.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cstdarg>
 #include <string>
 #include <map>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "../../include/mrp_ll.h"
 
 extern "C" void oracle_conflict_scan(int nAgents, const int32_t* pathLen, const int32_t* pathXY, int32_t* out);
+extern "C" int oracle_sipp_single_at(int dimx, int dimy, int nObst, const int32_t* obstXY, int sx, int sy, int gx, int gy, int nCI,
+                                     const int32_t* ci, int startTime, int32_t* statesXYT, int cap, int64_t* expanded,
+                                     int32_t* costFmin);
 extern "C" int oracle_ll_search(int algo, float w, int dimx, int dimy, int nObst, const int32_t* obstXY, int agentIdx,
                                 int startX, int startY, int goalX, int goalY, int nVC, const int32_t* vc, int nEC,
                                 const int32_t* ec, int nCtx, const int32_t* ctxLen, const int32_t* ctxXY,
@@ -35,7 +41,45 @@ struct mrp_ll_ctx {
   const mrp_ll_job* jobs = nullptr;
   mrp_ll_result* results = nullptr;
   std::vector<std::vector<int32_t>> store;  // MRP_MOCK_PATH_STORE=1: the "device" path store, slot -> x, y, x, y, ...
+  int32_t index = 0;      // how many contexts this process had created before this one (MRP_MOCK_CALL_LOG)
+  uint32_t tagsSeen = 0;  // bit t: a worker with tag t has made a tagged call since the last mrp_ll_session_end
 };
+
+// MRP_MOCK_CALL_LOG=<file>: the calls that size and start a solve — tiers, occupancy, geometry, session begin / end, store
+// reserves — append one line each, "<context index> <call> <integer arguments>", so that a test can pin what a driver asks
+// of every engine (tests/test_launch_plan_cpu.py).  Engines race each other in the file; the lines of one engine are in
+// call order.
+namespace {
+std::mutex g_logMu;
+int32_t g_created = 0;  // (under g_logMu)
+void callLog(const mrp_ll_ctx* c, const char* fmt, ...) {
+  const char* file = std::getenv("MRP_MOCK_CALL_LOG");
+  if (!file) return;
+  std::lock_guard<std::mutex> lock(g_logMu);
+  if (FILE* f = std::fopen(file, "a")) {
+    std::fprintf(f, "%d ", c->index);
+    va_list ap;
+    va_start(ap, fmt);
+    std::vfprintf(f, fmt, ap);
+    va_end(ap);
+    std::fputc('\n', f);
+    std::fclose(f);
+  }
+}
+// MRP_MOCK_GEOMETRY="occ,frontOcc,frontLds,heavyLds": what mrp_ll_configure_tiers / mrp_ll_session_occupancy (occ) and
+// mrp_ll_session_tiers_geometry (the other three) report.  Unset: 4, 12, 12928, 31360.
+struct MockGeometry {
+  int occ = 4, frontOcc = 12, frontLds = 12928, heavyLds = 31360;
+};
+MockGeometry mockGeometry() {
+  MockGeometry g;
+  if (const char* e = std::getenv("MRP_MOCK_GEOMETRY")) {
+    MockGeometry h;
+    if (std::sscanf(e, "%d,%d,%d,%d", &h.occ, &h.frontOcc, &h.frontLds, &h.heavyLds) == 4) g = h;
+  }
+  return g;
+}
+}  // namespace
 
 extern "C" {
 const char* mrp_ll_version(void) { return "mrp_ll MOCK (oracle-backed, tests only)"; }
@@ -43,6 +87,11 @@ const char* mrp_ll_last_error(const mrp_ll_ctx* c) { return c ? c->err.c_str() :
 int mrp_ll_create(const mrp_ll_options*, mrp_ll_ctx** out) {
   *out = new mrp_ll_ctx();
   std::memset(&(*out)->stats, 0, sizeof(mrp_ll_stats));
+  {
+    std::lock_guard<std::mutex> lock(g_logMu);
+    (*out)->index = g_created++;
+  }
+  callLog(*out, "create");
   return MRP_LL_SUCCESS;
 }
 void mrp_ll_destroy(mrp_ll_ctx* c) { delete c; }
@@ -133,10 +182,85 @@ static void mockChain(mrp_ll_ctx* c, const mrp_ll_job& j, mrp_ll_result& r) {
   }
 }
 
+}  // extern "C"
+
+// An incrementally maintained SIPP table (mrp_ll.h mrp_ll_sipp_table_*): per cell the collision intervals added so far, and
+// the cells that have some in first-touch order (the order does not matter to SIPP::setCollisionIntervals).
+struct mrp_ll_sipp_table {
+  std::map<std::pair<int32_t, int32_t>, std::vector<std::pair<int32_t, int32_t>>> perCell;
+  std::vector<std::pair<int32_t, int32_t>> touched;
+  void add(int32_t x, int32_t y, int32_t s, int32_t e) {
+    std::vector<std::pair<int32_t, int32_t>>& v = perCell[{x, y}];
+    if (v.empty()) touched.push_back({x, y});
+    v.push_back({s, e});
+  }
+};
+
+// An MRP_LL_SIPP job through the oracle's single-agent SIPP search, in either form: the collision_* arrays (a location given
+// twice keeps the later list) or a sipp_table, to which a committed search adds the stays of the path it found.  The oracle
+// has no expansion cap: a search that needed more than max_expansions > 0 expansions comes back as MRP_LL_CAP_EXPANSIONS.
+static void mockSipp(mrp_ll_ctx* c, const mrp_ll_job& j, mrp_ll_result& r) {
+  const MockMap& m = c->maps[j.map_id];
+  mrp_ll_sipp_table arrays;
+  if (!j.sipp_table) {
+    const int32_t* iv = j.collision_intervals;
+    for (int32_t l = 0; l < j.n_collision_locations; ++l) {
+      const std::pair<int32_t, int32_t> cell{j.collision_xy[2 * l], j.collision_xy[2 * l + 1]};
+      if (arrays.perCell.count(cell)) arrays.perCell[cell].clear();
+      for (int32_t k = 0; k < j.collision_count[l]; ++k, iv += 2) arrays.add(cell.first, cell.second, iv[0], iv[1]);
+    }
+  }
+  mrp_ll_sipp_table* table = j.sipp_table ? const_cast<mrp_ll_sipp_table*>(j.sipp_table) : &arrays;
+  std::vector<int32_t> ci;
+  for (const auto& cell : table->touched)
+    for (const auto& iv : table->perCell[cell]) ci.insert(ci.end(), {cell.first, cell.second, iv.first, iv.second});
+  const int cap = 4096;
+  std::vector<int32_t> xyt(3 * cap);
+  int64_t expanded = 0;
+  int32_t costFmin[2] = {0, 0};
+  const int n = oracle_sipp_single_at(m.dimx, m.dimy, static_cast<int>(m.obst.size() / 2), m.obst.data(), j.start_x, j.start_y,
+                                      j.goal_x, j.goal_y, static_cast<int>(ci.size() / 4), ci.data(), j.initial_cost, xyt.data(),
+                                      cap, &expanded, costFmin);
+  r.tier = 0;
+  c->stats.jobs += 1;
+  if (j.max_expansions > 0 && expanded > j.max_expansions) {
+    r.status = MRP_LL_CAP_EXPANSIONS;
+    r.expanded = j.max_expansions;
+    c->stats.expansions += r.expanded;
+    return;
+  }
+  r.expanded = expanded;
+  c->stats.expansions += expanded;
+  r.status = n > 0 ? MRP_LL_OK : MRP_LL_NO_SOLUTION;
+  r.cost = costFmin[0];
+  r.fmin = costFmin[1];
+  r.n_states = std::min(n, cap);
+  if (n == 0) return;
+  if (r.n_states > r.states_cap) r.status = MRP_LL_PATH_TRUNCATED;
+  for (int k = 0; k < r.n_states && k < r.states_cap && r.states_txy; ++k) {
+    r.states_txy[3 * k] = xyt[3 * k + 2];
+    r.states_txy[3 * k + 1] = xyt[3 * k];
+    r.states_txy[3 * k + 2] = xyt[3 * k + 1];
+  }
+  if (j.sipp_table && j.sipp_commit && r.status == MRP_LL_OK) {  // one interval per maximal stay, the last one open-ended
+    int first = 0;
+    for (int k = 1; k <= n; ++k)
+      if (k == n || xyt[3 * k] != xyt[3 * first] || xyt[3 * k + 1] != xyt[3 * first + 1]) {
+        table->add(xyt[3 * first], xyt[3 * first + 1], xyt[3 * first + 2], k == n ? INT32_MAX : xyt[3 * k + 2] - 1);
+        first = k;
+      }
+  }
+}
+
+extern "C" {
 int mrp_ll_search_batch(mrp_ll_ctx* c, int32_t n, const mrp_ll_job* jobs, mrp_ll_result* res) {
   for (int i = 0; i < n; ++i) {
     const mrp_ll_job& j = jobs[i];
     mrp_ll_result& r = res[i];
+    if (j.algo == MRP_LL_SIPP && j.map_id >= 0 && j.map_id < static_cast<int>(c->maps.size())) {
+      mockSipp(c, j, r);
+      continue;
+    }
     // MRP_MOCK_CHAIN_REJECT=1: an engine that cannot run root chains (mrp_ll.h MRP_LL_JOB_ROOT_CHAIN): nothing is run
     if ((j.flags & MRP_LL_JOB_ROOT_CHAIN) && std::getenv("MRP_MOCK_CHAIN_REJECT")) {
       r.status = MRP_LL_BAD_JOB;
@@ -258,6 +382,7 @@ int mrp_ll_submit_tagged(mrp_ll_ctx* c, int32_t tag, int32_t n, const mrp_ll_job
   if (tag < 0 || tag > 3) return MRP_LL_E_INVALID;
   traceSubmit(n, jobs);
   std::lock_guard<std::mutex> lock(g_coMu);
+  c->tagsSeen |= 1u << tag;
   if (mockBusy(g_coDone[tag][c].size())) return MRP_LL_E_BUSY;
   *ticket = c->nextTicket++ & 0xFFFF;
   g_coDone[tag][c].push_back(*ticket);
@@ -266,6 +391,9 @@ int mrp_ll_submit_tagged(mrp_ll_ctx* c, int32_t tag, int32_t n, const mrp_ll_job
 int mrp_ll_poll_any_tagged(mrp_ll_ctx* c, int32_t tag, int32_t* tickets, int32_t cap, int32_t* n) {
   if (tag < 0 || tag > 3) return MRP_LL_E_INVALID;
   std::lock_guard<std::mutex> lock(g_coMu);
+  // (a co-worker that finds the pool of instances empty never submits, but it always polls once: counting both calls keeps
+  // the tag count of the call log independent of which worker thread started first)
+  c->tagsSeen |= 1u << tag;
   std::vector<int32_t>& d = g_coDone[tag][c];
   int32_t k = 0;
   while (!d.empty() && k < cap && k < 3) {  // a few at a time, newest first: out of submission order
@@ -310,35 +438,65 @@ int mrp_ll_poll_any(mrp_ll_ctx* c, int32_t* tickets, int32_t cap, int32_t* n) {
   *n = k;
   return MRP_LL_SUCCESS;
 }
-int mrp_ll_wait(mrp_ll_ctx*, int32_t) { return MRP_LL_SUCCESS; }
+int mrp_ll_wait(mrp_ll_ctx* c, int32_t ticket) {  // (it ran inside mrp_ll_submit; a ticket waited for is not polled later)
+  auto it = std::find(c->doneTickets.begin(), c->doneTickets.end(), ticket);
+  if (it != c->doneTickets.end()) c->doneTickets.erase(it);
+  return MRP_LL_SUCCESS;
+}
 int mrp_ll_sync_maps(mrp_ll_ctx*) { return MRP_LL_SUCCESS; }
 int mrp_ll_release_maps(mrp_ll_ctx* c) {
   c->maps.clear();
   return MRP_LL_SUCCESS;
 }
-int mrp_ll_configure_tiers(mrp_ll_ctx*, int32_t, int32_t, int32_t, int32_t* occ) {
-  if (occ) *occ = 4;
+int mrp_ll_configure_tiers(mrp_ll_ctx* c, int32_t nodes, int32_t rows, int32_t pathBytes, int32_t* occ) {
+  callLog(c, "configure_tiers %d %d %d", nodes, rows, pathBytes);
+  if (occ) *occ = mockGeometry().occ;
   return MRP_LL_SUCCESS;
 }
-int mrp_ll_session_occupancy(mrp_ll_ctx*, int32_t, int32_t* occ) {
-  if (occ) *occ = 4;
+int mrp_ll_session_occupancy(mrp_ll_ctx* c, int32_t algo, int32_t* occ) {
+  callLog(c, "session_occupancy %d", algo);
+  if (occ) *occ = mockGeometry().occ;
   return MRP_LL_SUCCESS;
 }
-int mrp_ll_session_begin(mrp_ll_ctx*, int32_t) { return MRP_LL_SUCCESS; }
-int mrp_ll_session_begin_sipp(mrp_ll_ctx*, int32_t) { return MRP_LL_SUCCESS; }
-int mrp_ll_session_begin_algo(mrp_ll_ctx*, int32_t, int32_t) { return MRP_LL_SUCCESS; }
-int mrp_ll_session_begin_tiers(mrp_ll_ctx*, int32_t, int32_t, int32_t) { return MRP_LL_SUCCESS; }
-int mrp_ll_session_begin_tiers_gated(mrp_ll_ctx*, int32_t, int32_t, int32_t, int32_t* gate, int32_t) {
+int mrp_ll_session_begin(mrp_ll_ctx* c, int32_t wgs) {
+  callLog(c, "session_begin %d", wgs);
+  return MRP_LL_SUCCESS;
+}
+int mrp_ll_session_begin_sipp(mrp_ll_ctx* c, int32_t wgs) {
+  callLog(c, "session_begin_sipp %d", wgs);
+  return MRP_LL_SUCCESS;
+}
+int mrp_ll_session_begin_algo(mrp_ll_ctx* c, int32_t algo, int32_t wgs) {
+  callLog(c, "session_begin_algo %d %d", algo, wgs);
+  return MRP_LL_SUCCESS;
+}
+int mrp_ll_session_begin_tiers(mrp_ll_ctx* c, int32_t algo, int32_t wgs, int32_t heavy) {
+  callLog(c, "session_begin_tiers %d %d %d", algo, wgs, heavy);
+  return MRP_LL_SUCCESS;
+}
+int mrp_ll_session_begin_tiers_gated(mrp_ll_ctx* c, int32_t algo, int32_t wgs, int32_t heavy, int32_t* gate, int32_t nGate) {
+  callLog(c, "session_begin_tiers_gated %d %d %d %d", algo, wgs, heavy, nGate);
   if (gate) __atomic_fetch_add(gate, 1, __ATOMIC_ACQ_REL);
   return MRP_LL_SUCCESS;
 }
-int mrp_ll_session_tiers_geometry(mrp_ll_ctx*, int32_t* occ, int32_t* front, int32_t* heavy) {
-  if (occ) *occ = 12;
-  if (front) *front = 12928;
-  if (heavy) *heavy = 31360;
+int mrp_ll_session_tiers_geometry(mrp_ll_ctx* c, int32_t* occ, int32_t* front, int32_t* heavy) {
+  callLog(c, "session_tiers_geometry");
+  const MockGeometry g = mockGeometry();
+  if (occ) *occ = g.frontOcc;
+  if (front) *front = g.frontLds;
+  if (heavy) *heavy = g.heavyLds;
   return MRP_LL_SUCCESS;
 }
-int mrp_ll_session_end(mrp_ll_ctx*) { return MRP_LL_SUCCESS; }
+int mrp_ll_session_end(mrp_ll_ctx* c) {
+  int tags = 0;
+  {
+    std::lock_guard<std::mutex> lock(g_coMu);
+    for (int t = 0; t < 4; ++t) tags += (c->tagsSeen >> t) & 1u;
+    c->tagsSeen = 0;
+  }
+  callLog(c, "session_end tags=%d", tags);
+  return MRP_LL_SUCCESS;
+}
 int mrp_ll_poll(mrp_ll_ctx*, int32_t, int32_t* done) {
   *done = 1;  // the mock runs every job synchronously inside mrp_ll_submit
   return MRP_LL_SUCCESS;
@@ -350,16 +508,20 @@ int mrp_ll_conflict_scan(mrp_ll_ctx*, int32_t, const int32_t*, const int32_t*, c
 // ids and root chains run on the CPU too
 int mrp_ll_path_store_reserve(mrp_ll_ctx* c, int32_t n) {
   const char* e = std::getenv("MRP_MOCK_PATH_STORE");
-  if (!e || *e != '1') return MRP_LL_E_DEVICE;
+  const bool have = e && *e == '1';
+  callLog(c, "path_store_reserve %d -> %d", n, have ? MRP_LL_SUCCESS : MRP_LL_E_DEVICE);
+  if (!have) return MRP_LL_E_DEVICE;
   c->store.assign(static_cast<size_t>(std::max(n, 0)), std::vector<int32_t>());
   return MRP_LL_SUCCESS;
 }
-struct mrp_ll_sipp_table {};  // SIPP has no stand-in here: the prioritized-SIPP driver is covered by the GPU tests
 int mrp_ll_sipp_table_create(mrp_ll_ctx*, int32_t, mrp_ll_sipp_table** out) {
   *out = new mrp_ll_sipp_table();
   return MRP_LL_SUCCESS;
 }
-int mrp_ll_sipp_table_add(mrp_ll_sipp_table*, int32_t, int32_t, int32_t, int32_t) { return MRP_LL_SUCCESS; }
+int mrp_ll_sipp_table_add(mrp_ll_sipp_table* t, int32_t x, int32_t y, int32_t s, int32_t e) {
+  t->add(x, y, s, e);
+  return MRP_LL_SUCCESS;
+}
 void mrp_ll_sipp_table_destroy(mrp_ll_sipp_table* t) { delete t; }
 int mrp_ll_get_stats(const mrp_ll_ctx* c, mrp_ll_stats* out) {
   *out = c->stats;

@@ -43,7 +43,10 @@ void mock_ll_sets_reset(void) {
 }
 
 int mrp_ll_constraint_store_reserve(mrp_ll_ctx* c, int32_t nSlots, int32_t wordsPerSlot) {
-  if (!c || nSlots < 0 || wordsPerSlot < 0 || wordsPerSlot > 2048 || (nSlots > 0 && wordsPerSlot == 0)) return MRP_LL_E_INVALID;
+  if (!c) return MRP_LL_E_INVALID;
+  const bool bad = nSlots < 0 || wordsPerSlot < 0 || wordsPerSlot > 2048 || (nSlots > 0 && wordsPerSlot == 0);
+  callLog(c, "constraint_store_reserve %d %d -> %d", nSlots, wordsPerSlot, bad ? MRP_LL_E_INVALID : MRP_LL_SUCCESS);
+  if (bad) return MRP_LL_E_INVALID;
   {  // WORKAROUND for mock_ll.cpp, which this file may not change: its mrp_ll_destroy never forgets a context's co-worker
      // books (g_coDone), and a new context may live where a destroyed one did.  The `tagged` test in mrp_ll_submit_sets
      // below — and the same test in mock_ll_scan.cpp — would then take a lone worker for a co-worker and file its tickets

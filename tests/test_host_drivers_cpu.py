@@ -359,3 +359,130 @@ def test_publication_order_is_unchanged(cpu_solver, bench_instances, oracle_expe
     print(config, got, sha)
     assert got == want_stats
     assert sha == want_trace
+
+
+# ---- the prioritized-SIPP drivers (csrc/hl/sipp_drivers.hpp) against oracle.prioritized_sipp ----------------------------
+# The stand-in answers an MRP_LL_SIPP job with the oracle's single-agent SIPP search, in both job forms (collision arrays;
+# an engine-side table with sipp_commit), so the drivers' own part — the order of the agents, the interval bookkeeping,
+# the per-instance stop, the statistics — is what is compared.
+SIPP_SCHEDULES = {"session": {}, "batch": {"MRP_HL_SIPP_BATCH": "1"}}
+
+
+@pytest.fixture(scope="module")
+def sipp_instances(ref_tests):
+    """The reference's own prioritized-SIPP fixtures and a few generated instances of 8-12 agents on small grids."""
+    from libmultirobotplanning_amd import hl
+    insts = [ref_tests["mapf"][n] for n in ref_tests["prioritized_sipp"]["cost"]]
+    insts += [hl.generate_instance(8800 + k, 8, 8, 12, 8 + k % 5) for k in range(6)]
+    insts += [hl.generate_instance(16600 + k, 16, 16, 25, 12 - k % 5) for k in range(5)]
+    return insts
+
+
+@pytest.fixture(scope="module")
+def sipp_expected(oracle_mod, sipp_instances):
+    """Per instance: oracle.prioritized_sipp's answer plus the expansions of every agent's search, from the same loop
+    (mapf_prioritized_sipp.cpp:214-270) over the oracle's single-agent search."""
+    out = []
+    for inst in sipp_instances:
+        o = dict(oracle_mod.prioritized_sipp(inst))
+        o["agent_expanded"] = _sipp_agent_expansions(oracle_mod, inst, o)
+        out.append(o)
+    return out
+
+
+def _sipp_agent_expansions(oracle_mod, inst, o):
+    intervals, per_agent = [], []
+    for a, (s, g) in enumerate(zip(inst["starts"], inst["goals"])):
+        states, expanded, _, _ = oracle_mod.sipp_single_at(inst["dimx"], inst["dimy"], inst["obstacles"], s, g, intervals)
+        per_agent.append(expanded)
+        assert states == o["schedules"][a]
+        first = 0
+        for k in range(1, len(states) + 1):  # one interval per maximal stay on a cell, the last one open-ended
+            if k == len(states) or states[k][:2] != states[first][:2]:
+                intervals.append(states[first][:2] + [states[first][2], 2 ** 31 - 1 if k == len(states) else states[k][2] - 1])
+                first = k
+    assert sum(per_agent) == o["expanded"]
+    return per_agent
+
+
+def _assert_sipp_answers(res, stats, insts, expected):
+    for i, (inst, r, o) in enumerate(zip(insts, res, expected)):
+        assert (r["status"], r["cost"], r["n_planned"], r["planned"], r["expanded"]) == (
+            0, o["cost"], o["n_planned"], o["planned"], o["expanded"]), i
+        assert r["schedules"] == o["schedules"], i
+    assert stats["rounds"] == max(len(inst["starts"]) for inst in insts)  # the longest chain of dependent searches
+    assert stats["ll_searches"] == sum(len(inst["starts"]) for inst in insts)
+    assert stats["ll_expansions"] == sum(o["expanded"] for o in expected)
+    assert stats["solved"] == sum(1 for inst, o in zip(insts, expected) if o["n_planned"] == len(inst["starts"]))
+
+
+@pytest.mark.parametrize("schedule", sorted(SIPP_SCHEDULES))
+def test_prioritized_sipp_schedules_match_the_oracle(cpu_solver, ref_tests, sipp_instances, sipp_expected, monkeypatch, schedule):
+    for k, v in SIPP_SCHEDULES[schedule].items():
+        monkeypatch.setenv(k, v)
+    res, stats = cpu_solver.prioritized_sipp(sipp_instances)
+    _assert_sipp_answers(res, stats, sipp_instances, sipp_expected)
+    exp = ref_tests["prioritized_sipp"]
+    names = list(exp["cost"])
+    assert [r["cost"] for r in res[:len(names)]] == [exp["cost"][n] for n in names]
+    b = res[names.index("mapf_simple1b")]
+    assert len(b["schedules"][0]) == exp["simple1b_lens"]["agent0"] and len(b["schedules"][1]) == 0
+
+
+@pytest.mark.parametrize("knobs", [{"MRP_MOCK_BUSY": "1"}, {"MRP_MOCK_SHUFFLE": "3"}, {"MRP_HL_SIPP_WGS": "1", "MRP_HL_SIPP_TIMING": "1"}],
+                         ids=["busy1", "shuffle3", "wgs1_timing"])
+def test_prioritized_sipp_session_with_a_full_ring_and_scrambled_completions(cpu_solver, sipp_instances, sipp_expected,
+                                                                             monkeypatch, knobs):
+    for k, v in knobs.items():
+        monkeypatch.setenv(k, v)
+    res, stats = cpu_solver.prioritized_sipp(sipp_instances)
+    _assert_sipp_answers(res, stats, sipp_instances, sipp_expected)
+
+
+def test_prioritized_sipp_batch_schedule_in_two_halves(oracle_mod, cpu_solver, monkeypatch):
+    """MRP_HL_SIPP_BATCH with two tickets per engine and at least 64 instances on it: the instances go in two halves that
+    take turns (runSippGroup)."""
+    from libmultirobotplanning_amd import hl
+    insts = [hl.generate_instance(6400 + k, 8, 8, 12, 8 + k % 3) for k in range(64)]
+    expected = [oracle_mod.prioritized_sipp(inst) for inst in insts]
+    monkeypatch.setenv("MRP_HL_TICKETS", "2")
+    monkeypatch.setenv("MRP_HL_SIPP_BATCH", "1")
+    s = hl.BatchSolver(device=0, n_threads=1, _lib_path=os.path.join(BUILD, "libmrp_hl_cpu.so"))
+    try:
+        res, stats = s.prioritized_sipp(insts)
+    finally:
+        s.close()
+    _assert_sipp_answers(res, stats, insts, expected)
+
+
+@pytest.mark.parametrize("schedule", sorted(SIPP_SCHEDULES))
+def test_prioritized_sipp_capacity_status_is_per_instance_on_the_mock(cpu_solver, sipp_instances, sipp_expected, monkeypatch,
+                                                                      schedule):
+    """test_hl_parity_gpu.py's test of the same name, on the CPU: a search that hits the expansion cap stops ITS instance —
+    status says which, the agents planned before it keep the reference's schedules — and no other.  The cap comes from the
+    oracle's own per-search expansion counts, so that some instances stop and others do not."""
+    from libmultirobotplanning_amd import ll
+    largest = sorted(max(o["agent_expanded"]) for o in sipp_expected)
+    cap = largest[len(largest) // 2]
+    assert 0 < cap and largest[0] <= cap < largest[-1]
+    for k, v in SIPP_SCHEDULES[schedule].items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.setenv("MRP_HL_SIPP_MAX_EXPANSIONS", str(cap))
+    res, _ = cpu_solver.prioritized_sipp(sipp_instances)
+    stopped = 0
+    for i, (r, o) in enumerate(zip(res, sipp_expected)):
+        first_capped = next((a for a, e in enumerate(o["agent_expanded"]) if e > cap), None)
+        if r["status"] == 0:
+            assert first_capped is None, i
+            assert (r["cost"], r["planned"], r["schedules"]) == (o["cost"], o["planned"], o["schedules"]), i
+            continue
+        stopped += 1
+        assert r["status"] == ll.CAP_EXPANSIONS
+        # the prefix planned before the capped search — the first one the oracle needed more than `cap` expansions for — is
+        # the reference's; nothing is planned from it on
+        k = first_capped
+        assert k is not None, i
+        assert r["planned"][:k] == o["planned"][:k] and r["planned"][k:] == [0] * (len(r["planned"]) - k)
+        assert r["schedules"][:k] == o["schedules"][:k] and r["schedules"][k:] == [[]] * (len(r["planned"]) - k)
+        assert r["n_planned"] == sum(o["planned"][:k])
+    assert 0 < stopped < len(sipp_instances)
