@@ -87,7 +87,13 @@ extern "C" {
                            /* device: mrp_ll_compute_heuristics), Wait costs 0 at the goal, so g != time and decrease-key is live. */
                            /* Two tiers, like the other searches: the LDS tier (maps up to 32 x 32, at most 64 vertex and  */
                            /* 64 edge constraints, time steps <= 61, f <= 254, 1023 open nodes) and, for everything beyond */
-                           /* it, the arena tier (any map the context accepts, any number of constraints; limits:           */
+                           /* it, the arena tier.  "Time steps <= 61" is about the nodes the tier EXPANDS: a node that ends   */
+                           /* the search is popped, not expanded, so a solution whose last state has time 62 (63 states)     */
+                           /* still finishes in the LDS tier, one with time 63 does not.  Likewise f and h <= 254 are asked   */
+                           /* of every node the tier generates and of the start, and "1023 open nodes" means: before an       */
+                           /* expansion the open list, the popped node included, has room for five more.  The expansion cap   */
+                           /* is tested first at every pop: a search that ends MRP_LL_CAP_EXPANSIONS there is the tier's own   */
+                           /* answer.  The arena tier takes any map the context accepts, any number of constraints; limits:  */
                            /* mrp_ll_options.arena_nodes / max_horizon — MRP_LL_CAP_NODES / MRP_LL_CAP_HORIZON — and as many */
                            /* time steps as arena_nodes x 4 status words hold: 512 on a 32 x 32 map by default).            */
 
@@ -341,7 +347,8 @@ int mrp_ll_release_maps(mrp_ll_ctx* ctx);
  * (open list, focal list, walk queue, a (time, cell) bitmap of 64 time steps) in a window of fixed size, plus
  * lds_path_bytes for the focal path table of a search (a larger table is read from the search's arena slot); it serves
  * maps up to 32 x 32 and focal contexts of up to 128 agents.  lds_nodes / 2 = open-list entries a search may hold inside
- * the tier (at most 1023), lds_rows = time steps it may use (8 .. 64: a search leaves the tier when it is about to expand a
+ * the tier (at most 1023; lds_nodes is kept as a multiple of 4, rounded DOWN, and at least 8, so the number of entries is
+ * even below 1023: asking for 2 * 485 gives 484), lds_rows = time steps it may use (8 .. 64: a search leaves the tier when it is about to expand a
  * node that is no goal at a time beyond lds_rows - 2, and beyond 61 in any case); a search that outgrows a limit is run by the
  * arena tier instead (a root chain ends in front of it).  0 = keep the current value; lds_nodes < 0 disables the tier.
  * Results never depend on any of this.  *occupancy_out (may be NULL) receives the resident searches per CU (160 KiB / window + table).  MRP_LL_E_BUSY

@@ -89,6 +89,8 @@ def lib():
         _LIB.oracle_ta_ll_search.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, I32P, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, I32P, ctypes.c_int, I32P,
                                              ctypes.c_int64, I32P, I64P, I32P, I32P, I32P, ctypes.c_int]
+        _LIB.oracle_ta_ll_search_counted.restype = ctypes.c_int
+        _LIB.oracle_ta_ll_search_counted.argtypes = _LIB.oracle_ta_ll_search.argtypes + [I64P]
         _LIB.oracle_ta_cbs_fixed.restype = ctypes.c_int64
         _LIB.oracle_ta_cbs_fixed.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, I32P, ctypes.c_int, I32P, I32P, I64P,
                                              I32P, I32P, ctypes.c_int64, I32P]
@@ -369,9 +371,20 @@ def prioritized_sipp_batch(dimx, dimy, obstacles, starts, goals, n_threads=1):
     return out, wall / 1e9
 
 
-def ta_ll_search(inst_map, start, goal, vertex_constraints=(), edge_constraints=(), cap_expansions=-1, cap=1024):
+TA_COUNTERS = ("created", "decrease_keys", "open_at_decrease_key_max", "max_open_at_pop", "max_time_expanded",
+               "max_f_generated", "max_h_generated", "h_start", "reparented_on_path")
+
+
+def ta_ll_search(inst_map, start, goal, vertex_constraints=(), edge_constraints=(), cap_expansions=-1, cap=1024,
+                 counters=False):
     """One low-level search of the task-assignment callers (example/cbs_ta.cpp's Environment under AStar): goal = None for an
-    agent without a task.  Returns success, cost, fmin, expanded, states [t, x, y], actions, action_costs."""
+    agent without a task.  Returns success, cost, fmin, expanded, states [t, x, y], actions, action_costs.
+    counters=True adds the TA_COUNTERS (ta_restated.hpp Counters, taken through the Environment's hooks): created = nodes
+    pushed (the start too); decrease_keys = discoveries of a state discovered before, open_at_decrease_key_max the largest
+    open-list size at one; max_open_at_pop / max_time_expanded = largest open-list size (the popped node counts) / time at
+    the pop of a node that does not end the search (-1: none); max_f_generated / max_h_generated over the newly generated
+    nodes (-1: none); h_start = the table value at the start; reparented_on_path = states of the returned path whose
+    parent was replaced by a decrease-key."""
     obst, obst_p = _i32(np.asarray(inst_map["obstacles"], dtype=np.int32).reshape(-1, 2))
     vc, vc_p = _i32(np.asarray(vertex_constraints, dtype=np.int32).reshape(-1, 3))
     ec, ec_p = _i32(np.asarray(edge_constraints, dtype=np.int32).reshape(-1, 5))
@@ -381,15 +394,20 @@ def ta_ll_search(inst_map, start, goal, vertex_constraints=(), edge_constraints=
     actions = np.zeros(cap, dtype=np.int32)
     costs = np.zeros(cap, dtype=np.int32)
     g = goal if goal is not None else (0, 0)
-    rc = lib().oracle_ta_ll_search(inst_map["dimx"], inst_map["dimy"], len(obst), obst_p, start[0], start[1],
-                                   0 if goal is None else 1, g[0], g[1], len(vc), vc_p, len(ec), ec_p, cap_expansions,
-                                   out.ctypes.data_as(I32P), expanded.ctypes.data_as(I64P), states.ctypes.data_as(I32P),
-                                   actions.ctypes.data_as(I32P), costs.ctypes.data_as(I32P), cap)
+    cnt = np.zeros(len(TA_COUNTERS), dtype=np.int64)
+    rc = lib().oracle_ta_ll_search_counted(inst_map["dimx"], inst_map["dimy"], len(obst), obst_p, start[0], start[1],
+                                           0 if goal is None else 1, g[0], g[1], len(vc), vc_p, len(ec), ec_p, cap_expansions,
+                                           out.ctypes.data_as(I32P), expanded.ctypes.data_as(I64P),
+                                           states.ctypes.data_as(I32P), actions.ctypes.data_as(I32P),
+                                           costs.ctypes.data_as(I32P), cap, cnt.ctypes.data_as(I64P) if counters else None)
     n = int(out[3])
     assert n <= cap
-    return dict(rc=rc, success=bool(out[0]), cost=int(out[1]), fmin=int(out[2]), expanded=int(expanded[0]),
-                states=states[:n].tolist(), actions=actions[:max(n - 1, 0)].tolist(),
-                action_costs=costs[:max(n - 1, 0)].tolist())
+    r = dict(rc=rc, success=bool(out[0]), cost=int(out[1]), fmin=int(out[2]), expanded=int(expanded[0]),
+             states=states[:n].tolist(), actions=actions[:max(n - 1, 0)].tolist(),
+             action_costs=costs[:max(n - 1, 0)].tolist())
+    if counters:
+        r.update(zip(TA_COUNTERS, (int(v) for v in cnt)))
+    return r
 
 
 def ta_cbs_fixed(inst_map, starts, tasks):

@@ -551,9 +551,12 @@ int oracle_sipp_single_counted(int dimx, int dimy, int nObst, const int32_t* obs
 // One AStar::search over example/cbs_ta.cpp's Environment.  hasGoal = 0: the agent has no task (cbs_ta.cpp:283-319).
 // out[0..3] = success, cost, fmin, n_states; statesTXY [cap][3], actions [cap], actionCosts [cap] (Wait at the goal: 0).
 // Returns 0, or -1 when the expansion cap was exceeded.
-int oracle_ta_ll_search(int dimx, int dimy, int nObst, const int32_t* obstXY, int startX, int startY, int hasGoal, int goalX,
-                        int goalY, int nVC, const int32_t* vc, int nEC, const int32_t* ec, int64_t capExpansions,
-                        int32_t* out, int64_t* expanded, int32_t* statesTXY, int32_t* actions, int32_t* actionCosts, int cap) {
+// counters (may be NULL): ta::Counters as int64 words — created, decrease_keys, open_at_decrease_key_max, max_open_at_pop,
+// max_time_expanded, max_f_generated, max_h_generated, h_start, reparented_on_path (oracle.TA_COUNTERS).
+int oracle_ta_ll_search_counted(int dimx, int dimy, int nObst, const int32_t* obstXY, int startX, int startY, int hasGoal,
+                                int goalX, int goalY, int nVC, const int32_t* vc, int nEC, const int32_t* ec,
+                                int64_t capExpansions, int32_t* out, int64_t* expanded, int32_t* statesTXY, int32_t* actions,
+                                int32_t* actionCosts, int cap, int64_t* counters) {
   std::unordered_set<Cell, CellHash> obst;
   for (int i = 0; i < nObst; ++i) obst.insert(Cell{obstXY[2 * i], obstXY[2 * i + 1]});
   Constraints cons;
@@ -563,13 +566,19 @@ int oracle_ta_ll_search(int dimx, int dimy, int nObst, const int32_t* obstXY, in
   ta::Environment env(dimx, dimy, obst);
   const Cell goal{goalX, goalY};
   Plan plan;
+  ta::Counters cnt;
   bool ok = false;
   int rc = 0;
   try {
     ok = ta::lowLevelSearch(env, 0, cons, hasGoal ? &goal : nullptr, obst, dimx, dimy, State(0, startX, startY), plan,
-                            capExpansions);
+                            capExpansions, counters ? &cnt : nullptr);
   } catch (const CapExceeded&) {
     rc = -1;
+  }
+  if (counters) {
+    const long w[9] = {cnt.created, cnt.decreaseKeys, cnt.openAtDecreaseKeyMax, cnt.maxOpenAtPop, cnt.maxTimeExpanded,
+                       cnt.maxFGenerated, cnt.maxHGenerated, cnt.hStart, cnt.reparentedOnPath};
+    for (int k = 0; k < 9; ++k) counters[k] = w[k];
   }
   *expanded = env.m_llExpandedThisSearch;
   out[0] = ok ? 1 : 0;
@@ -587,6 +596,13 @@ int oracle_ta_ll_search(int dimx, int dimy, int nObst, const int32_t* obstXY, in
     }
   }
   return rc;
+}
+
+int oracle_ta_ll_search(int dimx, int dimy, int nObst, const int32_t* obstXY, int startX, int startY, int hasGoal, int goalX,
+                        int goalY, int nVC, const int32_t* vc, int nEC, const int32_t* ec, int64_t capExpansions,
+                        int32_t* out, int64_t* expanded, int32_t* statesTXY, int32_t* actions, int32_t* actionCosts, int cap) {
+  return oracle_ta_ll_search_counted(dimx, dimy, nObst, obstXY, startX, startY, hasGoal, goalX, goalY, nVC, vc, nEC, ec,
+                                     capExpansions, out, expanded, statesTXY, actions, actionCosts, cap, nullptr);
 }
 
 // cbs_ta.hpp:85-215 for ONE fixed assignment (ta::cbsFixedTasks): tasksXY[i] = (-1, -1): agent i has no task.

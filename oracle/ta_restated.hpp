@@ -177,18 +177,53 @@ class Environment {  // cbs_ta.cpp:250-520, the parts a low-level search and a f
   long m_llExpanded = 0;
 };
 
+// What one low-level search did, seen through the two hooks of the adapter below (the search itself is untouched): the
+// figures the device tiers' limits are stated in (tests/ta_tier_cases.py).  "A node that does not end the search": one whose
+// onExpandNode neither trips the expansion cap nor is followed by isSolution — it is popped and expanded.
+struct Counters {
+  long created = 1;                   // nodes pushed, the start included
+  long decreaseKeys = 0;              // onDiscover of a state that had been discovered before (a_star.hpp:139-145)
+  long openAtDecreaseKeyMax = 0;      // the largest open-list size at such an event
+  long maxOpenAtPop = 0;              // the largest open-list size at the pop of a node that does not end the search (it counts)
+  long maxTimeExpanded = -1;          // the largest time of such a node (-1: none)
+  long maxFGenerated = -1;            // the largest f / h of a newly generated node (-1: none), the start not included
+  long maxHGenerated = -1;
+  long hStart = 0;                    // the table value at the start (0 without a task)
+  long reparentedOnPath = 0;  // filled by lowLevelSearch: states of the returned path whose parent was replaced
+  long open = 1;                      // (running) entries of the open list
+  std::unordered_set<State, StateHash> seen, rekeyed;
+};
+
 // cbs_ta.hpp:263-302: the adapter the low-level search is instantiated on (+ the harness's expansion cap)
 struct LLEnv {
   Environment& env;
   long cap;  // < 0: unlimited (expansions of THIS search)
+  Counters* cnt = nullptr;
   int admissibleHeuristic(const State& s) { return env.admissibleHeuristic(s); }
   bool isSolution(const State& s) { return env.isSolution(s); }
   void getNeighbors(const State& s, std::vector<Neighbor<State, Action, int>>& n) { env.getNeighbors(s, n); }
   void onExpandNode(const State& s, int f, int g) {
     env.onExpandLowLevelNode(s, f, g);
     if (cap >= 0 && env.m_llExpandedThisSearch > cap) throw mapf::CapExceeded();
+    if (cnt && !env.isSolution(s)) {  // a_star.hpp:109: this node is popped next
+      cnt->maxOpenAtPop = std::max(cnt->maxOpenAtPop, cnt->open);
+      cnt->maxTimeExpanded = std::max<long>(cnt->maxTimeExpanded, s.time);
+      cnt->open -= 1;
+    }
   }
-  void onDiscover(const State&, int, int) {}
+  void onDiscover(const State& s, int f, int g) {
+    if (!cnt) return;
+    if (cnt->seen.insert(s).second) {  // a_star.hpp:120-129
+      cnt->created += 1;
+      cnt->open += 1;
+      cnt->maxFGenerated = std::max<long>(cnt->maxFGenerated, f);
+      cnt->maxHGenerated = std::max<long>(cnt->maxHGenerated, f - g);
+    } else {                           // a_star.hpp:139-145
+      cnt->decreaseKeys += 1;
+      cnt->openAtDecreaseKeyMax = std::max(cnt->openAtDecreaseKeyMax, cnt->open);
+      cnt->rekeyed.insert(s);
+    }
+  }
 };
 
 struct LowLevelCall {  // recorder entry: one search with everything it saw and returned
@@ -204,14 +239,22 @@ struct LowLevelCall {  // recorder entry: one search with everything it saw and 
 // One low-level search of the task-assignment callers (cbs_ta.hpp:106-109,156-158,196-199).
 inline bool lowLevelSearch(Environment& env, std::size_t agent, const Constraints& c, const Cell* task,
                            const std::unordered_set<Cell, CellHash>& obstacles, int dimx, int dimy, const State& start,
-                           Plan& out, long cap = -1) {
+                           Plan& out, long cap = -1, Counters* cnt = nullptr) {
   std::vector<int> table;
   if (task) table = shortestPathTable(dimx, dimy, obstacles, *task);
   env.setLowLevelContext(agent, &c, task, task ? &table : nullptr);
   env.m_llExpandedThisSearch = 0;
-  LLEnv ll{env, cap};
+  if (cnt) {
+    *cnt = Counters();
+    cnt->hStart = env.admissibleHeuristic(start);
+    cnt->seen.insert(start);
+  }
+  LLEnv ll{env, cap, cnt};
   AStar<State, Action, int, LLEnv, StateHash> search(ll);
-  return search.search(start, out);
+  const bool ok = search.search(start, out);
+  if (ok && cnt)
+    for (const auto& s : out.states) cnt->reparentedOnPath += cnt->rekeyed.count(s.first) ? 1 : 0;
+  return ok;
 }
 
 // cbs_ta.hpp:85-215 for ONE fixed assignment (tasks[i] = nullptr: agent i has no task): best-first conflict tree by cost.

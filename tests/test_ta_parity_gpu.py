@@ -25,9 +25,10 @@ def _bfs(dimx, dimy, obstacles, goal):
     return dist
 
 
-def _run(eng, cases, ids=None):
+def _run(eng, cases, ids=None, tiers=None):
     """cases: (map dict, start, goal or None, vc, ec, cap, oracle result).  One batch through mrp_ll_search_batch.
-    ids: (maps, heuristics) already uploaded to this engine (tables cannot be uploaded during a session)."""
+    ids: (maps, heuristics) already uploaded to this engine (tables cannot be uploaded during a session).
+    tiers: result.tier every case must report (tests/ta_tier_cases.py's rule on the oracle's counters)."""
     from libmultirobotplanning_amd import ll
     maps, heurs = ids if ids is not None else ({}, {})
     jobs = []
@@ -45,6 +46,8 @@ def _run(eng, cases, ids=None):
                              max_expansions=cap, heuristic_id=hid))
     res = eng.search_batch(jobs)
     n = 0
+    if tiers is not None:
+        assert [r.tier for r in res] == list(tiers)
     for (m, s, g, vc, ec, cap, o), r in zip(cases, res):
         # no capacity status: what the LDS tier cannot hold (64 + 64 constraints, 1023 open nodes, t <= 61, maps up to
         # 32 x 32) the arena tier runs — its own limits (mrp_ll_options.arena_nodes / max_horizon: 512 time steps on these
@@ -87,8 +90,10 @@ def test_task_assignment_low_level_on_the_reference_fixtures(oracle_mod, ref_tes
 
 def test_task_assignment_low_level_random_constraint_sets(oracle_mod, bench_instances):
     """Random vertex / edge constraints (up to 90 of each: beyond the 64 keys a wave holds, the arena tier takes over) on
-    shipped 8x8 and 32x32 maps, with and without a task, with expansion caps; batch mode and a session of A* jobs.  Not one
-    capacity status (asserted in _run)."""
+    shipped 8x8 and 32x32 maps, with and without a task, with expansion caps; batch mode and a mixed session.  Not one
+    capacity status (asserted in _run), and every search in the tier the documented rule puts it in: the LDS tier
+    finishes most of them."""
+    import ta_tier_cases as tc
     from libmultirobotplanning_amd import ll
     rng = np.random.default_rng(5)
     cases = []
@@ -110,14 +115,16 @@ def test_task_assignment_low_level_random_constraint_sets(oracle_mod, bench_inst
             dx, dy = [(0, 0), (1, 0), (-1, 0), (0, 1), (0, -1)][int(rng.integers(0, 5))]
             ec.append([int(rng.integers(0, 14)), x, y, x + dx, y + dy])
         cap = int(rng.choice([-1, -1, -1, 25]))
-        cases.append((m, s, goal, vc, ec, cap, oracle_mod.ta_ll_search(m, s, goal, vc, ec, cap_expansions=cap)))
+        cases.append((m, s, goal, vc, ec, cap, oracle_mod.ta_ll_search(m, s, goal, vc, ec, cap_expansions=cap, counters=True)))
+    tiers = [0 if tc.rule(dict(map=m, vc=vc, ec=ec), o, tc.DEFAULT_CFG)[0] == "tier" else 1 for m, _, _, vc, ec, _, o in cases]
+    assert tiers.count(0) >= 100 and tiers[:100].count(0) >= 40 and tiers.count(1) >= 20
     eng = ll.LowLevelEngine(device=0, n_tickets=1, slots=256)
     try:
         ids = ({}, {})
-        assert _run(eng, cases, ids) >= 200
+        assert _run(eng, cases, ids, tiers) >= 200
         eng.session_begin(64)  # (maps and heuristic tables were uploaded before the session)
         try:
-            assert _run(eng, cases[:100], ids) >= 80
+            assert _run(eng, cases[:100], ids, tiers[:100]) >= 80
         finally:
             eng.session_end()
     finally:
