@@ -408,6 +408,14 @@ int mrp_ll_session_begin_tiers_gated(mrp_ll_ctx* ctx, int32_t algo, int32_t work
  * workgroup takes: a caller sizes the pair with 256 CUs x (160 KiB - its share of heavy windows) / front window. */
 int mrp_ll_session_tiers_geometry(mrp_ll_ctx* ctx, int32_t* front_occupancy_out, int32_t* front_lds_bytes_out,
                                   int32_t* heavy_lds_bytes_out);
+/* Where the FRONT workgroups of such a pair keep the focal path table of a search.  in_memory = 0 (a new context): behind
+ * the LDS window when it fits mrp_ll_configure_tiers' lds_path_bytes, which the window is then launched with.  in_memory != 0:
+ * always in the workgroup's arena slot — the window is launched without a table (10 880 bytes for every agent count), the
+ * search reads the two table rows of an expansion with two vector loads, and a root chain's table is bounded by the arena
+ * slot's path area instead of lds_path_bytes.  mrp_ll_session_tiers_geometry then reports that window and what the runtime
+ * grants for it; mrp_ll_session_occupancy, single-launch sessions, batches and the heavy workgroups are not affected.
+ * Results never depend on it.  MRP_LL_E_BUSY while a batch or a session is in flight. */
+int mrp_ll_session_front_tables(mrp_ll_ctx* ctx, int32_t in_memory);
 int mrp_ll_session_end(mrp_ll_ctx* ctx);
 /* Session mode: the same as mrp_ll_submit.  There is one device queue and it is first in, first out; which search
  * starts next is decided by the ORDER in which the caller publishes — keep the queue shallow (about two searches per

@@ -36,6 +36,10 @@
 
 using namespace mrp_hl;
 
+// mrp_ll_session_front_tables through a weak reference, as the constraint store's calls (ct_session.hpp): a low-level
+// library without it still loads, and its front workgroups keep their tables in LDS.
+extern "C" __attribute__((weak)) int mrp_ll_session_front_tables(mrp_ll_ctx* ctx, int32_t in_memory);
+
 struct mrp_hl_preloaded {
   mrp_hl_solver* owner = nullptr;
   int32_t nInst = 0;
@@ -295,6 +299,15 @@ int mrp_hl_solver_solve_stream(mrp_hl_solver* s, const mrp_hl_options* optIn, in
     if (mrp_ll_session_occupancy(s->engines[0], opt.algo == MRP_HL_ECBS ? MRP_LL_ASTAR_EPS : MRP_LL_ASTAR, &occ) == MRP_LL_SUCCESS && occ > 0)
       rep.occupancy = occ;
   }
+  // where the front workgroups keep their focal tables: asked of every engine of this call before the geometry, which
+  // answers for the window that results (an engine without the call — an older one, the CPU tests' stand-in — keeps them in LDS)
+  const bool frontInMemory = in.knobs.frontTables >= 0 ? in.knobs.frontTables != 0 : in.maxAgents <= 64;  // (solve_knobs.hpp)
+  if (tiers.askGeometry && &mrp_ll_session_front_tables != nullptr)
+    for (int32_t t = 0; t < nRun; ++t)
+      if (mrp_ll_session_front_tables(s->engines[t], frontInMemory ? 1 : 0) != MRP_LL_SUCCESS) {
+        s->err = llError("mrp_ll_session_front_tables", s->engines[t]);
+        return MRP_LL_E_DEVICE;
+      }
   if (tiers.askGeometry && mrp_ll_session_tiers_geometry(s->engines[0], &rep.frontOcc, &rep.frontLds, &rep.heavyLds) != MRP_LL_SUCCESS)
     rep.frontOcc = 0;
   Residency res = residency(in, rep);

@@ -25,6 +25,13 @@ struct SolveKnobs {
   bool deviceCons = false;
   int32_t consSlots = -1;  // MRP_HL_CONS_SLOTS: slots of every engine's constraint store (-1 unset: as many as the path store would have)
   int32_t consWords = 64;  // MRP_HL_CONS_WORDS: constraints a slot holds, 1..2048; a larger set ships flat
+  // MRP_HL_FRONT_TABLES=memory|lds (ECBS sessions with heavy workgroups): where the front workgroups keep a search's focal path
+  // table (mrp_ll.h mrp_ll_session_front_tables).  memory: the front window is the same 10 880 bytes for every agent count and
+  // more searches fit a CU, each a little slower; lds: the table behind the window, as the tier choice sized it.  Same results.
+  // Unset (-1): memory up to 64 agents — one pair of row loads per expansion; measured +4 % at ten agents, +4 … 13 % at fifty —,
+  // lds beyond, where a row is two loads wide and the leg is bound by its dependent chains (a hundred agents: -2 … -8 %;
+  // DESIGN.md section 5).
+  int32_t frontTables = -1;
   int32_t workers = 0;     // MRP_HL_WORKERS: worker threads of the call, at least 1 (0 unset: what mrp_hl_solver_create was asked for)
   // ---- how a session worker runs (ct_session.hpp) ----
   // MRP_HL_SPEC=k, speculation width of the conflict-tree machines (ct_solver.hpp).  Default 2: measured on the shipped
@@ -68,6 +75,7 @@ struct SolveKnobs {
     k.deviceCons = num("MRP_HL_DEVICE_CONSTRAINTS", 0) != 0;
     if (isSet("MRP_HL_CONS_SLOTS")) k.consSlots = std::max(0, i32("MRP_HL_CONS_SLOTS", 0));
     k.consWords = std::max(1, std::min(2048, i32("MRP_HL_CONS_WORDS", 64)));
+    if (const char* e = std::getenv("MRP_HL_FRONT_TABLES")) k.frontTables = (e[0] == 'l' || e[0] == 'L' || e[0] == '0') ? 0 : 1;
     if (isSet("MRP_HL_WORKERS")) k.workers = std::max(1, i32("MRP_HL_WORKERS", 0));
     k.specWidth = static_cast<int32_t>(std::max<int64_t>(1, num("MRP_HL_SPEC", 2)));
     k.chainDebug = isSet("MRP_HL_CHAIN_DEBUG");

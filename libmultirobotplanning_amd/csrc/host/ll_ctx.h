@@ -208,6 +208,7 @@ struct mrp_ll_ctx {
   uint32_t maxWpr = 1;
   uint32_t extraHbmWgs = 0;       // session mode: additional resident workgroups without an LDS tier (see Ring::grid2)
   uint32_t tierRows = 64, tierPathBytes = 4096;  // LDS tier geometry (mrp_ll_configure_tiers); nodes live in env.ldsNodes
+  bool frontTablesInMemory = false;  // mrp_ll_session_front_tables: front workgroups keep every focal table in their arena slot
   uint32_t sessionRowWords = 0;   // LDS bitmap row width the resident kernel was launched with
   uint32_t arenaRowWords = 0;
   uint64_t arenaStride = 0;

@@ -180,7 +180,17 @@ int launchFrontHeavy(mrp_ll_ctx* ctx, mrp::LaunchParams& P, uint32_t ldsBytes, i
            std::chrono::duration<double>(std::chrono::steady_clock::now() - tg0).count() < 2.0) {
     }
   }
-  HIPCHK(ctx, mrp_ll_launch_front_heavy(&P, g.grid, ldsBytes, 0, t.stream));
+  int frontKernel = 0;  // (ll_kernel.hip mrp_ll_launch_front_heavy: 0 = the table behind the window, 2 = no table)
+  if (ctx->frontTablesInMemory && P.lds_nodes != 0) {
+    frontKernel = 2;
+    // mrp_ll_session_front_tables: the front window ends behind the obstacle row; every focal table of a front workgroup —
+    // a child's, a root chain's — lives in the path area of its arena slot (ll_jobs.h runJob, runChain), so what bounds a
+    // chain's table is that area and no longer the window (ll_pack.h packJob asks the session)
+    P.lds_paths_bytes = 0;
+    ldsBytes = mrp_ll_lds_bytes(1, P.lds_nodes, P.lds_rows, P.lds_row_words, 0);
+    ctx->env.session.ldsPathBytes = P.arena_paths_bytes;
+  }
+  HIPCHK(ctx, mrp_ll_launch_front_heavy(&P, g.grid, ldsBytes, frontKernel, t.stream));
   HIPCHK(ctx, hipEventRecord(g.ev1, t.stream));
   ctx->stats.launches += 2;
   ctx->env.session.kind = 1;

@@ -458,6 +458,15 @@ DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t*
 // paths of the agents in front of it, the focal table [kChainRows][n_agents_pad] stays in the window between the
 // searches and gains one column per path.  Everything runs in the compact tier; a search that outgrows it ends the chain
 // in front of it.  Written for the A*-epsilon-only kernels (BG window).
+// A launch whose window holds no table (lds_paths_bytes == 0: the front workgroups of mrp_ll_session_front_tables) keeps the
+// chain's table in the path area of its arena slot instead, and the searches read it there (PLDS = false, CJob::pathsG).
+// The rule that rests on is the one the compact tier's (time, cell) bitmap rests on (ll_compact.h, the successor probes): the
+// table is written by THIS wave alone — the fill, the columns of the paths that exist, the column appended after each
+// search, all plain stores — and read by this wave alone, with plain loads; a wave's vector-memory operations reach its
+// CU's L1 in program order and that cache writes through, so a wave's later load of an address sees its own earlier store
+// with no fence and no cache-wide action (the LLVM AMDGPU memory model asks for nothing between a store and a load of one
+// thread in program order).  No other workgroup ever looks at the area, so no scope wider than the wave is involved; the one
+// wait is the compiler's own, in front of the first use of a loaded value.
 DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t* arenaSlot, DevResult& res,
                    uint16_t* outPath, uint16_t* hostOut) {
   constexpr bool BG = true;
@@ -468,7 +477,7 @@ DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
   res.n_states = 0;
   res.expanded = 0;
   if (P.lds_nodes == 0 || J.dimx > 32u || J.dimy > 32u || n > kChainMaxAgents || first >= n || npad < n || npad > 128u ||
-      (npad & 1u) || kChainRows * npad * 2u > P.lds_paths_bytes ||
+      (npad & 1u) || kChainRows * npad * 2u > (P.lds_paths_bytes != 0u ? P.lds_paths_bytes : P.arena_paths_bytes) ||
       (uint64_t)P.arena_nodes * 16u < ct::kParentBytes + ct::kBitsBytes ||
       (uint64_t)n * kChainEntryWords * 2u + (uint64_t)n * 64u > (uint64_t)P.out_host_stride) {
     res.status = ST_BAD;  // (the host packer refuses such a job)
@@ -476,7 +485,9 @@ DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
   }
   const uint32_t* who = P.cons + J.vc_off;   // starts / goals
   const uint32_t* ids = who + n;             // path-store slots
-  uint16_t* table = (uint16_t*)(smem + ldsBytes(0, BG));
+  const bool tabInLds = P.lds_paths_bytes != 0u;
+  uint16_t* table = tabInLds ? (uint16_t*)(smem + ldsBytes(0, BG))
+                             : (uint16_t*)(arenaSlot + P.arena_scratch_off + (size_t)P.out_stride * 2 + (size_t)kConsLocalWords * 4);
   for (uint32_t i = lane; i < kChainRows * npad / 2u; i += 64) ((uint32_t*)table)[i] = 0xFFFFFFFFu;  // nobody anywhere
   __syncthreads();
   for (uint32_t a = 0; a < first; ++a) {  // the paths that exist already: lane = time step
@@ -496,6 +507,10 @@ DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
   bool allOk = true;
   int64_t total = 0;
   for (uint32_t a = first; a < end; ++a) {
+    // (The bases of what a search's results are written through, made opaque once per search: the per-lane addresses behind
+    // them are then built where they are used — two instructions — instead of being kept, which under the front kernel's
+    // 128 VGPRs means spilled and reloaded, across the search.)
+    asm volatile("" : "+s"(hostW), "+s"(outPath));
     const uint32_t sg = rfl(hostLoad32(who + a));
     ct::CJob cj;
     cj.dimx = J.dimx; cj.dimy = J.dimy;
@@ -512,7 +527,7 @@ DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
     cj.rows = 0;
     cj.vc = 0; cj.ec = 0;
     cj.obst = (uint64_t)(P.maps + J.map_word_off);
-    cj.pathsG = 0;
+    cj.pathsG = tabInLds ? 0ull : (uint64_t)table;
     cj.parentTab = (uint64_t)arenaSlot;
     cj.outPath = (uint64_t)outPath;
     cj.bitsG = (uint64_t)(arenaSlot + ct::kParentBytes);
@@ -521,7 +536,7 @@ DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
 #ifndef MRP_LL_TRACE
     const uint64_t tl0 = __builtin_amdgcn_s_memrealtime();
 #endif
-    const int32_t crc = ct::compactSearch<true, true, BG>((wv::Lds)smem);
+    const int32_t crc = tabInLds ? ct::compactSearch<true, true, BG>((wv::Lds)smem) : ct::compactSearch<true, false, BG>((wv::Lds)smem);
     const ct::CRes cr = getCRes(smem);
     const int32_t cost = cr.cost, fmin = cr.fmin, nStates = cr.nStates;
     const uint32_t expanded = cr.expanded;
@@ -562,7 +577,9 @@ DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
         for (uint32_t i = lane; i < len; i += 64) __hip_atomic_store(slot + 1 + i, outPath[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(slot, (uint16_t)len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
-      table[lane * npad + a] = outPath[lane < len ? lane : len - 1];
+      uint32_t rowLen = npad;  // (opaque likewise: lane * npad is computed here, not kept across the search)
+      asm volatile("" : "+s"(rowLen));
+      table[lane * rowLen + a] = outPath[lane < len ? lane : len - 1];
     }
     if (budget >= 0) budget = budget > (int64_t)expanded ? budget - (int64_t)expanded : 0;  // Instance::remainingLL()
   }
@@ -581,20 +598,43 @@ DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
   // (t, vertex before edge, i, j).  Seven instances in ten of the ten-agent workload end here: HL 1, no conflict.
   if (first == 0 && end == n && done == n && allOk && maxLen >= 1u && maxLen <= kChainRows) {
     const uint32_t T = maxLen - 1u;  // <= 62
-    const bool inT = lane < T;
-    const uint32_t rowC = lane * npad, rowN = (lane + 1u < kChainRows ? lane + 1u : kChainRows - 1u) * npad;
-    uint32_t cnt = 0, bestV = 0xFFFFu, bestE = 0xFFFFu;  // this lane's (time step's) first vertex / edge pair: i << 8 | j
-    for (uint32_t i = 0; i + 1u < n; ++i) {
-      const uint32_t ci = table[rowC + i], ni = table[rowN + i];
-      for (uint32_t j = i + 1u; j < n; ++j) {
-        const uint32_t cj = table[rowC + j], nj = table[rowN + j];
-        const bool v = inT && ci == cj, e = inT && ci == nj && ni == cj;
-        cnt += (v ? 1u : 0u) + (e ? 1u : 0u);
-        if (v && bestV == 0xFFFFu) bestV = (i << 8) | j;
-        if (e && bestE == 0xFFFFu) bestE = (i << 8) | j;
+    uint32_t cnt = 0, key = 0x7FFFFFFFu;  // this lane's conflicts, and its first one: t << 24 | edge << 16 | i << 8 | j
+    // the pairs of time step t, whose row and the next one are tab[rowC ..] and tab[rowN ..] (inT: this lane has a time step)
+    auto pairsOf = [&](const uint16_t* tab, uint32_t rowC, uint32_t rowN, uint32_t t, bool inT) {
+      uint32_t bestV = 0xFFFFu, bestE = 0xFFFFu;  // the time step's first vertex / edge pair: i << 8 | j
+      for (uint32_t i = 0; i + 1u < n; ++i) {
+        const uint32_t ci = tab[rowC + i], ni = tab[rowN + i];
+        for (uint32_t j = i + 1u; j < n; ++j) {
+          const uint32_t cj = tab[rowC + j], nj = tab[rowN + j];
+          const bool v = inT && ci == cj, e = inT && ci == nj && ni == cj;
+          cnt += (v ? 1u : 0u) + (e ? 1u : 0u);
+          if (v && bestV == 0xFFFFu) bestV = (i << 8) | j;
+          if (e && bestE == 0xFFFFu) bestE = (i << 8) | j;
+        }
+      }
+      const uint32_t k = bestV != 0xFFFFu ? (t << 24) | bestV : bestE != 0xFFFFu ? (t << 24) | (1u << 16) | bestE : 0x7FFFFFFFu;
+      key = k < key ? k : key;
+    };
+    if (tabInLds) {
+      pairsOf(table, lane * npad, (lane + 1u < kChainRows ? lane + 1u : kChainRows - 1u) * npad, lane, lane < T);
+    } else {
+      // The table is in device memory: its rows come into the window's open and focal areas — free after the last search,
+      // 8 KB — with coalesced 4-byte loads, as many rows as fit, and a pass looks at the time steps whose row and next row it
+      // holds: ONE pass up to 64 agents (64 rows of 128 bytes), two at 128 (rows 0 .. 31, then 31 .. 62).  A time step belongs
+      // to one lane of one pass, so the count and the smallest key are what the single pass over a table in the window gives.
+      uint16_t* stage = (uint16_t*)(smem + ct::oOpen);
+      static_assert(2u * ct::kHeapBytes >= 32u * kChainMaxAgents * 2u, "room for 32 rows of the widest table");
+      const uint32_t rowsFit = 2u * ct::kHeapBytes / (npad * 2u) < kChainRows ? 2u * ct::kHeapBytes / (npad * 2u) : kChainRows;  // >= 32
+      for (uint32_t r0 = 0; r0 < T; r0 += rowsFit - 1u) {
+        const uint32_t nRows = kChainRows - r0 < rowsFit ? kChainRows - r0 : rowsFit;  // rows r0 .. r0 + nRows - 1 (r0 < T <= 62: >= 2)
+        __syncthreads();
+        for (uint32_t i = lane; i < nRows * npad / 2u; i += 64) ((uint32_t*)stage)[i] = ((const uint32_t*)table)[r0 * npad / 2u + i];
+        __syncthreads();
+        const bool inT = lane + 1u < nRows && r0 + lane < T;
+        const uint32_t row = inT ? lane : 0u;
+        pairsOf(stage, row * npad, (row + 1u) * npad, r0 + lane, inT);
       }
     }
-    uint32_t key = bestV != 0xFFFFu ? (lane << 24) | bestV : bestE != 0xFFFFu ? (lane << 24) | (1u << 16) | bestE : 0x7FFFFFFFu;
 #pragma unroll
     for (uint32_t off = 32; off >= 1; off >>= 1) {
       cnt += (uint32_t)__shfl_xor((int)cnt, (int)off, 64);

@@ -19,7 +19,7 @@
 //   ll_ta.h            TaEnv, runTaArena / runJobTA, runJobTaEps: the task-assignment low levels
 //   ll_sipp.h          SIPP: its tiers, sippLoop, runSipp, processSippJob
 //   ll_node_scan.h     nodeScan: the conflicts of the conflict-tree node a search has completed (also compiled for the CPU)
-//   here               scanNode, processJob, batchLoop, publishDone, residentLoop, the ten kernels, the launchers
+//   here               scanNode, processJob, batchLoop, publishDone, residentLoop, the eleven kernels, the launchers
 //
 // Reference semantics implemented (file:line in the reference project, libMultiRobotPlanning):
 //   AStarEpsilon::search   include/libMultiRobotPlanning/a_star_epsilon.hpp:86-285
@@ -452,22 +452,25 @@ extern "C" __global__ void __launch_bounds__(64) mrp_ll_ecbs_persistent_kernel(L
 // with the narrow compact tier alone — no arena-tier code, hence a smaller register allocation; heavy workgroups wait on
 // the device-side queue the front ones fill, run each search in the WIDE compact geometry (31.4 KB of LDS: open and focal
 // lists of 3071 entries, walk queue) and, beyond even that, in the arena tier.
-// (MRP_LL_FRONT_WAVES4: at most 128 VGPRs = four waves per SIMD; the searches' own function needs 118, what is spilled is
-// state of the job set-up and of the chain's conflict scan)
-#ifdef MRP_LL_FRONT_WAVES4
-#define MRP_LL_FRONT_ATTR __attribute__((amdgpu_waves_per_eu(4, 4)))
-#else
-#define MRP_LL_FRONT_ATTR
-#endif
-extern "C" __global__ void __launch_bounds__(64) MRP_LL_FRONT_ATTR mrp_ll_ecbs_front_kernel(LaunchParams Parg) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  MRP_LL_WINDOW_BLOCKS(smem, jobS, resS);
-  const LaunchParams& P = Parg;
-  // "the front launch runs" (the host turns a launch that never starts — streams sharing a hardware queue with a resident
-  // kernel — into an error instead of a hang): the last alive word
-  if (blockIdx.x == 0) hostStore32(P.heavy_alive + (kRingSlots - 1u), 1u);
-  residentLoop<false, 1, kTiersFront>(P, smem, jobS, resS);
-}
+// Two builds of the front kernel.  mrp_ll_ecbs_front_kernel is the compiler's own allocation (153 VGPRs, three waves per
+// SIMD = twelve per CU): the launch whose window holds a path table, which LDS caps at twelve per CU or fewer anyway.
+// mrp_ll_ecbs_front4_kernel is held to 128 VGPRs = four waves per SIMD, sixteen per CU, so that registers do not cap the
+// fourteen 10 880-byte windows of a launch WITHOUT a table (mrp_ll_session_front_tables); the searches' own function needs
+// 118 and is a call, what is spilled is state of the job set-up and of the chain's conflict scan.  Measured with the table in
+// the window, the four-wave build runs an expansion 1.5-2 % slower than the other: each mode keeps
+// the build that suits it.
+#define MRP_LL_FRONT_KERNEL(NAME, ATTR)                                                                                  \
+  extern "C" __global__ void __launch_bounds__(64) ATTR NAME(LaunchParams Parg) {                                        \
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];                                                       \
+    MRP_LL_WINDOW_BLOCKS(smem, jobS, resS);                                                                              \
+    const LaunchParams& P = Parg;                                                                                        \
+    /* "the front launch runs" (the host turns a launch that never starts - streams sharing a hardware queue with a  */ \
+    /* resident kernel - into an error instead of a hang): the last alive word                                        */ \
+    if (blockIdx.x == 0) hostStore32(P.heavy_alive + (kRingSlots - 1u), 1u);                                             \
+    residentLoop<false, 1, kTiersFront>(P, smem, jobS, resS);                                                            \
+  }
+MRP_LL_FRONT_KERNEL(mrp_ll_ecbs_front_kernel, )
+MRP_LL_FRONT_KERNEL(mrp_ll_ecbs_front4_kernel, __attribute__((amdgpu_waves_per_eu(4, 4))))
 
 // Exit conditions every wave reaches: the stop flag (its device mirror, written by the front workgroup that polls the
 // host, or the host word itself, looked at every ~0.5 ms), or a host heartbeat that stood still for ring_idle_limit_s.
@@ -545,16 +548,16 @@ extern "C" __global__ void __launch_bounds__(64) mrp_ll_sipp_persistent_kernel(L
 // The CBS / ECBS kernels by role and kind (0 = mixed, 1 = A*-epsilon jobs only, 2 = A* jobs only, see processJob; the front /
 // heavy pair exists for kind 1 alone).  `slot` numbers the kernel for allowFullLds.
 typedef void (*Kern)(LaunchParams);
-enum Role : int { kBatch = 0, kResident = 1, kFront = 2, kHeavy = 3 };
+enum Role : int { kBatch = 0, kResident = 1, kFront = 2, kHeavy = 3, kFront4 = 4 };
 struct KernelRef {
   Kern fn;
   int slot;
 };
 static KernelRef kernelFor(Role role, int kind) {
-  static const Kern table[8] = {mrp_ll_search_kernel,     mrp_ll_ecbs_search_kernel,     mrp_ll_cbs_search_kernel,
+  static const Kern table[9] = {mrp_ll_search_kernel,     mrp_ll_ecbs_search_kernel,     mrp_ll_cbs_search_kernel,
                                 mrp_ll_persistent_kernel, mrp_ll_ecbs_persistent_kernel, mrp_ll_cbs_persistent_kernel,
-                                mrp_ll_ecbs_front_kernel, mrp_ll_ecbs_heavy_kernel};
-  const int slot = role == kFront ? 6 : role == kHeavy ? 7 : 3 * role + (kind == 1 || kind == 2 ? kind : 0);
+                                mrp_ll_ecbs_front_kernel, mrp_ll_ecbs_heavy_kernel,      mrp_ll_ecbs_front4_kernel};
+  const int slot = role == kFront ? 6 : role == kHeavy ? 7 : role == kFront4 ? 8 : 3 * role + (kind == 1 || kind == 2 ? kind : 0);
   return KernelRef{table[slot], slot};
 }
 
@@ -563,7 +566,7 @@ static KernelRef kernelFor(Role role, int kind) {
 // launches through here, and the attribute is per device.
 static hipError_t allowFullLds(const KernelRef& k) {
   static std::mutex mu;
-  static bool done[8][64] = {};
+  static bool done[9][64] = {};
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
@@ -611,17 +614,20 @@ extern "C" int mrp_ll_persistent_occupancy(int kind, uint32_t ldsBytes) {
   return mrp::occupancyOf(mrp::kernelFor(mrp::kResident, kind), ldsBytes);
 }
 
-// The front / heavy pair (kind 1 sessions with heavy workgroups): `heavy` = false launches the front workgroups with the
-// narrow window of `ldsBytes`, true the heavy ones with the wide window.
+// The front / heavy pair (kind 1 sessions with heavy workgroups).  `heavy`: 0 = the front workgroups with the narrow window
+// and the table behind it (`ldsBytes`), 1 = the heavy ones with the wide window, 2 = the front workgroups of a launch whose
+// window holds no table (the four-wave build of the kernel).
 extern "C" uint32_t mrp_ll_heavy_lds_bytes(void) { return mrp::ct::Wide::windowBytes(true); }
+static mrp::KernelRef frontHeavyKernel(int heavy) {
+  return mrp::kernelFor(heavy == 1 ? mrp::kHeavy : heavy == 2 ? mrp::kFront4 : mrp::kFront, 1);
+}
 extern "C" hipError_t mrp_ll_launch_front_heavy(const mrp::LaunchParams* P, uint32_t grid, uint32_t ldsBytes, int heavy,
                                                 hipStream_t stream) {
-  return mrp::launchWithLds(mrp::kernelFor(heavy ? mrp::kHeavy : mrp::kFront, 1), P, grid,
-                            heavy ? mrp_ll_heavy_lds_bytes() : ldsBytes, stream);
+  return mrp::launchWithLds(frontHeavyKernel(heavy), P, grid, heavy == 1 ? mrp_ll_heavy_lds_bytes() : ldsBytes, stream);
 }
-// Resident workgroups per CU of the front kernel (`heavy` = 0) / the heavy kernel alone (0 on error).
+// Resident workgroups per CU of that kernel alone (0 on error).
 extern "C" int mrp_ll_front_heavy_occupancy(int heavy, uint32_t ldsBytes) {
-  return mrp::occupancyOf(mrp::kernelFor(heavy ? mrp::kHeavy : mrp::kFront, 1), heavy ? mrp_ll_heavy_lds_bytes() : ldsBytes);
+  return mrp::occupancyOf(frontHeavyKernel(heavy), heavy == 1 ? mrp_ll_heavy_lds_bytes() : ldsBytes);
 }
 
 // The SIPP kernels' LDS is static: no attribute to set.

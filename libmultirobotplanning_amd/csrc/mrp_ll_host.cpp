@@ -178,15 +178,23 @@ int mrp_ll_session_tiers_geometry(mrp_ll_ctx* ctx, int32_t* frontOcc, int32_t* f
   if (!ctx) return MRP_LL_E_INVALID;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const uint32_t rowWords = (ctx->maxWpr + 3u) & ~3u;
+  // (mrp_ll_session_front_tables: the front window holds no table)
   const uint32_t bytes = mrp_ll_lds_bytes(1, static_cast<uint32_t>(ctx->env.ldsNodes), ctx->tierRows, rowWords,
-                                          ctx->env.ldsNodes ? ctx->tierPathBytes : 0);
+                                          ctx->env.ldsNodes && !ctx->frontTablesInMemory ? ctx->tierPathBytes : 0);
   if (frontOcc) {
-    int occ = mrp_ll_front_heavy_occupancy(0, bytes);
+    int occ = mrp_ll_front_heavy_occupancy(ctx->env.ldsNodes && ctx->frontTablesInMemory ? 2 : 0, bytes);
     if (occ <= 0) occ = occupancyByLds(bytes + 256u);
     *frontOcc = std::min(occ, 16);
   }
   if (frontLds) *frontLds = static_cast<int32_t>(bytes);
   if (heavyLds) *heavyLds = static_cast<int32_t>(mrp_ll_heavy_lds_bytes());
+  return MRP_LL_SUCCESS;
+}
+
+int mrp_ll_session_front_tables(mrp_ll_ctx* ctx, int32_t inMemory) {
+  if (!ctx) return MRP_LL_E_INVALID;
+  if (engineBusy(ctx)) return MRP_LL_E_BUSY;
+  ctx->frontTablesInMemory = inMemory != 0;
   return MRP_LL_SUCCESS;
 }
 

@@ -80,7 +80,7 @@ EXPORTS = ["mrp_ll_create", "mrp_ll_destroy", "mrp_ll_last_error", "mrp_ll_uploa
            "mrp_ll_upload_heuristic", "mrp_ll_session_begin_tiers", "mrp_ll_session_tiers_geometry",
            "mrp_ll_session_begin_tiers_gated", "mrp_ll_submit_tagged", "mrp_ll_poll_any_tagged",
            "mrp_ll_compute_heuristics", "mrp_ll_read_heuristic", "mrp_ll_heuristic_lookup", "mrp_ll_submit_scan",
-           "mrp_ll_constraint_store_reserve", "mrp_ll_submit_sets"]
+           "mrp_ll_constraint_store_reserve", "mrp_ll_submit_sets", "mrp_ll_session_front_tables"]
 
 _lib = None
 
@@ -125,6 +125,8 @@ def load_library(path: Optional[str] = None):
     lib.mrp_ll_session_begin_tiers.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
     lib.mrp_ll_session_tiers_geometry.restype = ctypes.c_int
     lib.mrp_ll_session_tiers_geometry.argtypes = [ctypes.c_void_p, I32P, I32P, I32P]
+    lib.mrp_ll_session_front_tables.restype = ctypes.c_int
+    lib.mrp_ll_session_front_tables.argtypes = [ctypes.c_void_p, ctypes.c_int32]
     lib.mrp_ll_session_end.restype = ctypes.c_int
     lib.mrp_ll_session_end.argtypes = [ctypes.c_void_p]
     lib.mrp_ll_poll.restype = ctypes.c_int
@@ -486,6 +488,17 @@ class LowLevelEngine:
         occ = ctypes.c_int32(0)
         self._check(self._lib.mrp_ll_session_occupancy(self._h, algo, ctypes.byref(occ)), "mrp_ll_session_occupancy")
         return occ.value
+
+    def session_front_tables(self, in_memory: bool) -> None:
+        """mrp_ll_session_front_tables: the front workgroups of a front / heavy session keep focal tables in device memory."""
+        self._check(self._lib.mrp_ll_session_front_tables(self._h, 1 if in_memory else 0), "mrp_ll_session_front_tables")
+
+    def session_tiers_geometry(self):
+        """mrp_ll_session_tiers_geometry: (front workgroups per CU, front window bytes, heavy window bytes)."""
+        occ, front, heavy = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        self._check(self._lib.mrp_ll_session_tiers_geometry(self._h, ctypes.byref(occ), ctypes.byref(front), ctypes.byref(heavy)),
+                    "mrp_ll_session_tiers_geometry")
+        return occ.value, front.value, heavy.value
 
     def configure_tiers(self, lds_nodes: int = 0, lds_rows: int = 0, lds_path_bytes: int = 0) -> int:
         """Geometry of the LDS fast tier for the launches that follow (0 = keep); returns resident searches per CU."""
