@@ -19,7 +19,7 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-f
 
 TARGETS = {
     "libmrp_ll.so": dict(srcs=["ll_kernel.hip", "conflict_kernel.hip", "heur_kernel.hip", "mrp_ll_host.cpp"],
-                         deps=["ll_device.h", "ll_compact.h", "ll_arena_heap.h", "ll_arena_search.h", "ll_jobs.h", "ll_ta.h",
+                         deps=["ll_device.h", "ll_slot.h", "ll_compact.h", "ll_arena_heap.h", "ll_arena_search.h", "ll_jobs.h", "ll_ta.h",
                                "ll_sipp.h", "ll_node_scan.h", "wave_dev.h", "wave_dev_bool.h", "heur_bfs.h", "heur_layout.h",
                                "ll_launch.h", "host/ll_pack.h", "host/ll_sipp_table.h", "host/ll_unpack.h", "host/ll_ctx.h",
                                "host/ll_maps.h", "host/ll_heur_host.h", "host/ll_stores.h", "host/ll_batch.h",

@@ -140,7 +140,7 @@ struct LaunchParams {
   uint8_t* arena;             // HBM tier: per resident workgroup `arena_stride` bytes
   uint64_t arena_stride;
   uint32_t queue_base;
-  uint32_t arena_scratch_off; // byte offset inside a slot of [path out][constraint copy][path-table copy]
+  uint32_t arena_scratch_off; // byte offset of a slot's scratch tail (ll_slot.h: the slot's byte map, outPath / consCopy / pathsCopy)
   uint32_t arena_paths_bytes; // capacity of the path-table copy in the arena slot
   uint32_t lds_paths_bytes;   // capacity of the path-table copy in LDS
   uint32_t n_jobs;

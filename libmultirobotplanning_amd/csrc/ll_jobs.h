@@ -1,8 +1,9 @@
 // From a job descriptor to a search: the LDS window's size, the host / path-store access helpers (hostLoad32, hostStore32,
-// storeLoad), job staging shared by all searches (stageConstraints, fillCtx, putCJob / getCRes), the arena slot's cut
-// (cutHeaps, cutArena), and the two CBS / ECBS job runners: runJob (compact tier, then arena tier) and runChain (the root
-// chain of an ECBS conflict tree).
-// Needs ll_compact.h (ct::), ll_arena_heap.h and ll_arena_search.h.
+// storeLoad), job staging shared by all searches (stageConstraints, fillCtx, baseCJob, putCJob / getCRes), the arena slot's
+// cut (cutHeaps, cutArena, compactFits), and the two CBS / ECBS job runners: runJob (stageFocalTable, compactAttempt, then
+// arenaAttempt) and runChain (the root chain of an ECBS conflict tree), with what they share with the other job loops
+// (publishPath, beginJob / endJob).
+// Needs ll_slot.h (slot::), ll_compact.h (ct::), ll_arena_heap.h and ll_arena_search.h.
 #ifndef MRP_LL_JOBS_H
 #define MRP_LL_JOBS_H
 
@@ -156,9 +157,27 @@ DEVI uint8_t* cutHeaps(Mem<TierHbm>& g, uint8_t* p, uint32_t cap) {
 DEVI Mem<TierHbm> cutArena(const LaunchParams& P, uint8_t* arenaSlot) {
   Mem<TierHbm> g = {};
   g.nodes = (Mem<TierHbm>::PN32)arenaSlot;
-  g.bits = (Mem<TierHbm>::P32)cutHeaps(g, arenaSlot + (size_t)P.arena_nodes * 16, P.arena_nodes);
+  g.bits = (Mem<TierHbm>::P32)cutHeaps(g, arenaSlot + slot::nodeBytes(P.arena_nodes), P.arena_nodes);
   g.capRows = P.arena_rows; g.rowWords = P.arena_row_words;
   return g;
+}
+// The compact tiers' claim on the slot's node area, free while a search is in them: the cameFrom table of geometry Geo for
+// `rows` time steps (the narrow geometry: always its own kRows) at offset 0 and, BG, the (time, cell) bitmap behind it.
+template <class Geo>
+DEVI bool compactFits(uint32_t arenaNodes, uint32_t rows, bool bg) {
+  return slot::nodeBytes(arenaNodes) >= Geo::parentBytes(rows) + (bg ? Geo::bitsBytes(rows) : 0u);
+}
+// What every compact-tier job takes from the descriptor and the launch: map, budget, narrow limits, the slot's areas as
+// above.  The caller adds start, goal, constraints and focal table, and replaces what differs.
+template <class Geo = ct::Narrow>
+DEVI ct::CJob baseCJob(const LaunchParams& P, const DevJob& J, uint8_t* arenaSlot, uint16_t* outPath, uint32_t rows = 0) {
+  ct::CJob cj;
+  cj.dimx = J.dimx; cj.dimy = J.dimy; cj.w = J.w; cj.obstWords = J.words_per_row;
+  cj.obst = (uint64_t)(P.maps + J.map_word_off);
+  cj.maxExp = clampMaxExp(J.max_expansions);
+  cj.openCap = narrowOpenCap(P); cj.maxT = narrowMaxT(P); cj.taNoGoal = 0; cj.rows = 0;
+  cj.parentTab = (uint64_t)arenaSlot; cj.bitsG = (uint64_t)(arenaSlot + Geo::parentBytes(rows)); cj.outPath = (uint64_t)outPath;
+  return cj;
 }
 
 // Which tiers a kernel carries:
@@ -176,184 +195,150 @@ DEVI bool idTableInLds(const LaunchParams& P, uint32_t pathBytes) {
   return TIERS != kTiersHeavy && P.lds_nodes != 0 && pathBytes <= P.lds_paths_bytes;
 }
 
-// Returns true when the job has to be handed to the heavy workgroups (kTiersFront only).
 // A front workgroup hands these searches over without looking at them (runJob's first test, kTiersFront).
 DEVI bool frontHandsOver(const LaunchParams& P, const DevJob& J) {
   return (J.ctx_flags & kCtxHeavy) != 0 || P.lds_nodes == 0 || J.dimx > 32u || J.dimy > 32u || J.n_agents_pad > 128u || J.n_ec > 64u;
 }
 
-template <bool EPS, bool BG, int TIERS>
-DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t* arenaSlot, DevResult& res,
-                 uint16_t* outPath) {
-  typedef typename std::conditional<TIERS == kTiersHeavy, ct::Wide, ct::Narrow>::type Geo;
+// runJob's first phase: the job's focal path table leaves host memory, or is built from the path store, in one coalesced
+// pass — into `ldsPaths` (behind the LDS window) when it fits there, else into `pathsArena` (the slot's path-table copy).
+// Leaves where the table is in c.paths / c.pathsLds; false: a table named by ids fits nowhere (nothing was written).
+template <int TIERS>
+DEVI bool stageFocalTable(const LaunchParams& P, const DevJob& J, uint8_t* ldsPaths, uint8_t* pathsArena, Ctx& c) {
   constexpr bool kTableMayBeInLds = TIERS != kTiersHeavy;  // the wide window holds no path table
   const uint32_t lane = threadIdx.x;
-  const bool heavyHint = (J.ctx_flags & kCtxHeavy) != 0;
-  if (TIERS == kTiersFront) {
-    // not a search of the narrow tier (the caller says so, or the job's shape does): nothing to set up here
-    if (frontHandsOver(P, J)) return true;
-  }
-  Ctx c;
-  fillCtx(c, J, P.maps, P.debug);
-
-  // ---- bulk-copy the job's constraint words and path table out of host memory (one pass, coalesced) ----
-  uint8_t* scratch = arenaSlot + P.arena_scratch_off;
-  uint32_t* consLocal = (uint32_t*)(scratch + (size_t)P.out_stride * 2);
-  uint8_t* pathsArena = (uint8_t*)(consLocal + kConsLocalWords);
-  if ((J.pad_[0] | J.pad_[2]) != 0u) {  // the union is in the copy area already (processJob, stageConstraintSet)
-    c.vc = consLocal;
-    c.ec = consLocal + c.nVc;
-  } else {
-    stageConstraints(P.cons, J.vc_off, c.nVc, c.nEc, consLocal, c.vc, c.ec);
-  }
-  {
-    const uint32_t pathBytes = c.tPad * c.nAgentsPad * 2;  // multiple of 32
-    const uint32_t* psrc = (const uint32_t*)(P.paths + J.path_off);
-    uint8_t* ldsPaths = smem + Geo::windowBytes(BG);
-    c.pathsLds = nullptr;
-    if (pathBytes != 0 && (J.ctx_flags & kCtxById)) {
-      // f2: the CT node's paths are named by their slots in the device-resident path store (each was written there by
-      // the search that produced it); the time-major table [t][agent] is built here, on the device, instead of being
-      // packed by the host and read over PCIe.  One coalesced read per agent (lane = time step).
-      const bool inLds = idTableInLds<TIERS>(P, pathBytes);
-      if (!inLds && pathBytes > P.arena_paths_bytes) {  // (the host packer refuses such a job; never write past the slot)
-        res.status = ST_BAD;
-        res.expanded = 0;
-        res.nodes_created = 0;
-        return false;
-      }
-      uint16_t* dst = inLds ? (uint16_t*)ldsPaths : (uint16_t*)pathsArena;
-      {
-        uint32_t* d32 = (uint32_t*)dst;
-        for (uint32_t i = lane; i < pathBytes / 4; i += 64) d32[i] = 0xFFFFFFFFu;  // kEmptyCell everywhere
-      }
-      // The slots named here were written by OTHER workgroups of this same resident launch (possibly on another XCD,
-      // whose L2 is not coherent with ours), each before its job's completion was published (processJob writes them in
-      // front of residentLoop's system-scope release).  One agent-scope acquire drops whatever stale copies this CU's L1 /
-      // this XCD's L2 may hold from an earlier use of a recycled slot; after it plain, cached, coalesced loads are
-      // correct (MI355X_MICROARCH.md "Valid forms": poll -> ONE acquire -> s_waitcnt -> barrier -> plain loads).
-#ifdef MRP_LL_STORE_ACQUIRE_FENCE  // A/B: one fence + plain loads instead of agent-scope loads
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-      __syncthreads();
-      const uint32_t* ids = P.cons + J.path_off;
-      const uint32_t nCtx = J.n_ctx;
-      for (uint32_t a0 = 0; a0 < nCtx; a0 += 64) {
-        // this chunk's ids and lengths, one agent per lane (one gather for all lengths)
-        uint32_t idL = kNoStoreSlot, lenL = 0;
-        if (a0 + lane < nCtx) idL = hostLoad32(ids + a0 + lane);
-        if (idL < P.path_store_slots) lenL = storeLoad(P.path_store + (size_t)idL * P.path_store_stride);
-        if (lenL > P.path_store_stride - 1) lenL = P.path_store_stride - 1;
-        const uint32_t nHere = nCtx - a0 < 64 ? nCtx - a0 : 64;
-        if (!inLds) {
-          // Table in the arena (global memory): one lane per AGENT, so that a row of the table is one coalesced store
-          // (a lane per time step would scatter 2-byte stores 2 * n_agents_pad bytes apart — measured on agents100: the
-          // longest conflict-tree chain of a batch a third slower).  The reads gather one cell per slot and stay in L2
-          // from row to row; eight rows are in flight at a time.
-          const uint32_t lenA = lenL;
-          const uint16_t* slotA = P.path_store + (size_t)(idL < P.path_store_slots ? idL : 0) * P.path_store_stride + 1;
-          const bool hasA = idL < P.path_store_slots && lenA != 0;
-          for (uint32_t t0 = 0; t0 < c.tPad; t0 += 8) {
-            uint32_t v[8];
-#pragma unroll
-            for (uint32_t u = 0; u < 8; ++u) {
-              const uint32_t t = t0 + u;
-              v[u] = kEmptyCell;
-              if (hasA && t < c.tPad) v[u] = storeLoad(slotA + (t < lenA ? t : lenA - 1));
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < 8; ++u)
-              if (hasA && t0 + u < c.tPad) dst[(t0 + u) * c.nAgentsPad + a0 + lane] = (uint16_t)v[u];
-          }
-          continue;
-        }
-        // table in LDS: a lane per time step (one coalesced read per agent); eight agents' loads are in flight before
-        // the first store
-        for (uint32_t t0 = 0; t0 < c.tPad; t0 += 64) {
-          const uint32_t t = t0 + lane;
-          for (uint32_t q0 = 0; q0 < nHere; q0 += 8) {
-            uint32_t v[8];
-            bool has[8];
-#pragma unroll
-            for (uint32_t u = 0; u < 8; ++u) {
-              uint32_t id = kNoStoreSlot, len = 0;
-              if (q0 + u < nHere) {
-                id = __builtin_amdgcn_readlane(idL, q0 + u);
-                len = __builtin_amdgcn_readlane(lenL, q0 + u);
-              }
-              has[u] = id < P.path_store_slots && len != 0 && t < c.tPad;  // not: empty path / the searching agent itself
-              v[u] = kEmptyCell;
-              if (has[u]) v[u] = storeLoad(P.path_store + (size_t)id * P.path_store_stride + 1 + (t < len ? t : len - 1));
-            }
-#pragma unroll
-            for (uint32_t u = 0; u < 8; ++u)
-              if (has[u]) dst[t * c.nAgentsPad + a0 + q0 + u] = (uint16_t)v[u];
-          }
-        }
-      }
-      c.paths = dst;
-      if (inLds) c.pathsLds = (__attribute__((address_space(3))) const uint16_t*)ldsPaths;
-    } else if (pathBytes == 0) {
-      c.paths = nullptr;
-    } else if (kTableMayBeInLds && P.lds_nodes != 0 && pathBytes <= P.lds_paths_bytes) {
-      uint32_t* dst = (uint32_t*)ldsPaths;
-      for (uint32_t i = lane; i < pathBytes / 4; i += 64) dst[i] = hostLoad32(psrc + i);
-      c.paths = (const uint16_t*)ldsPaths;
-      c.pathsLds = (__attribute__((address_space(3))) const uint16_t*)ldsPaths;
-    } else if (pathBytes <= P.arena_paths_bytes) {
-      uint32_t* dst = (uint32_t*)pathsArena;
-      for (uint32_t i = lane; i < pathBytes / 4; i += 64) dst[i] = hostLoad32(psrc + i);
-      c.paths = (const uint16_t*)pathsArena;
-    } else {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-      c.paths = P.paths + J.path_off;
+  const uint32_t pathBytes = c.tPad * c.nAgentsPad * 2;  // multiple of 32
+  const uint32_t* psrc = (const uint32_t*)(P.paths + J.path_off);
+  c.pathsLds = nullptr;
+  if (pathBytes != 0 && (J.ctx_flags & kCtxById)) {
+    // f2: the CT node's paths are named by their slots in the device-resident path store (each was written there by
+    // the search that produced it); the time-major table [t][agent] is built here, on the device, instead of being
+    // packed by the host and read over PCIe.  One coalesced read per agent (lane = time step).
+    const bool inLds = idTableInLds<TIERS>(P, pathBytes);
+    if (!inLds && pathBytes > P.arena_paths_bytes) return false;  // (the host packer refuses such a job; never write past the slot)
+    uint16_t* dst = inLds ? (uint16_t*)ldsPaths : (uint16_t*)pathsArena;
+    {
+      uint32_t* d32 = (uint32_t*)dst;
+      for (uint32_t i = lane; i < pathBytes / 4; i += 64) d32[i] = 0xFFFFFFFFu;  // kEmptyCell everywhere
     }
+    // The slots named here were written by OTHER workgroups of this same resident launch (possibly on another XCD,
+    // whose L2 is not coherent with ours), each before its job's completion was published (processJob writes them in
+    // front of residentLoop's system-scope release).  One agent-scope acquire drops whatever stale copies this CU's L1 /
+    // this XCD's L2 may hold from an earlier use of a recycled slot; after it plain, cached, coalesced loads are
+    // correct (MI355X_MICROARCH.md "Valid forms": poll -> ONE acquire -> s_waitcnt -> barrier -> plain loads).
+#ifdef MRP_LL_STORE_ACQUIRE_FENCE  // A/B: one fence + plain loads instead of agent-scope loads
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+    __syncthreads();
+    const uint32_t* ids = P.cons + J.path_off;
+    const uint32_t nCtx = J.n_ctx;
+    for (uint32_t a0 = 0; a0 < nCtx; a0 += 64) {
+      // this chunk's ids and lengths, one agent per lane (one gather for all lengths)
+      uint32_t idL = kNoStoreSlot, lenL = 0;
+      if (a0 + lane < nCtx) idL = hostLoad32(ids + a0 + lane);
+      if (idL < P.path_store_slots) lenL = storeLoad(P.path_store + (size_t)idL * P.path_store_stride);
+      if (lenL > P.path_store_stride - 1) lenL = P.path_store_stride - 1;
+      const uint32_t nHere = nCtx - a0 < 64 ? nCtx - a0 : 64;
+      if (!inLds) {
+        // Table in the arena (global memory): one lane per AGENT, so that a row of the table is one coalesced store
+        // (a lane per time step would scatter 2-byte stores 2 * n_agents_pad bytes apart — measured on agents100: the
+        // longest conflict-tree chain of a batch a third slower).  The reads gather one cell per slot and stay in L2
+        // from row to row; eight rows are in flight at a time.
+        const uint32_t lenA = lenL;
+        const uint16_t* slotA = P.path_store + (size_t)(idL < P.path_store_slots ? idL : 0) * P.path_store_stride + 1;
+        const bool hasA = idL < P.path_store_slots && lenA != 0;
+        for (uint32_t t0 = 0; t0 < c.tPad; t0 += 8) {
+          uint32_t v[8];
+#pragma unroll
+          for (uint32_t u = 0; u < 8; ++u) {
+            const uint32_t t = t0 + u;
+            v[u] = kEmptyCell;
+            if (hasA && t < c.tPad) v[u] = storeLoad(slotA + (t < lenA ? t : lenA - 1));
+          }
+#pragma unroll
+          for (uint32_t u = 0; u < 8; ++u)
+            if (hasA && t0 + u < c.tPad) dst[(t0 + u) * c.nAgentsPad + a0 + lane] = (uint16_t)v[u];
+        }
+        continue;
+      }
+      // table in LDS: a lane per time step (one coalesced read per agent); eight agents' loads are in flight before
+      // the first store
+      for (uint32_t t0 = 0; t0 < c.tPad; t0 += 64) {
+        const uint32_t t = t0 + lane;
+        for (uint32_t q0 = 0; q0 < nHere; q0 += 8) {
+          uint32_t v[8];
+          bool has[8];
+#pragma unroll
+          for (uint32_t u = 0; u < 8; ++u) {
+            uint32_t id = kNoStoreSlot, len = 0;
+            if (q0 + u < nHere) {
+              id = __builtin_amdgcn_readlane(idL, q0 + u);
+              len = __builtin_amdgcn_readlane(lenL, q0 + u);
+            }
+            has[u] = id < P.path_store_slots && len != 0 && t < c.tPad;  // not: empty path / the searching agent itself
+            v[u] = kEmptyCell;
+            if (has[u]) v[u] = storeLoad(P.path_store + (size_t)id * P.path_store_stride + 1 + (t < len ? t : len - 1));
+          }
+#pragma unroll
+          for (uint32_t u = 0; u < 8; ++u)
+            if (has[u]) dst[t * c.nAgentsPad + a0 + q0 + u] = (uint16_t)v[u];
+        }
+      }
+    }
+    c.paths = dst;
+    if (inLds) c.pathsLds = (__attribute__((address_space(3))) const uint16_t*)ldsPaths;
+  } else if (pathBytes == 0) {
+    c.paths = nullptr;
+  } else if (kTableMayBeInLds && P.lds_nodes != 0 && pathBytes <= P.lds_paths_bytes) {
+    uint32_t* dst = (uint32_t*)ldsPaths;
+    for (uint32_t i = lane; i < pathBytes / 4; i += 64) dst[i] = hostLoad32(psrc + i);
+    c.paths = (const uint16_t*)ldsPaths;
+    c.pathsLds = (__attribute__((address_space(3))) const uint16_t*)ldsPaths;
+  } else if (pathBytes <= P.arena_paths_bytes) {
+    uint32_t* dst = (uint32_t*)pathsArena;
+    for (uint32_t i = lane; i < pathBytes / 4; i += 64) dst[i] = hostLoad32(psrc + i);
+    c.paths = (const uint16_t*)pathsArena;
+  } else {
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+    c.paths = P.paths + J.path_off;
   }
-  __syncthreads();
+  return true;
+}
 
-  SState s;
-  int rc = ST_BAD;
-  res.tier = 0;
-
-  // ---- compact tier (ll_compact.h): the whole search in LDS, a state = its 32-bit heap entry.  Maps up to 32 x 32 and
-  // up to 128 agents in the focal context; a search that outgrows the tier (open list, time steps, focalH field) comes
-  // back as C_OVERFLOW with nothing of it observable, and is run again from the start by the next tier.
+// runJob's second phase, the compact tier (ll_compact.h): the whole search in LDS, a state = its 32-bit heap entry.  Maps up
+// to 32 x 32 and up to 128 agents in the focal context; a search that outgrows the tier (open list, time steps, focalH
+// field) comes back as C_OVERFLOW with nothing of it observable, and is run again from the start by the next tier.
+// Returns true when the search ended here: its answer is in rc, res and s.
+template <bool EPS, bool BG, int TIERS>
+DEVI bool compactAttempt(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t* arenaSlot, const Ctx& c, DevResult& res,
+                         uint16_t* outPath, SState& s, int& rc) {
+  typedef typename std::conditional<TIERS == kTiersHeavy, ct::Wide, ct::Narrow>::type Geo;
   // the wide geometry: as many time steps as the arena slot's node area has room for (cameFrom table + bitmap), in
   // chunks of 64, up to the job's horizon
   uint32_t geoRows = Geo::kRows;
   if (TIERS == kTiersHeavy) {
-    const uint64_t room = (uint64_t)P.arena_nodes * 16u / (1024u + ct::kRowBytes);
+    const uint64_t room = slot::nodeBytes(P.arena_nodes) / (1024u + ct::kRowBytes);
     geoRows = (uint32_t)(room < P.arena_rows ? room : P.arena_rows) & ~63u;
   }
-  const bool compactOk = !(TIERS == kTiersAll && heavyHint) && P.lds_nodes != 0 && c.dimx <= 32u && c.dimy <= 32u &&
-                         c.nAgentsPad <= 128u && c.nEc <= 64u && geoRows >= 64u &&
-                         (uint64_t)P.arena_nodes * 16u >= Geo::parentBytes(geoRows) + (BG ? Geo::bitsBytes(geoRows) : 0u);
+  const bool compactOk = !(TIERS == kTiersAll && (J.ctx_flags & kCtxHeavy) != 0) && P.lds_nodes != 0 && c.dimx <= 32u &&
+                         c.dimy <= 32u && c.nAgentsPad <= 128u && c.nEc <= 64u && geoRows >= 64u &&
+                         compactFits<Geo>(P.arena_nodes, geoRows, BG);
   bool done = false;
   if (compactOk) {
-    ct::CJob cj;
-    cj.dimx = c.dimx; cj.dimy = c.dimy; cj.sx = c.sx; cj.sy = c.sy; cj.gx = c.gx; cj.gy = c.gy;
+    ct::CJob cj = baseCJob<Geo>(P, J, arenaSlot, outPath, geoRows);
+    cj.obstWords = c.wpr;  // (the Ctx's copy, live for the arena tier anyway: the descriptor's, read again, costs the all-tier kernels a VGPR)
+    cj.sx = c.sx; cj.sy = c.sy; cj.gx = c.gx; cj.gy = c.gy;
     cj.lastGoal = c.lastGoal;
-    cj.w = c.w;
     cj.nVc = c.nVc; cj.nEc = c.nEc;
-    cj.obstWords = c.wpr;
     cj.nAgentsPad = EPS ? c.nAgentsPad : 0u; cj.tPad = c.tPad;
-    cj.maxExp = clampMaxExp(c.maxExp);
     cj.rows = geoRows;
     if (TIERS == kTiersHeavy) {  // the wide geometry at its full size
       cj.openCap = Geo::kCap;
       cj.maxT = Geo::kMaxT < geoRows - 2u ? Geo::kMaxT : geoRows - 2u;
-    } else {
-      cj.openCap = narrowOpenCap(P);
-      cj.maxT = narrowMaxT(P);
     }
-    cj.taNoGoal = 0;
     cj.vc = (uint64_t)c.vc; cj.ec = (uint64_t)c.ec;
-    cj.obst = (uint64_t)c.obst;
     cj.pathsG = (uint64_t)c.paths;
-    cj.parentTab = (uint64_t)arenaSlot;  // the arena's node area: unused while the search is in this tier
-    cj.outPath = (uint64_t)outPath;
-    cj.bitsG = (uint64_t)(arenaSlot + Geo::parentBytes(geoRows));  // (BG) ... and its (time, cell) bitmap behind it
     putCJob(smem, cj);
     const bool tableInLds = !EPS || c.nAgentsPad == 0u || c.pathsLds != nullptr;
 #ifndef MRP_LL_TRACE  // (the trace build uses prof[] for its phase counters)
@@ -379,11 +364,8 @@ DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t*
 #endif
     if (crc != ct::C_OVERFLOW) {
       rc = crc;  // C_OK / C_NO_SOLUTION / C_CAP_EXP == ST_OK / ST_NO_SOLUTION / ST_CAP_EXP
-      res.cost = cr.cost;
-      res.fmin = cr.fmin;
-      res.n_states = cr.nStates;
-      s.expansions = cr.expanded;
-      s.nNodes = cr.nodes;
+      res.cost = cr.cost; res.fmin = cr.fmin; res.n_states = cr.nStates;
+      s.expansions = cr.expanded; s.nNodes = cr.nodes;
       done = true;
       if (TIERS == kTiersHeavy) res.tier = 2;
     } else {
@@ -393,58 +375,96 @@ DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t*
 #endif
     }
   }
-  if constexpr (TIERS == kTiersFront) {
-    if (!done) return true;  // the heavy workgroups run it from the start
-  } else {
-    if (!done) {
-      // HBM tier view of this workgroup's arena slot
-      const Mem<TierHbm> g = cutArena(P, arenaSlot);
-      // ... and the view the arena tier actually runs on: the same arrays, the heaps' first nTop entries in this
-      // workgroup's LDS (the compact tier's area, free once a search has left it)
-      Mem<TierHyb> gh = viewAs<TierHyb>(g);
-      {
-        const uint32_t area = Geo::windowBytes(BG) - ct::oOpen;  // (the window's control blocks in front of it stay as they are)
-        // the open list gets half of the area, the focal list five sixteenths, the walk queue the rest (MRP_LL_TOPS_EQUAL:
-        // thirds, as before the A*-epsilon kernels' window shrank)
+  return done;
+}
+
+// runJob's third phase, the arena tier: the search from the start with its state in the arena slot (cutArena) and the heaps'
+// top levels in the LDS window.  Returns runSearch's code.
+template <bool EPS, bool BG, int TIERS>
+DEVI int arenaAttempt(const LaunchParams& P, uint8_t* smem, uint8_t* arenaSlot, const Ctx& c, DevResult& res, uint16_t* outPath,
+                      SState& s) {
+  typedef typename std::conditional<TIERS == kTiersHeavy, ct::Wide, ct::Narrow>::type Geo;
+  int rc;
+  // HBM tier view of this workgroup's arena slot
+  const Mem<TierHbm> g = cutArena(P, arenaSlot);
+  // ... and the view the arena tier actually runs on: the same arrays, the heaps' first nTop entries in this
+  // workgroup's LDS (the compact tier's area, free once a search has left it)
+  Mem<TierHyb> gh = viewAs<TierHyb>(g);
+  {
+    const uint32_t area = Geo::windowBytes(BG) - ct::oOpen;  // (the window's control blocks in front of it stay as they are)
+    // the open list gets half of the area, the focal list five sixteenths, the walk queue the rest (MRP_LL_TOPS_EQUAL:
+    // thirds, as before the A*-epsilon kernels' window shrank)
 #ifdef MRP_LL_TOPS_EQUAL
-        const uint32_t perO = (area / 3u) & ~15u, perF = perO, perA = perO;
+    const uint32_t perO = (area / 3u) & ~15u, perF = perO, perA = perO;
 #else
-        const uint32_t perO = (area / 2u) & ~15u, perF = (area * 5u / 16u) & ~15u, perA = (area - perO - perF) & ~15u;
+    const uint32_t perO = (area / 2u) & ~15u, perF = (area * 5u / 16u) & ~15u, perA = (area - perO - perF) & ~15u;
 #endif
-        auto tops = [&](uint32_t per) {
-          uint32_t n = per >= 32u ? ((per - 8u) / 8u) : 0u;
-          if (n > 4095u) n = 4095u;
-          n = n ? ((n - 1u) | 1u) : 0u;  // odd (or 0: no LDS tier configured)
-          return P.lds_nodes == 0 ? 0u : n;
-        };
-        auto l8 = (__attribute__((address_space(3))) uint8_t*)smem + ct::oOpen;
-        gh.open = HybPtr{(__attribute__((address_space(3))) uint64_t*)(l8 + 8), (uint64_t*)g.open, tops(perO)};
-        gh.focal = HybPtr{(__attribute__((address_space(3))) uint64_t*)(l8 + perO + 8), (uint64_t*)g.focal, tops(perF)};
-        gh.aux = HybPtr{(__attribute__((address_space(3))) uint64_t*)(l8 + perO + perF + 8), (uint64_t*)g.aux, tops(perA)};
-      }
-      const bool xyEntries = P.arena_nodes <= 65536u;  // TierHybXy: 16-bit node ids leave room for the cell in the entry
-      Mem<TierHybXy> ghx = viewAs<TierHybXy>(gh);
-      res.tier = 1;
-      __syncthreads();  // previous job's / the compact attempt's LDS accesses are done
-      if (xyEntries)
-        initSearch<TierHybXy, EPS>(ghx, s, c);
-      else
-        initSearch<TierHyb, EPS>(gh, s, c);
-      __syncthreads();
+    auto tops = [&](uint32_t per) {
+      uint32_t n = per >= 32u ? ((per - 8u) / 8u) : 0u;
+      if (n > 4095u) n = 4095u;
+      n = n ? ((n - 1u) | 1u) : 0u;  // odd (or 0: no LDS tier configured)
+      return P.lds_nodes == 0 ? 0u : n;
+    };
+    auto l8 = (__attribute__((address_space(3))) uint8_t*)smem + ct::oOpen;
+    gh.open = HybPtr{(__attribute__((address_space(3))) uint64_t*)(l8 + 8), (uint64_t*)g.open, tops(perO)};
+    gh.focal = HybPtr{(__attribute__((address_space(3))) uint64_t*)(l8 + perO + 8), (uint64_t*)g.focal, tops(perF)};
+    gh.aux = HybPtr{(__attribute__((address_space(3))) uint64_t*)(l8 + perO + perF + 8), (uint64_t*)g.aux, tops(perA)};
+  }
+  const bool xyEntries = P.arena_nodes <= 65536u;  // TierHybXy: 16-bit node ids leave room for the cell in the entry
+  Mem<TierHybXy> ghx = viewAs<TierHybXy>(gh);
+  res.tier = 1;
+  __syncthreads();  // previous job's / the compact attempt's LDS accesses are done
+  if (xyEntries)
+    initSearch<TierHybXy, EPS>(ghx, s, c);
+  else
+    initSearch<TierHyb, EPS>(gh, s, c);
+  __syncthreads();
 #ifndef MRP_LL_TRACE
-      const uint64_t th0 = __builtin_amdgcn_s_memrealtime();
+  const uint64_t th0 = __builtin_amdgcn_s_memrealtime();
 #endif
-      if (xyEntries)
-        rc = runSearch<TierHybXy, EPS>(ghx, s, c, res, outPath);
-      else
-        rc = runSearch<TierHyb, EPS>(gh, s, c, res, outPath);
+  if (xyEntries)
+    rc = runSearch<TierHybXy, EPS>(ghx, s, c, res, outPath);
+  else
+    rc = runSearch<TierHyb, EPS>(gh, s, c, res, outPath);
 #ifndef MRP_LL_TRACE
-      if (TIERS != kTiersHeavy) {
-        res.prof[2] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - th0);
-        res.prof[3] = (uint32_t)s.expansions;
-      }
+  if (TIERS != kTiersHeavy) {
+    res.prof[2] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - th0);
+    res.prof[3] = (uint32_t)s.expansions;
+  }
 #endif
-    }
+  return rc;
+}
+
+// One CBS / ECBS job: its constraint words and focal table into place, then the compact tier, then the arena tier.
+// Returns true when the job has to be handed to the heavy workgroups (kTiersFront only).
+template <bool EPS, bool BG, int TIERS>
+DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t* arenaSlot, DevResult& res,
+                 uint16_t* outPath) {
+  typedef typename std::conditional<TIERS == kTiersHeavy, ct::Wide, ct::Narrow>::type Geo;
+  // not a search of the narrow tier (the caller says so, or the job's shape does): nothing to set up here
+  if (TIERS == kTiersFront && frontHandsOver(P, J)) return true;
+  Ctx c;
+  fillCtx(c, J, P.maps, P.debug);
+  uint32_t* consLocal = slot::consCopy(arenaSlot, P.arena_scratch_off, P.out_stride);
+  if ((J.pad_[0] | J.pad_[2]) != 0u) {  // the union is in the copy area already (processJob, stageConstraintSet)
+    c.vc = consLocal;
+    c.ec = consLocal + c.nVc;
+  } else {
+    stageConstraints(P.cons, J.vc_off, c.nVc, c.nEc, consLocal, c.vc, c.ec);
+  }
+  if (!stageFocalTable<TIERS>(P, J, smem + Geo::windowBytes(BG), slot::pathsCopy(arenaSlot, P.arena_scratch_off, P.out_stride), c)) {
+    res.status = ST_BAD; res.expanded = 0; res.nodes_created = 0;
+    return false;
+  }
+  __syncthreads();
+  SState s;
+  int rc = ST_BAD;
+  res.tier = 0;
+  if (!compactAttempt<EPS, BG, TIERS>(P, J, smem, arenaSlot, c, res, outPath, s, rc)) {
+    if constexpr (TIERS == kTiersFront)
+      return true;  // the heavy workgroups run it from the start
+    else
+      rc = arenaAttempt<EPS, BG, TIERS>(P, smem, arenaSlot, c, res, outPath, s);
   }
   if (rc == RUN_MIGRATE_NODES) rc = ST_CAP_NODES;
   if (rc == RUN_MIGRATE_ROWS) rc = ST_CAP_HORIZON;
@@ -452,6 +472,44 @@ DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t*
   res.expanded = s.expansions;
   res.nodes_created = s.nNodes;
   return false;
+}
+
+// A search's path, `len` states at outPath, becomes visible: to the host at hostDst, then (f2) as cells in the device path
+// store, where the jobs of the conflict-tree nodes that contain it will read it; visible to them because they are published
+// after this job's completion was seen.  sidOf() names the slot and is asked between the two.  Agent-scope stores: through
+// this XCD's L2 to memory, where the readers' agent-scope loads find them — no write-back of the whole L2 (residentLoop).
+template <class SidFn>
+DEVI void publishPath(const LaunchParams& P, const uint16_t* outPath, uint32_t len, uint32_t* hostDst, SidFn sidOf) {
+  const uint32_t lane = threadIdx.x;
+  const uint32_t* src = (const uint32_t*)outPath;
+  for (uint32_t i = lane; i < (len + 1u) / 2u; i += 64) hostStore32(hostDst + i, src[i]);
+  const uint32_t sid = sidOf();
+  if (sid < P.path_store_slots && len < P.path_store_stride) {
+    uint16_t* slot = P.path_store + (size_t)sid * P.path_store_stride;
+    for (uint32_t i = lane; i < len; i += 64) __hip_atomic_store(slot + 1 + i, outPath[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // x | y << 8
+    __hip_atomic_store(slot, (uint16_t)len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the length word last
+  }
+}
+
+// One job's bracket, shared by processJob and processSippJob: the descriptor out of host memory into the staging record in
+// one coalesced read — HOSTLOADS: with system-scope loads; else with plain loads behind the resident loop's acquire fence —,
+// the blank result, and at the end the result record back to host memory with lane-parallel stores.
+template <bool HOSTLOADS>
+DEVI void beginJob(const DevJob* jobSrc, DevJob& jobS, DevResult& res, uint32_t tier) {
+  const uint32_t lane = threadIdx.x;
+  const uint32_t* src = (const uint32_t*)jobSrc;
+  __syncthreads();
+  if (lane < sizeof(DevJob) / 4) ((uint32_t*)&jobS)[lane] = HOSTLOADS ? hostLoad32(src + lane) : src[lane];
+  __syncthreads();
+  res.status = ST_BAD; res.cost = 0; res.fmin = 0; res.n_states = 0; res.expanded = 0; res.nodes_created = 0;
+  res.tier = tier;
+  for (int q = 0; q < 8; ++q) res.prof[q] = 0;
+}
+DEVI void endJob(const DevResult& res, DevResult& resS, DevResult* resDst) {
+  __syncthreads();
+  resS = res;
+  __syncthreads();
+  if (threadIdx.x < sizeof(DevResult) / 4) hostStore32((uint32_t*)resDst + threadIdx.x, ((const uint32_t*)&resS)[threadIdx.x]);
 }
 
 // The root chain of one ECBS conflict tree (ecbs.hpp:118-136; ll_device.h kCtxChain): agent a is planned against the
@@ -473,12 +531,10 @@ DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
   const uint32_t lane = threadIdx.x;
   const uint32_t n = J.n_ctx, first = J.t_pad, npad = J.n_agents_pad;
   const uint32_t end = J.reserved > first && J.reserved < n ? J.reserved : n;  // one past the last agent of this job
-  res.tier = 0;
-  res.n_states = 0;
-  res.expanded = 0;
+  res.tier = 0; res.n_states = 0; res.expanded = 0;
   if (P.lds_nodes == 0 || J.dimx > 32u || J.dimy > 32u || n > kChainMaxAgents || first >= n || npad < n || npad > 128u ||
       (npad & 1u) || kChainRows * npad * 2u > (P.lds_paths_bytes != 0u ? P.lds_paths_bytes : P.arena_paths_bytes) ||
-      (uint64_t)P.arena_nodes * 16u < ct::kParentBytes + ct::kBitsBytes ||
+      !compactFits<ct::Narrow>(P.arena_nodes, 0, BG) ||
       (uint64_t)n * kChainEntryWords * 2u + (uint64_t)n * 64u > (uint64_t)P.out_host_stride) {
     res.status = ST_BAD;  // (the host packer refuses such a job)
     return;
@@ -486,8 +542,7 @@ DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
   const uint32_t* who = P.cons + J.vc_off;   // starts / goals
   const uint32_t* ids = who + n;             // path-store slots
   const bool tabInLds = P.lds_paths_bytes != 0u;
-  uint16_t* table = tabInLds ? (uint16_t*)(smem + ldsBytes(0, BG))
-                             : (uint16_t*)(arenaSlot + P.arena_scratch_off + (size_t)P.out_stride * 2 + (size_t)kConsLocalWords * 4);
+  uint16_t* table = (uint16_t*)(tabInLds ? smem + ldsBytes(0, BG) : slot::pathsCopy(arenaSlot, P.arena_scratch_off, P.out_stride));
   for (uint32_t i = lane; i < kChainRows * npad / 2u; i += 64) ((uint32_t*)table)[i] = 0xFFFFFFFFu;  // nobody anywhere
   __syncthreads();
   for (uint32_t a = 0; a < first; ++a) {  // the paths that exist already: lane = time step
@@ -512,25 +567,14 @@ DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
     // 128 VGPRs means spilled and reloaded, across the search.)
     asm volatile("" : "+s"(hostW), "+s"(outPath));
     const uint32_t sg = rfl(hostLoad32(who + a));
-    ct::CJob cj;
-    cj.dimx = J.dimx; cj.dimy = J.dimy;
+    ct::CJob cj = baseCJob(P, J, arenaSlot, outPath);
     cj.sx = sg & 0xFFu; cj.sy = (sg >> 8) & 0xFFu; cj.gx = (sg >> 16) & 0xFFu; cj.gy = sg >> 24;
     cj.lastGoal = -1;
-    cj.w = J.w;
     cj.nVc = 0; cj.nEc = 0;
-    cj.obstWords = J.words_per_row;
     cj.nAgentsPad = npad; cj.tPad = kChainRows;
     cj.maxExp = clampMaxExp(budget);
-    cj.openCap = narrowOpenCap(P);
-    cj.maxT = narrowMaxT(P);
-    cj.taNoGoal = 0;
-    cj.rows = 0;
     cj.vc = 0; cj.ec = 0;
-    cj.obst = (uint64_t)(P.maps + J.map_word_off);
     cj.pathsG = tabInLds ? 0ull : (uint64_t)table;
-    cj.parentTab = (uint64_t)arenaSlot;
-    cj.outPath = (uint64_t)outPath;
-    cj.bitsG = (uint64_t)(arenaSlot + ct::kParentBytes);
     __syncthreads();
     putCJob(smem, cj);
 #ifndef MRP_LL_TRACE
@@ -567,16 +611,8 @@ DEVI void runChain(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
     const uint32_t len = (uint32_t)nStates;
     maxLen = len > maxLen ? len : maxLen;
     {  // the path: to the host, to its path-store slot, into the table
-      const uint32_t words = (len + 1u) / 2u;
-      const uint32_t* src = (const uint32_t*)outPath;
-      for (uint32_t i = lane; i < words; i += 64) hostStore32(hostW + pathOff + i, src[i]);
-      pathOff += words;
-      const uint32_t sid = rfl(hostLoad32(ids + a));
-      if (sid < P.path_store_slots && len < P.path_store_stride) {
-        uint16_t* slot = P.path_store + (size_t)sid * P.path_store_stride;
-        for (uint32_t i = lane; i < len; i += 64) __hip_atomic_store(slot + 1 + i, outPath[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(slot, (uint16_t)len, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
+      publishPath(P, outPath, len, hostW + pathOff, [&] { return rfl(hostLoad32(ids + a)); });
+      pathOff += (len + 1u) / 2u;
       uint32_t rowLen = npad;  // (opaque likewise: lane * npad is computed here, not kept across the search)
       asm volatile("" : "+s"(rowLen));
       table[lane * rowLen + a] = outPath[lane < len ? lane : len - 1];

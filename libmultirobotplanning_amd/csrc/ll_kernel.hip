@@ -12,10 +12,12 @@
 // entry); one that outgrows it is run again from the start in the arena tier, with its state in this workgroup's slot of a
 // global-memory arena and the heaps' top levels in LDS.  This translation unit is split by subject; the headers are
 // included once, here, in dependency order:
+//   ll_slot.h          the arena slot's layout: sizes and scratch areas (also the host's, mrp_ll_create)
 //   ll_compact.h       the compact tier (also compiled for the CPU emulator of the tests)
 //   ll_arena_heap.h    tiers, Mem views, the exact heap emulations, PushChains, the ordered walk
 //   ll_arena_search.h  ensureRows, initSearch, runSearch: the CBS / ECBS search of the arena tier
-//   ll_jobs.h          job staging, the arena slot's cut, runJob (compact, then arena) and runChain (ECBS root chains)
+//   ll_jobs.h          job staging and bracket, the arena slot's cut, baseCJob, runJob (stageFocalTable, compactAttempt,
+//                      arenaAttempt), publishPath and runChain (ECBS root chains)
 //   ll_ta.h            TaEnv, runTaArena / runJobTA, runJobTaEps: the task-assignment low levels
 //   ll_sipp.h          SIPP: its tiers, sippLoop, runSipp, processSippJob
 //   ll_node_scan.h     nodeScan: the conflicts of the conflict-tree node a search has completed (also compiled for the CPU)
@@ -33,6 +35,7 @@
 #include <type_traits>
 
 #include "ll_device.h"
+#include "ll_slot.h"
 #include "ll_launch.h"
 #include "wave_dev.h"
 #include "ll_compact.h"
@@ -73,7 +76,7 @@ DEVI void scanNode(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
   nj.agentIdx = J.reserved;
   nj.nStates = nStates;
   nj.tabLds = inLds ? Geo::windowBytes(BG) : ns::kTableInGlobal;
-  nj.tabG = (uint64_t)(arenaSlot + P.arena_scratch_off + (size_t)P.out_stride * 2 + (size_t)kConsLocalWords * 4);
+  nj.tabG = (uint64_t)slot::pathsCopy(arenaSlot, P.arena_scratch_off, P.out_stride);
   nj.newPath = (uint64_t)outPath;
   __syncthreads();
   {
@@ -100,32 +103,23 @@ template <int KIND, int TIERS = kTiersAll>
 DEVI bool processJob(const LaunchParams& P, const DevJob* jobSrc, DevResult* resDst, uint16_t* pathDst, uint8_t* smem,
                      uint8_t* arenaSlot, DevJob& jobS, DevResult& resS) {
   static_assert(TIERS == kTiersAll || KIND == 1, "front / heavy workgroups exist for the A*-epsilon sessions");
-  const uint32_t lane = threadIdx.x;
-  __syncthreads();
-  {  // one coalesced read of the 80-byte descriptor from host memory
-    const uint32_t* src = (const uint32_t*)jobSrc;
-    if (lane < sizeof(DevJob) / 4) ((uint32_t*)&jobS)[lane] = hostLoad32(src + lane);
-  }
-  __syncthreads();
   const DevJob& J = jobS;
   DevResult res;
-  res.status = ST_BAD; res.cost = 0; res.fmin = 0; res.n_states = 0; res.expanded = 0; res.nodes_created = 0;
-  res.tier = 0;
-  for (int q = 0; q < 8; ++q) res.prof[q] = 0;
+  beginJob<true>(jobSrc, jobS, res, 0);
   PROF_T0();
 #ifndef MRP_LL_TRACE
   const uint64_t tj0 = __builtin_amdgcn_s_memrealtime();
 #endif
-  uint16_t* outPath = (uint16_t*)(arenaSlot + P.arena_scratch_off);  // device scratch; copied out below
+  uint16_t* outPath = slot::outPath(arenaSlot, P.arena_scratch_off, P.out_stride);  // device scratch; copied out below
   uint32_t algo = rfl(J.algo);
   bool handOver = false;
   // A job that names its constraint set in the device store (ll_device.h DevJob::pad_): the union goes into the arena slot's
   // copy area — and into the result slot — here, in front of runJob; a descriptor that does not fit stays ST_BAD.  (Not in a
   // front workgroup that hands the search over unseen: the heavy workgroup that runs it stages, and writes the result slot.)
   if ((rfl(J.pad_[0]) | rfl(J.pad_[2])) != 0u && !(TIERS == kTiersFront && frontHandsOver(P, J))) {
-    uint32_t* consLocal = (uint32_t*)(arenaSlot + P.arena_scratch_off + (size_t)P.out_stride * 2);
     if (algo > 1u || (rfl(J.ctx_flags) & kCtxChain) ||
-        !stageConstraintSet(&jobS, P.cons, P.cons_store, P.cons_store_stride, P.cons_store_slots, consLocal))
+        !stageConstraintSet(&jobS, P.cons, P.cons_store, P.cons_store_stride, P.cons_store_slots,
+                            slot::consCopy(arenaSlot, P.arena_scratch_off, P.out_stride)))
       algo = 0xFFFFFFFFu;  // no search below takes it
   }
   if constexpr (KIND == 0) {
@@ -170,28 +164,9 @@ DEVI bool processJob(const LaunchParams& P, const DevJob* jobSrc, DevResult* res
   res.prof[5] = 1;
 #endif
   DBG(P, 2, res.status + 100);
-  // result + path back to host memory with lane-parallel stores
-  __syncthreads();
-  resS = res;
-  __syncthreads();
-  if (lane < sizeof(DevResult) / 4) hostStore32((uint32_t*)resDst + lane, ((const uint32_t*)&resS)[lane]);
-  if (res.status == ST_OK && !(KIND == 1 && (rfl(J.ctx_flags) & kCtxChain))) {  // (a root chain wrote its own output)
-    const uint32_t words = ((uint32_t)res.n_states + 1) / 2;
-    const uint32_t* src = (const uint32_t*)outPath;
-    uint32_t* dst = (uint32_t*)pathDst;
-    for (uint32_t i = lane; i < words; i += 64) hostStore32(dst + i, src[i]);
-    // f2: the path also goes into the device path store (as cells), where the jobs of the conflict-tree nodes that
-    // contain it will read it; visible to them because they are published after this job's completion was seen
-    const uint32_t sid = rfl(J.store_out_id);
-    if (sid < P.path_store_slots && (uint32_t)res.n_states < P.path_store_stride) {
-      // (agent-scope stores: through this XCD's L2 to memory, where the readers' agent-scope loads find them — no
-      // write-back of the whole L2 is needed to publish them, residentLoop)
-      uint16_t* slot = P.path_store + (size_t)sid * P.path_store_stride;
-      for (uint32_t i = lane; i < (uint32_t)res.n_states; i += 64)
-        __hip_atomic_store(slot + 1 + i, outPath[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // x | y << 8
-      __hip_atomic_store(slot, (uint16_t)res.n_states, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  endJob(res, resS, resDst);
+  if (res.status == ST_OK && !(KIND == 1 && (rfl(J.ctx_flags) & kCtxChain)))  // (a root chain wrote its own output)
+    publishPath(P, outPath, (uint32_t)res.n_states, (uint32_t*)pathDst, [&] { return rfl(J.store_out_id); });
   return false;
 }
 
@@ -204,6 +179,14 @@ static_assert(sizeof(DevJob) + sizeof(DevResult) <= ct::oJob, "control block of 
   if ((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)smem != 0u) __builtin_trap(); \
   DevJob& jobS = *(DevJob*)(smem + ct::oCtl);                                                         \
   DevResult& resS = *(DevResult*)(smem + ct::oCtl + sizeof(DevJob))
+// A kernel whose whole body is one job loop on the window's blocks
+#define MRP_LL_WINDOW_KERNEL(NAME, ...)                                                  \
+  extern "C" __global__ void __launch_bounds__(64) NAME(LaunchParams Parg) {             \
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];                       \
+    MRP_LL_WINDOW_BLOCKS(smem, jobS, resS);                                              \
+    const LaunchParams& P = Parg;                                                        \
+    __VA_ARGS__(P, smem, jobS, resS);                                                    \
+  }
 template <int KIND>
 DEVI void batchLoop(const LaunchParams& P, uint8_t* smem, DevJob& jobS, DevResult& resS) {
   const uint32_t lane = threadIdx.x;
@@ -222,24 +205,9 @@ DEVI void batchLoop(const LaunchParams& P, uint8_t* smem, DevJob& jobS, DevResul
   DBG(P, 4, 1);
 }
 
-extern "C" __global__ void __launch_bounds__(64) mrp_ll_search_kernel(LaunchParams Parg) {  // mixed batches
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  MRP_LL_WINDOW_BLOCKS(smem, jobS, resS);
-  const LaunchParams& P = Parg;
-  batchLoop<0>(P, smem, jobS, resS);
-}
-extern "C" __global__ void __launch_bounds__(64) mrp_ll_ecbs_search_kernel(LaunchParams Parg) {  // A*-epsilon jobs only
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  MRP_LL_WINDOW_BLOCKS(smem, jobS, resS);
-  const LaunchParams& P = Parg;
-  batchLoop<1>(P, smem, jobS, resS);
-}
-extern "C" __global__ void __launch_bounds__(64) mrp_ll_cbs_search_kernel(LaunchParams Parg) {  // A* jobs only
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  MRP_LL_WINDOW_BLOCKS(smem, jobS, resS);
-  const LaunchParams& P = Parg;
-  batchLoop<2>(P, smem, jobS, resS);
-}
+MRP_LL_WINDOW_KERNEL(mrp_ll_search_kernel, batchLoop<0>)  // mixed batches
+MRP_LL_WINDOW_KERNEL(mrp_ll_ecbs_search_kernel, batchLoop<1>)  // A*-epsilon jobs only
+MRP_LL_WINDOW_KERNEL(mrp_ll_cbs_search_kernel, batchLoop<2>)  // A* jobs only
 
 // SIPP batches (MRP_LL_SIPP jobs only) run in their own kernels so that the CBS/ECBS kernels' register allocation is
 // not widened by a path they never take.  Same queue discipline as mrp_ll_search_kernel.
@@ -307,11 +275,31 @@ DEVI void publishDone(const LaunchParams& P, uint32_t slot, uint32_t doneVal) {
 #endif
 }
 
+// Safety net for a host that died: the host bumps a heartbeat word on every submit / poll.  True when that word has not
+// moved for ring_idle_limit_s (tBeat: the last look, lastBeat: what it saw) — the waiting workgroup leaves; a live host that is
+// merely slow to publish (a long tail search elsewhere, a caller pausing between submits while it keeps polling) never loses
+// the workgroup that holds the ticket it will publish next.
+DEVI bool hostGone(const LaunchParams& P, uint64_t& tBeat, uint32_t& lastBeat) {
+  const uint64_t idleLimit = (uint64_t)P.ring_idle_limit_s * 100000000ull;  // s_memrealtime ticks at 100 MHz
+  if (__builtin_amdgcn_s_memrealtime() - tBeat <= idleLimit) return false;
+  const uint32_t hb = rfl(__hip_atomic_load(P.ring_head + kHeartbeatWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
+  if (hb == lastBeat) return true;
+  lastBeat = hb;
+  tBeat = __builtin_amdgcn_s_memrealtime();
+  return false;
+}
+// A leaving workgroup's share of sess_ticks[first .. first + 2]: busy ticks, idle ticks, "ran at least one job"
+DEVI void reportTicks(const LaunchParams& P, uint32_t first, uint64_t busyTicks, uint64_t idleTicks) {
+  const uint32_t lane = threadIdx.x;
+  atomicAdd(P.sess_ticks + first, lane == 0 ? (unsigned long long)busyTicks : 0ull);
+  atomicAdd(P.sess_ticks + first + 1, lane == 0 ? (unsigned long long)idleTicks : 0ull);
+  atomicAdd(P.sess_ticks + first + 2, (lane == 0 && busyTicks != 0) ? 1ull : 0ull);
+}
+
 template <bool SIPP, int KIND, int TIERS = kTiersAll>
 DEVI void residentLoop(const LaunchParams& P, uint8_t* smem, DevJob& jobS, DevResult& resS) {
   const uint32_t lane = threadIdx.x;
   uint8_t* arenaSlot = P.arena + (size_t)blockIdx.x * P.arena_stride;
-  const uint64_t idleLimit = (uint64_t)P.ring_idle_limit_s * 100000000ull;  // s_memrealtime ticks at 100 MHz
   uint64_t busyTicks = 0, idleTicks = 0;
   const uint32_t q0 = P.ring_size;
   uint32_t* const ring0 = P.ring_state;
@@ -389,22 +377,9 @@ DEVI void residentLoop(const LaunchParams& P, uint8_t* smem, DevJob& jobS, DevRe
         }
       }
       if (sp == 0) sp = rfl(__hip_atomic_load(mirror + 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      if (sp != 0) {
+      if (sp != 0 || hostGone(P, tBeat, lastBeat)) {  // (a workgroup always holds a bulk ticket while it waits)
         stop = true;
         break;
-      }
-      // Safety net for a host that died: the host bumps a heartbeat word on every submit / poll.  A workgroup — which
-      // always holds a bulk ticket while it waits — leaves only when that word has not moved for ring_idle_limit_s; a
-      // live host that is merely slow to publish (a long tail search elsewhere, a caller pausing between submits while
-      // it keeps polling) never loses the workgroup that holds the ticket it will publish next.
-      if (__builtin_amdgcn_s_memrealtime() - tBeat > idleLimit) {
-        const uint32_t hb = rfl(__hip_atomic_load(P.ring_head + kHeartbeatWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-        if (hb == lastBeat) {
-          stop = true;
-          break;
-        }
-        lastBeat = hb;
-        tBeat = __builtin_amdgcn_s_memrealtime();
       }
       uint32_t naps = (int32_t)(bulkT - hd) > 0 ? 1 + (bulkT - hd) : 1;
       if (naps > 48) naps = 48;
@@ -431,23 +406,11 @@ DEVI void residentLoop(const LaunchParams& P, uint8_t* smem, DevJob& jobS, DevRe
     }
     busyTicks += __builtin_amdgcn_s_memrealtime() - t1c;
   }
-  atomicAdd(P.sess_ticks + 0, lane == 0 ? (unsigned long long)busyTicks : 0ull);
-  atomicAdd(P.sess_ticks + 1, lane == 0 ? (unsigned long long)idleTicks : 0ull);
-  atomicAdd(P.sess_ticks + 2, (lane == 0 && busyTicks != 0) ? 1ull : 0ull);  // workgroups that ran at least one job
+  reportTicks(P, 0, busyTicks, idleTicks);
 }
 
-extern "C" __global__ void __launch_bounds__(64) mrp_ll_persistent_kernel(LaunchParams Parg) {  // mixed sessions
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  MRP_LL_WINDOW_BLOCKS(smem, jobS, resS);
-  const LaunchParams& P = Parg;
-  residentLoop<false, 0>(P, smem, jobS, resS);
-}
-extern "C" __global__ void __launch_bounds__(64) mrp_ll_ecbs_persistent_kernel(LaunchParams Parg) {  // A*-epsilon only
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  MRP_LL_WINDOW_BLOCKS(smem, jobS, resS);
-  const LaunchParams& P = Parg;
-  residentLoop<false, 1>(P, smem, jobS, resS);
-}
+MRP_LL_WINDOW_KERNEL(mrp_ll_persistent_kernel, residentLoop<false, 0>)  // mixed sessions
+MRP_LL_WINDOW_KERNEL(mrp_ll_ecbs_persistent_kernel, residentLoop<false, 1>)  // A*-epsilon only
 // The front / heavy pair of an A*-epsilon session (ll_device.h heavy_q).  Front workgroups are the resident loop above
 // with the narrow compact tier alone — no arena-tier code, hence a smaller register allocation; heavy workgroups wait on
 // the device-side queue the front ones fill, run each search in the WIDE compact geometry (31.4 KB of LDS: open and focal
@@ -481,7 +444,6 @@ extern "C" __global__ void __launch_bounds__(64) mrp_ll_ecbs_heavy_kernel(Launch
   const uint32_t lane = threadIdx.x;
   uint8_t* arenaSlot = P.arena + (size_t)blockIdx.x * P.arena_stride;
   uint32_t* const mirror = P.queue_head + 32;
-  const uint64_t idleLimit = (uint64_t)P.ring_idle_limit_s * 100000000ull;
   uint64_t busyTicks = 0, idleTicks = 0;
   hostStore32(P.heavy_alive + blockIdx.x, 1u);  // "this workgroup is resident" (the host checks before it relies on us)
   uint32_t lastBeat = 0;
@@ -498,18 +460,9 @@ extern "C" __global__ void __launch_bounds__(64) mrp_ll_ecbs_heavy_kernel(Launch
       if ((((uint32_t)e) >> kRingSlotBits) == gen) break;
       uint32_t sp = rfl(__hip_atomic_load(mirror + 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
       if (sp == 0 && (++looks & 31u) == 0u) sp = rfl(__hip_atomic_load(P.ring_stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-      if (sp != 0) {
+      if (sp != 0 || hostGone(P, tBeat, lastBeat)) {
         stop = true;
         break;
-      }
-      if (__builtin_amdgcn_s_memrealtime() - tBeat > idleLimit) {
-        const uint32_t hb = rfl(__hip_atomic_load(P.ring_head + kHeartbeatWord, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM));
-        if (hb == lastBeat) {
-          stop = true;
-          break;
-        }
-        lastBeat = hb;
-        tBeat = __builtin_amdgcn_s_memrealtime();
       }
       for (uint32_t q = 0; q < naps; ++q) __builtin_amdgcn_s_sleep(64);  // ~2 us, doubling to ~16 us
       if (naps < 8) naps *= 2;
@@ -523,17 +476,10 @@ extern "C" __global__ void __launch_bounds__(64) mrp_ll_ecbs_heavy_kernel(Launch
     publishDone<false>(P, slot, doneVal);
     busyTicks += __builtin_amdgcn_s_memrealtime() - t1c;
   }
-  atomicAdd(P.sess_ticks + 4, lane == 0 ? (unsigned long long)busyTicks : 0ull);
-  atomicAdd(P.sess_ticks + 5, lane == 0 ? (unsigned long long)idleTicks : 0ull);
-  atomicAdd(P.sess_ticks + 6, (lane == 0 && busyTicks != 0) ? 1ull : 0ull);
+  reportTicks(P, 4, busyTicks, idleTicks);
 }
 
-extern "C" __global__ void __launch_bounds__(64) mrp_ll_cbs_persistent_kernel(LaunchParams Parg) {  // A* only
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  MRP_LL_WINDOW_BLOCKS(smem, jobS, resS);
-  const LaunchParams& P = Parg;
-  residentLoop<false, 2>(P, smem, jobS, resS);
-}
+MRP_LL_WINDOW_KERNEL(mrp_ll_cbs_persistent_kernel, residentLoop<false, 2>)  // A* only
 
 // The same resident loop for SIPP sessions (jobs of algo MRP_LL_SIPP only).  9.2 KB of LDS per workgroup hold up to 768
 // nodes and the open list of a search on a device-resident table (16 workgroups per CU; ll_sipp.h kSippLdsCap).

@@ -654,8 +654,7 @@ DEVI void runSipp(const LaunchParams& P, const DevJob& J, uint8_t* arenaSlot, ui
   typedef TierHbm T;
   Mem<T> g = cutArena(P, arenaSlot);
   const Mem<T>::PNode4 gNodes = (Mem<T>::PNode4)g.nodes;
-  uint8_t* scratch = arenaSlot + P.arena_scratch_off;
-  uint32_t* tab = (uint32_t*)((uint32_t*)(scratch + (size_t)P.out_stride * 2) + kConsLocalWords);  // path-table area
+  uint32_t* tab = (uint32_t*)slot::pathsCopy(arenaSlot, P.arena_scratch_off, P.out_stride);
   SippView<RES> tv;
   tv.cells = cells;
   tv.epochBits = 0;
@@ -901,17 +900,9 @@ DEVI void runSipp(const LaunchParams& P, const DevJob& J, uint8_t* arenaSlot, ui
 DEVI void processSippJob(const LaunchParams& P, const DevJob* jobSrc, DevResult* resDst, uint16_t* pathDst,
                          uint8_t* arenaSlot, uint8_t* ldsTier, DevJob& jobS, DevResult& resS) {
   const uint32_t lane = threadIdx.x;
-  __syncthreads();
-  {
-    const uint32_t* src = (const uint32_t*)jobSrc;
-    if (lane < sizeof(DevJob) / 4) ((uint32_t*)&jobS)[lane] = src[lane];
-  }
-  __syncthreads();
   DevResult res;
-  res.status = ST_BAD; res.cost = 0; res.fmin = 0; res.n_states = 0; res.expanded = 0; res.nodes_created = 0;
-  res.tier = 1;
-  for (int q = 0; q < 8; ++q) res.prof[q] = 0;
-  uint16_t* outPath = (uint16_t*)(arenaSlot + P.arena_scratch_off);
+  beginJob<false>(jobSrc, jobS, res, 1);
+  uint16_t* outPath = slot::outPath(arenaSlot, P.arena_scratch_off, P.out_stride);
   const uint64_t tj0 = __builtin_amdgcn_s_memrealtime();
   if (rfl(jobS.algo) == 2) {  // anything else stays ST_BAD
     if (rfl(jobS.ctx_flags) & kSippResident) {
@@ -923,10 +914,7 @@ DEVI void processSippJob(const LaunchParams& P, const DevJob* jobSrc, DevResult*
   }
   res.prof[4] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - tj0);  // the whole of runSipp (table update + search)
   res.prof[5] = 1;
-  __syncthreads();
-  resS = res;
-  __syncthreads();
-  if (lane < sizeof(DevResult) / 4) hostStore32((uint32_t*)resDst + lane, ((const uint32_t*)&resS)[lane]);
+  endJob(res, resS, resDst);
   if (res.status == ST_OK) {  // one u32 (cell | g << 16) per raw A* state
     const uint32_t* src = (const uint32_t*)outPath;
     uint32_t* dst = (uint32_t*)pathDst;

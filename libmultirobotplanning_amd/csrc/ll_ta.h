@@ -128,7 +128,7 @@ DEVI void runTaArena(const LaunchParams& P, const DevJob& J, uint8_t* arenaSlot,
   Mem<T> g = cutArena(P, arenaSlot);
   uint32_t* status = (uint32_t*)((uint8_t*)g.focal - 8);  // (the status table lives from here on)
   g.aux = g.focal;
-  const uint64_t statusWords = ((uint64_t)P.arena_nodes * 8 + 16) * 2 / 4;
+  const uint64_t statusWords = slot::heapBytes(P.arena_nodes) * 2 / 4;
   Ctx c;
   fillCtx(c, J, P.maps, P.debug);
   c.w = 1.0f;
@@ -241,31 +241,22 @@ DEVI void runJobTA(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
   res.tier = 0;
   const uint32_t* vc;
   const uint32_t* ec;
-  stageConstraints(P.cons, J.vc_off, J.n_vc, J.n_ec, (uint32_t*)(arenaSlot + P.arena_scratch_off + (size_t)P.out_stride * 2),
-                   vc, ec);
+  stageConstraints(P.cons, J.vc_off, J.n_vc, J.n_ec, slot::consCopy(arenaSlot, P.arena_scratch_off, P.out_stride), vc, ec);
   __syncthreads();
   const bool small = J.dimx <= 32u && J.dimy <= 32u;
   const uint16_t* heur = (const uint16_t*)(P.maps + J.path_off);
   const bool compactOk = P.lds_nodes != 0 && P.lds_paths_bytes >= 2048u && small && J.n_vc <= 64u && J.n_ec <= 64u &&
-                         (uint64_t)P.arena_nodes * 16u >= ct::kParentBytes;
+                         compactFits<ct::Narrow>(P.arena_nodes, 0, false);
   if (compactOk) {
-    ct::CJob cj;
-    cj.dimx = J.dimx; cj.dimy = J.dimy; cj.sx = J.sx; cj.sy = J.sy; cj.gx = J.gx; cj.gy = J.gy;
+    ct::CJob cj = baseCJob(P, J, arenaSlot, outPath);
+    cj.sx = J.sx; cj.sy = J.sy; cj.gx = J.gx; cj.gy = J.gy;
     cj.lastGoal = J.last_goal_constraint;
     cj.w = 1.0f;
     cj.nVc = J.n_vc; cj.nEc = J.n_ec;
-    cj.obstWords = J.words_per_row;
     cj.nAgentsPad = 0; cj.tPad = 0;
-    cj.maxExp = clampMaxExp(J.max_expansions);
-    cj.openCap = narrowOpenCap(P);
-    cj.maxT = narrowMaxT(P);
     cj.taNoGoal = (J.ctx_flags & kTaNoGoal) ? 1u : 0u;
-    cj.rows = 0;
     cj.vc = (uint64_t)vc; cj.ec = (uint64_t)ec;
-    cj.obst = (uint64_t)(P.maps + J.map_word_off);
     cj.pathsG = (uint64_t)heur;
-    cj.parentTab = (uint64_t)arenaSlot;
-    cj.outPath = (uint64_t)outPath;
     putCJob(smem, cj);
     const uint64_t tl0 = __builtin_amdgcn_s_memrealtime();
     const int32_t crc = ct::compactSearchTA((wv::Lds)smem);
@@ -273,12 +264,8 @@ DEVI void runJobTA(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
     res.prof[0] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - tl0);
     res.prof[1] = cr.expanded;
     if (crc != ct::C_CAP_NODES && crc != ct::C_CAP_HORIZON) {  // an answer (C_OK / C_NO_SOLUTION / C_CAP_EXP == the ST_ codes)
-      res.status = crc;
-      res.cost = cr.cost;
-      res.fmin = cr.fmin;
-      res.n_states = cr.nStates;
-      res.expanded = cr.expanded;
-      res.nodes_created = cr.nodes;
+      res.status = crc; res.cost = cr.cost; res.fmin = cr.fmin; res.n_states = cr.nStates;
+      res.expanded = cr.expanded; res.nodes_created = cr.nodes;
       return;
     }
     res.prof[6] = cr.expanded;  // expansions thrown away with the attempt
@@ -302,7 +289,7 @@ DEVI void runJobTA(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
 // entry's key is rewritten at its position (TierFocalPos keeps handle -> focal position) and nothing is sifted; every later
 // focal operation then sees the same (possibly out-of-order) array the reference's heap sees.
 //
-// The arena slot's node + heap area (LaunchParams.arena_nodes * 40 + 48 bytes; the (time, cell) bitmap behind it stays
+// The arena slot's node + heap area (ll_slot.h areaBytes: arena_nodes * 40 + 48 bytes; the (time, cell) bitmap behind it stays
 // where it is) is cut differently from the other searches, because this one needs the status table AND both heaps:
 //   status   one word per (t, cell): 0 unseen, node + 1 in the open list, bit 31 closed; rows = min(arena_rows,
 //            area / 8 / cells) time steps (at most half of the area)
@@ -400,10 +387,9 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
   s.nNodes = 0; s.nOpen = 0; s.nFocal = 0; s.rowsReady = 0; s.bestF = 0; s.expansions = 0;
 
   // ---- the job's constraint words and focal path table leave host memory in one pass
-  uint8_t* scratch = arenaSlot + scratchOff;
-  uint16_t* outPath = (uint16_t*)scratch;
-  uint32_t* consLocal = (uint32_t*)(scratch + (size_t)outStride * 2);
-  uint8_t* pathsArena = (uint8_t*)(consLocal + kConsLocalWords);
+  uint16_t* outPath = slot::outPath(arenaSlot, scratchOff, outStride);
+  uint32_t* consLocal = slot::consCopy(arenaSlot, scratchOff, outStride);
+  uint8_t* pathsArena = slot::pathsCopy(arenaSlot, scratchOff, outStride);
   stageConstraints(consHost, rfl(Jp->vc_off), c.nVc, c.nEc, consLocal, c.vc, c.ec);
   {
     const uint32_t pathOff = rfl(Jp->path_off);
@@ -424,7 +410,7 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
   __syncthreads();
 
   // ---- this search's cut of the slot
-  const uint64_t area = (uint64_t)arenaNodes * 16 + 3 * ((uint64_t)arenaNodes * 8 + 16);
+  const uint64_t area = slot::areaBytes(arenaNodes);
   const uint64_t rows64 = area / 8 / cells;
   const uint32_t rows = (uint32_t)(rows64 < arenaRows ? rows64 : arenaRows);
   const uint64_t statusBytes = ((uint64_t)rows * cells * 4 + 15) & ~15ull;

@@ -20,6 +20,7 @@
 #include "host/ll_session.h"
 #include "host/ll_session_jobs.h"
 #include "host/ll_submit.h"
+#include "ll_slot.h"
 
 namespace {
 // Resident workgroups per CU when the runtime gives no answer: what the LDS window alone allows, 1 .. 16.
@@ -69,14 +70,9 @@ int mrp_ll_create(const mrp_ll_options* optIn, mrp_ll_ctx** out) {
     return MRP_LL_E_DEVICE;
   }
   ctx->arenaRowWords = (static_cast<uint32_t>(o.max_cells) + 31u) / 32u;
-  uint64_t stride = static_cast<uint64_t>(o.arena_nodes) * 16 + 3ull * (static_cast<uint64_t>(o.arena_nodes) * 8 + 16) +
-                    static_cast<uint64_t>(o.max_horizon) * ctx->arenaRowWords * 4;
-  stride = (stride + 255) & ~255ull;
-  // scratch tail of every slot: [path out: max_horizon u16][constraint copy][path-table copy]
-  ctx->arenaScratchOff = static_cast<uint32_t>(stride);
   ctx->env.arenaPathsBytes = 128 * 1024;
-  stride += static_cast<uint64_t>(o.max_horizon) * 2 + mrp::kConsLocalWords * 4 + ctx->env.arenaPathsBytes;
-  stride = (stride + 255) & ~255ull;
+  ctx->arenaScratchOff = static_cast<uint32_t>(mrp::slot::scratchOff(o.arena_nodes, o.max_horizon, ctx->arenaRowWords));
+  const uint64_t stride = mrp::slot::stride(o.arena_nodes, o.max_horizon, ctx->arenaRowWords, ctx->env.arenaPathsBytes);
   ctx->arenaStride = stride;
   ctx->tickets.resize(o.n_tickets);
   for (auto& t : ctx->tickets) {
