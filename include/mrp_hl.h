@@ -87,6 +87,9 @@ typedef struct mrp_hl_batch_stats {
   /* ECBS sessions with MRP_HL_DEVICE_SCAN=1: conflict-tree nodes whose first conflict and conflict count came back with their
    * low-level search (mrp_ll.h mrp_ll_submit_scan) instead of being scanned by the driver; 0 otherwise */
   int64_t device_scans;
+  /* ... those of them (MRP_HL_DEVICE_SCAN_INCREMENTAL=1, an engine with mrp_ll_submit_node) whose workgroup started from what
+   * the parent node's scan had established (MRP_LL_JOB_SCAN_FROM_PARENT); counted in device_scans too; 0 otherwise */
+  int64_t incremental_scans;
 } mrp_hl_batch_stats;
 
 /* One engine context per calling thread is created internally for every worker thread on `device`. */

@@ -518,6 +518,42 @@ typedef struct mrp_ll_constraint_ref {
 int mrp_ll_submit_sets(mrp_ll_ctx* ctx, int32_t tag, int32_t n_jobs, const mrp_ll_job* jobs, mrp_ll_result* results,
                        mrp_ll_conflict* conflicts, const mrp_ll_constraint_ref* sets, int32_t* ticket);
 
+/* ---- a conflict-tree child's conflicts from what its PARENT's scan established ---------------------------------
+ * A child differs from its parent in one path, and the caller that scanned the parent knows its number of conflicts and a
+ * time before which it has none (the time of the conflict it was split on; ecbs.hpp:200-270).  Given both and the slot of
+ * the REPLACED path, the workgroup produces the child's mrp_ll_conflict with work linear in the agents for the count and
+ * all-pairs work only for the time steps between the parent's first conflict and the child's, instead of
+ * MRP_LL_JOB_SCAN_CONFLICTS' all pairs at every time step. */
+typedef struct mrp_ll_scan_base {
+  int32_t parent_count;   /* focalHeuristic of the PARENT node (agent_idx's replaced path in place) */
+  int32_t clean_before;   /* the parent node has no conflict at any time step < this; 0 is always valid */
+} mrp_ll_scan_base;
+
+#define MRP_LL_JOB_SCAN_FROM_PARENT 64 /* mrp_ll_job.flags, only together with MRP_LL_JOB_SCAN_CONFLICTS: bases[i] of
+                                        * mrp_ll_submit_node is honoured for this job */
+
+/* mrp_ll_submit_sets plus `bases`; bases may be NULL when no job has MRP_LL_JOB_SCAN_FROM_PARENT, and an unflagged job
+ * ignores bases[i].  Same lock, tag rules and collection calls as mrp_ll_submit_sets, in and outside a session.
+ * A flagged job must satisfy everything MRP_LL_JOB_SCAN_CONFLICTS requires; in addition path_ids[agent_idx] >= 0 names the
+ * path-store slot of the replaced path — agent_idx's path at the parent node — with path_len[agent_idx] >= 1 (the search
+ * still never sees its own agent's column: the slot is not part of the focal context), and parent_count >= 0,
+ * clean_before >= 0.  Anything else, the flag without MRP_LL_JOB_SCAN_CONFLICTS, or the flag through any other entry point,
+ * is MRP_LL_BAD_JOB: not run, no slot touched.
+ * With a = agent_idx, tPad = the longest other path, L_new = the found path's length, L_old = the length stored in the
+ * replaced path's slot, T_x = max(tPad, L_x) - 1 and C(p, T) = the vertex + swap conflicts between path p and every other
+ * agent at t < T (every path holding its last cell beyond its end):  T_new == T_old gives
+ * count = parent_count - C(old, T) + C(new, T); with different horizons the workgroup runs MRP_LL_JOB_SCAN_CONFLICTS' full scan
+ * (stationary agents that share a last cell make the extra steps count).  found and the first conflict are the child's, in
+ * mrp_ll_conflict_scan's order.  With TRUTHFUL bases all ten words of conflicts[i] equal mrp_ll_conflict_scan of the
+ * child, which is also what the same job returns with MRP_LL_JOB_SCAN_CONFLICTS alone; the job's result never depends on
+ * the flag; a status other than MRP_LL_OK / MRP_LL_PATH_TRUNCATED gives found = -1, the rest 0; n_agents == 1 gives found 0,
+ * count 0.
+ * UNTRUTHFUL bases (a wrong parent_count, a clean_before behind the parent's first conflict, a slot that holds another
+ * path) give a wrong mrp_ll_conflict and nothing else: no access outside the job's buffers, no loop beyond T time steps. */
+int mrp_ll_submit_node(mrp_ll_ctx* ctx, int32_t tag, int32_t n_jobs, const mrp_ll_job* jobs, mrp_ll_result* results,
+                       mrp_ll_conflict* conflicts, const mrp_ll_constraint_ref* sets, const mrp_ll_scan_base* bases /* [n_jobs] */,
+                       int32_t* ticket);
+
 int mrp_ll_get_stats(const mrp_ll_ctx* ctx, mrp_ll_stats* out);
 int mrp_ll_reset_stats(mrp_ll_ctx* ctx);
 

@@ -68,6 +68,7 @@ struct GroupResult {
   int64_t specSearches = 0, specWasted = 0;          // searches issued ahead of their node's pop; expansions that were run but never consumed
   int64_t rootSolved = 0;                            // instances whose root node was conflict-free, written out without a conflict tree
   int64_t deviceScans = 0;                           // conflict-tree nodes whose conflicts came with their low-level search
+  int64_t incrementalScans = 0;                      // ... those scanned from what their parent's scan established (mrp_ll_submit_node)
   double buildS = 0, llS = 0, consumeS = 0;
   std::string err;
 };
@@ -128,7 +129,9 @@ struct JobBatch {
   std::vector<const int32_t*> pathPtrPool;
   std::vector<size_t> poolOff;  // per job: where its context starts in the pools
   std::vector<uint8_t> idOk;  // per job: every context path it needs has a device path-store slot
+  std::vector<uint8_t> ownOk;  // per job: ... and the path it replaces has one too, and is named in the searching agent's entry
   void clear() {
+    ownOk.clear();
     jobs.clear();
     pathLenPool.clear();
     idPool.clear();
@@ -137,7 +140,9 @@ struct JobBatch {
     idOk.clear();
   }
   // One job for request `r` of instance `I`.  `withIds`: also name the context paths by their device path-store slots (f2).
-  mrp_ll_job& add(const Instance& I, const LLRequest& r, bool withIds = false) {
+  // `withOwn`: the searching agent's entry names the slot of the path the search replaces (mrp_ll_submit_node; every other
+  // entry point ignores that entry).
+  mrp_ll_job& add(const Instance& I, const LLRequest& r, bool withIds = false, bool withOwn = false) {
     jobs.emplace_back();
     mrp_ll_job& j = jobs.back();
     std::memset(&j, 0, sizeof(j));
@@ -156,7 +161,7 @@ struct JobBatch {
     j.max_expansions = I.remainingLL();
     j.result_path_id = -1;
     poolOff.push_back(pathLenPool.size());
-    bool all = false;
+    bool all = false, own = false;
     if (r.context) {
       j.n_agents = static_cast<int32_t>(r.context->size());
       all = withIds;
@@ -171,8 +176,15 @@ struct JobBatch {
         }
         ++a;
       }
+      if (withOwn && all && r.replaced && r.parentCount >= 0 && r.cleanBefore >= 0) {
+        // (the context still holds the parent's path of the searching agent: the one this search replaces)
+        const PathPtr& p = (*r.context)[r.agent];
+        own = p.get() == r.replaced && p->len() > 0 && p->devSlot >= 0;
+        if (own) idPool[poolOff.back() + static_cast<size_t>(r.agent)] = p->devSlot;
+      }
     }
     idOk.push_back(all ? 1 : 0);
+    ownOk.push_back(all && own ? 1 : 0);
     return j;
   }
   void patch() {
@@ -196,6 +208,10 @@ extern "C" __attribute__((weak)) int mrp_ll_submit_sets(mrp_ll_ctx* ctx, int32_t
                                                         mrp_ll_result* results, mrp_ll_conflict* conflicts,
                                                         const mrp_ll_constraint_ref* sets, int32_t* ticket);
 extern "C" __attribute__((weak)) int mrp_ll_constraint_store_reserve(mrp_ll_ctx* ctx, int32_t n_slots, int32_t words_per_slot);
+// mrp_ll_submit_node likewise: without it MRP_HL_DEVICE_SCAN_INCREMENTAL changes nothing.
+extern "C" __attribute__((weak)) int mrp_ll_submit_node(mrp_ll_ctx* ctx, int32_t tag, int32_t n_jobs, const mrp_ll_job* jobs,
+                                                        mrp_ll_result* results, mrp_ll_conflict* conflicts,
+                                                        const mrp_ll_constraint_ref* sets, const mrp_ll_scan_base* bases, int32_t* ticket);
 inline bool engineHasConstraintStore() { return &mrp_ll_submit_sets != nullptr && &mrp_ll_constraint_store_reserve != nullptr; }
 // mrp_ll_constraint_store_reserve, or MRP_LL_E_INVALID on an engine without it
 inline int reserveConstraintStore(mrp_ll_ctx* ctx, int32_t nSlots, int32_t wordsPerSlot) {
@@ -347,7 +363,10 @@ class SessionWorker {
   SessionWorker(const SessionPlan& plan, const WorkerSeat& seat, GroupResult& out)
       : plan_(plan), seat_(seat), out_(out), tagged_(seat.coCount > 1 && seat.co != nullptr),
         rootChains_(plan.pathSlots > 0 && plan.opt.algo == MRP_HL_ECBS && plan.knobs.rootChains),
-        deviceScan_(plan.knobs.deviceScan && plan.pathSlots > 0 && plan.opt.algo == MRP_HL_ECBS && &mrp_ll_submit_scan != nullptr),
+        scanFromParent_(plan.knobs.deviceScanIncremental && plan.pathSlots > 0 && plan.opt.algo == MRP_HL_ECBS &&
+                        &mrp_ll_submit_node != nullptr),
+        deviceScan_(scanFromParent_ ||
+                    (plan.knobs.deviceScan && plan.pathSlots > 0 && plan.opt.algo == MRP_HL_ECBS && &mrp_ll_submit_scan != nullptr)),
         deviceCons_(plan.consSlots > 0 && plan.consWords > 0),  // (reserved only with MRP_HL_DEVICE_CONSTRAINTS on an engine that has the store)
         // this worker's share of the engine's resident wavefronts
         myWorkgroups_(std::max(1, plan.workgroups / std::max(seat.coCount, 1))),
@@ -404,6 +423,12 @@ class SessionWorker {
     // those jobs name: a set (and with it its slot) outlives every unfinished job that reads or writes the slot
     std::vector<mrp_ll_constraint_ref> sets;
     std::vector<ConsPtr> consHold;
+    // per job, when the ticket went through mrp_ll_submit_node (else empty): what the parent's scan established; the paths
+    // the jobs replace stay alive, and with them their slots, until the ticket is back
+    std::vector<mrp_ll_scan_base> bases;
+    std::vector<PathPtr> replacedHold;
+    std::vector<uint8_t> flagged;  // per job: it carried MRP_LL_JOB_SCAN_FROM_PARENT
+    bool fromParent(size_t q) const { return q < flagged.size() && flagged[q] != 0; }
     // a root chain (MRP_LL_JOB_ROOT_CHAIN): ONE job whose result fans out into chainRes, one per agent from chainFirst on
     std::vector<mrp_ll_result> chainRes;
     int32_t chainFirst = -1;
@@ -489,6 +514,9 @@ class SessionWorker {
     pend_[pi].conf.clear();
     pend_[pi].sets.clear();
     pend_[pi].consHold.clear();
+    pend_[pi].bases.clear();
+    pend_[pi].replacedHold.clear();
+    pend_[pi].flagged.clear();
     pend_[pi].chainReq.clear();
     pendFree_.push_back(pi);
   }
@@ -501,7 +529,9 @@ class SessionWorker {
   int publish(int32_t pi, int32_t nJobs, const mrp_ll_job* jobs, const char* what) {
     Pending& P = pend_[pi];
     int32_t ticket = -1;
-    const int rc = !P.sets.empty() ? mrp_ll_submit_sets(seat_.ctx, tagged_ ? seat_.coIndex : 0, nJobs, jobs, P.res.data(),
+    const int rc = !P.bases.empty() ? mrp_ll_submit_node(seat_.ctx, tagged_ ? seat_.coIndex : 0, nJobs, jobs, P.res.data(), P.conf.data(),
+                                                         P.sets.empty() ? nullptr : P.sets.data(), P.bases.data(), &ticket)
+                   : !P.sets.empty() ? mrp_ll_submit_sets(seat_.ctx, tagged_ ? seat_.coIndex : 0, nJobs, jobs, P.res.data(),
                                                         P.conf.empty() ? nullptr : P.conf.data(), P.sets.data(), &ticket)
                    : !P.conf.empty() ? mrp_ll_submit_scan(seat_.ctx, tagged_ ? seat_.coIndex : 0, nJobs, jobs, P.res.data(), P.conf.data(), &ticket)
                    : tagged_      ? mrp_ll_submit_tagged(seat_.ctx, seat_.coIndex, nJobs, jobs, P.res.data(), &ticket)
@@ -603,7 +633,7 @@ class SessionWorker {
     batch_.clear();
     size_t end = L.reqHead;
     for (; end < L.req.size() && L.req[end].group == group; ++end) {
-      mrp_ll_job& j = batch_.add(*L.inst, L.req[end], plan_.pathSlots > 0);
+      mrp_ll_job& j = batch_.add(*L.inst, L.req[end], plan_.pathSlots > 0, scanFromParent_ && group != kRootGroup);
       // a root search that ended a chain outgrows the LDS tier: no second attempt there
       if (group == kRootGroup && L.req[end].agent == L.noChainAgent) j.flags |= MRP_LL_JOB_HEAVY;
     }
@@ -627,6 +657,18 @@ class SessionWorker {
           any = true;
         }
       if (any) P.conf.assign(jobs.size(), mrp_ll_conflict{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0});
+      if (any && scanFromParent_) {
+        P.bases.assign(jobs.size(), mrp_ll_scan_base{0, 0});
+        P.flagged.assign(jobs.size(), 0);
+        for (size_t q = 0; q < jobs.size(); ++q)
+          if (batch_.ownOk[q]) {
+            const LLRequest& r = L.req[L.reqHead + q];
+            jobs[q].flags |= MRP_LL_JOB_SCAN_FROM_PARENT;
+            P.bases[q] = mrp_ll_scan_base{r.parentCount, r.cleanBefore};
+            P.replacedHold.push_back((*r.context)[r.agent]);
+            P.flagged[q] = 1;
+          }
+      }
     }
     if (deviceCons_ && group != kRootGroup) nameSets(L, P, jobs);
     const int rc = publish(pi, static_cast<int32_t>(jobs.size()), jobs.data(), "mrp_ll_submit");
@@ -761,6 +803,7 @@ class SessionWorker {
     if (L.counted || !L.inst->done()) return;
     writeSolution(*L.inst, plan_.view->sol(gidx_[k]));
     out_.deviceScans += L.inst->deviceScans();
+    out_.incrementalScans += L.inst->incrementalScans();
     finishLive(L, L.inst->hlExpanded(), L.inst->llExpanded(), L.inst->specSearches(), L.inst->llSearches());
   }
 
@@ -866,7 +909,10 @@ class SessionWorker {
     for (size_t q = 0; q < P.res.size(); ++q) {
       ranExpansions_ += P.res[q].expanded;
       ans_.push_back(answerOf(P.res[q], P.outSlot[q], &slotPool_));
-      if (!P.conf.empty() && P.res[q].status == MRP_LL_OK) ans_.back().scan = P.conf[q];
+      if (!P.conf.empty() && P.res[q].status == MRP_LL_OK) {
+        ans_.back().scan = P.conf[q];
+        ans_.back().scanFromParent = P.fromParent(q);
+      }
     }
     const int32_t group = P.group;
     releasePending(pi);
@@ -941,6 +987,7 @@ class SessionWorker {
         out_.expansions += live_[k].inst->llExpanded();
         out_.specSearches += live_[k].inst->specSearches();
         out_.deviceScans += live_[k].inst->deviceScans();
+        out_.incrementalScans += live_[k].inst->incrementalScans();
       }
     out_.specWasted += ranExpansions_ - out_.expansions;
     if (tm_.on) {
@@ -957,7 +1004,10 @@ class SessionWorker {
   // not const: an engine that cannot run chains — no compact tier, a window too small for the chain's focal table —
   // rejects the first one, and this worker goes on with one job per root search
   bool rootChains_;
-  bool deviceScan_;  // children go out through mrp_ll_submit_scan (SolveKnobs::deviceScan, and the engine has the call)
+  // children go out through mrp_ll_submit_node and say what their parent's scan established (SolveKnobs::deviceScanIncremental,
+  // and the engine has the call)
+  bool scanFromParent_;
+  bool deviceScan_;  // children go out through mrp_ll_submit_scan (SolveKnobs::deviceScan, and the engine has the call) — or as above
   const bool deviceCons_;  // children name their constraint sets by slot (the call reserved a constraint store: SolveKnobs::deviceCons)
   const int32_t myWorkgroups_;
   // f2: slots of the engine's device-resident path store, handed to the searches of this worker for their result paths.

@@ -34,6 +34,12 @@ struct LLRequest {            // one pending low-level search of an instance
   int32_t slot;               // position of the answer inside its group
   int32_t group;              // kRootGroup, or the id of the CT node these searches expand; requests of one group are
                               // consecutive and are answered together
+  // A child's search (ECBS): what the parent node's scan established, for an engine that scans the child from it
+  // (mrp_ll_submit_node) — the parent's focalHeuristic, the time of the conflict it is split on (nothing in the parent
+  // conflicts before it), and the parent's path of `agent`, which this search replaces (the entry `context` still holds for
+  // the agent: a plain pointer, the request takes no share in the path).  -1 / null: not known.
+  int32_t parentCount = -1, cleanBefore = -1;
+  const Path* replaced = nullptr;
 };
 constexpr int32_t kRootGroup = -1;
 
@@ -44,6 +50,7 @@ struct LLAnswer {
   PathPtr path;               // valid when status == MRP_LL_OK
   // the conflicts of the node this search completes, when the engine scanned it (mrp_ll_submit_scan): found >= 0
   mrp_ll_conflict scan{-1, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  bool scanFromParent = false;  // ... and it did so from the request's parentCount / cleanBefore / replaced
 };
 
 class Instance {
@@ -71,6 +78,7 @@ class Instance {
   int32_t llSearches() const { return llSearches_; }
   int64_t specSearches() const { return specSearches_; }  // searches issued ahead of their node's pop
   int64_t deviceScans() const { return deviceScans_; }    // committed nodes whose conflicts came with their search
+  int64_t incrementalScans() const { return incrementalScans_; }  // ... those of them that were scanned from their parent's facts
   const PathVec& finalSolution() const { return final_; }
   int64_t remainingLL() const { return capLL_ < 0 ? -1 : std::max<int64_t>(0, capLL_ - llExpanded_); }
   // CT nodes whose children may be computed at the same time (1 = the popped node only, i.e. no speculation)
@@ -297,6 +305,12 @@ class Instance {
       const CTNode& ch = *it->second.child[k];
       next.push_back(LLRequest{it->second.agent[k], ch.constraints[it->second.agent[k]],
                                algo_ == MRP_HL_ECBS ? &ch.solution : nullptr, k, pid});
+      if (algo_ == MRP_HL_ECBS) {
+        LLRequest& r = next.back();
+        r.parentCount = P.focalHeuristic;
+        r.cleanBefore = c.time;
+        r.replaced = P.solution[r.agent].get();
+      }
     }
     if (speculative) specSearches_ += 2;
     return it;
@@ -321,6 +335,7 @@ class Instance {
           ch.LB += a.fmin;
           ch.focalHeuristic = a.scan.count;
           deviceScans_ += 1;
+          if (a.scanFromParent) incrementalScans_ += 1;
           int32_t id = storeNode(chp);
           if (scanned_.size() <= static_cast<size_t>(id)) scanned_.resize(static_cast<size_t>(id) + 1);
           scanned_[id] = ScanNote{a.scan.found ? 1 : 0,
@@ -421,7 +436,7 @@ class Instance {
   std::unordered_map<int32_t, Branch> branches_;  // storage index of a CT node -> its expansion
   std::vector<int32_t> cand_;
   PathVec final_;
-  int64_t hlExpanded_ = 0, llExpanded_ = 0, specSearches_ = 0, deviceScans_ = 0;
+  int64_t hlExpanded_ = 0, llExpanded_ = 0, specSearches_ = 0, deviceScans_ = 0, incrementalScans_ = 0;
   int32_t llSearches_ = 0;
   std::vector<int32_t> scratch_;
 };

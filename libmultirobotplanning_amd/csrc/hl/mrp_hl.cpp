@@ -389,6 +389,7 @@ int mrp_hl_solver_solve_stream(mrp_hl_solver* s, const mrp_hl_options* optIn, in
     st.wasted_ll_expansions += g.specWasted;
     st.root_solved += g.rootSolved;
     st.device_scans += g.deviceScans;
+    st.incremental_scans += g.incrementalScans;
     st.build_seconds += g.buildS;
     st.ll_call_seconds += g.llS;
     st.consume_seconds += g.consumeS;

@@ -53,6 +53,11 @@ struct SolveKnobs {
   // MRP_HL_DEVICE_SCAN=1 (ECBS with a path store): a child's conflicts come back with its low-level search
   // (mrp_ll_submit_scan) instead of being scanned here at commit and at pop time.  Same results; off by default.
   bool deviceScan = false;
+  // MRP_HL_DEVICE_SCAN_INCREMENTAL=1 (ECBS with a path store, an engine that exports mrp_ll_submit_node): the same, and the
+  // child's job also says what the parent's scan established — its conflict count, the time of the conflict it is split
+  // on, the slot of the replaced path — so that the workgroup counts in linear work (MRP_LL_JOB_SCAN_FROM_PARENT).  Same
+  // results; off by default; without the export the driver behaves as with the variable unset.
+  bool deviceScanIncremental = false;
 
   static SolveKnobs read() {
     auto num = [](const char* name, int64_t dflt) {
@@ -87,6 +92,7 @@ struct SolveKnobs {
     k.ringDepth = std::max<int64_t>(0, num("MRP_HL_RING_DEPTH", 0));
     k.activeLimit = isSet("MRP_HL_ACTIVE_LIMIT") ? static_cast<int32_t>(std::max<int64_t>(1, num("MRP_HL_ACTIVE_LIMIT", 1))) : 0;
     k.deviceScan = num("MRP_HL_DEVICE_SCAN", 0) != 0;
+    k.deviceScanIncremental = num("MRP_HL_DEVICE_SCAN_INCREMENTAL", 0) != 0;
     return k;
   }
 };

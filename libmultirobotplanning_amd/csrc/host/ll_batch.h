@@ -13,7 +13,8 @@ struct SubmitArgs {
   mrp_ll_result* results;
   mrp_ll_conflict* conflicts;         // mrp_ll_submit_scan / _sets: one entry per job (what admits flagged jobs), else null
   const mrp_ll_constraint_ref* sets;  // mrp_ll_submit_sets: one entry per job (what admits by-set jobs), else null
-  PackArgs packArgs(int i) const { return PackArgs{conflicts != nullptr, sets ? sets + i : nullptr}; }
+  const mrp_ll_scan_base* bases;      // mrp_ll_submit_node: one entry per job (what admits MRP_LL_JOB_SCAN_FROM_PARENT jobs), else null
+  PackArgs packArgs(int i) const { return PackArgs{conflicts != nullptr, sets ? sets + i : nullptr, bases ? bases + i : nullptr}; }
 };
 
 // Where a packed job's constraint words / path table go in a batch: growable buffers (sessions: the slot sinks of ll_pack.h).

@@ -78,6 +78,7 @@ struct PackEnv {
 struct PackArgs {
   bool scanAllowed = false;                    // the call hands conflicts back (what admits MRP_LL_JOB_SCAN_CONFLICTS jobs)
   const mrp_ll_constraint_ref* ref = nullptr;  // the job's entry of mrp_ll_submit_sets (what admits MRP_LL_JOB_CONSTRAINT_SET jobs)
+  const mrp_ll_scan_base* base = nullptr;      // the job's entry of mrp_ll_submit_node (what admits MRP_LL_JOB_SCAN_FROM_PARENT jobs)
 };
 // The constraint-store slot the job just packed writes (-1: none) and what the mirror holds for it once the job has been
 // accepted (commitSet).
@@ -445,6 +446,8 @@ static inline bool packJob(const PackEnv& env, const mrp_ll_job& j, const PackAr
     }
   }
   const bool scan = (j.flags & MRP_LL_JOB_SCAN_CONFLICTS) != 0;
+  const bool fromParent = (j.flags & MRP_LL_JOB_SCAN_FROM_PARENT) != 0;
+  if (fromParent && (!scan || !args.base)) return false;  // only with a scan, and only through mrp_ll_submit_node
   if (scan) {
     // the conflicts of the node come back through mrp_ll_submit_scan's array alone, and the workgroup scans what it holds:
     // an A*-epsilon search whose context names EVERY other agent's path by its path-store slot (mrp_ll.h)
@@ -452,6 +455,10 @@ static inline bool packJob(const PackEnv& env, const mrp_ll_job& j, const PackAr
     if (!j.path_ids || !j.path_len || !env.pathStoreSlots || j.n_agents < 1 || j.agent_idx < 0 || j.agent_idx >= j.n_agents) return false;
     for (int a = 0; a < j.n_agents; ++a)
       if (a != j.agent_idx && (j.path_ids[a] < 0 || j.path_len[a] < 1)) return false;
+    // from the parent: the searching agent's entry names the slot of the path this search REPLACES (mrp_ll.h)
+    if (fromParent && (j.path_ids[j.agent_idx] < 0 || static_cast<uint32_t>(j.path_ids[j.agent_idx]) >= env.pathStoreSlots ||
+                       j.path_len[j.agent_idx] < 1 || args.base->parent_count < 0 || args.base->clean_before < 0))
+      return false;
   }
   if (j.flags & MRP_LL_JOB_ROOT_CHAIN) {  // the root step of an ECBS conflict tree as one job (mrp_ll.h; ll_device.h kCtxChain)
     const int n = j.n_agents, first = j.agent_idx;
@@ -597,6 +604,14 @@ static inline bool packJob(const PackEnv& env, const mrp_ll_job& j, const PackAr
       d.path_off = static_cast<uint32_t>(cs.size());
       for (int a = 0; a < j.n_agents; ++a)
         cs.push(a != j.agent_idx && j.path_len[a] > 0 ? static_cast<uint32_t>(j.path_ids[a]) : kNoStoreSlot);
+      if (fromParent) {
+        // behind the ids, never among them (the search must not see its own agent's column): the replaced path's slot and
+        // what the caller knows of the parent node (ll_device.h kCtxScanParent)
+        cs.push(static_cast<uint32_t>(j.path_ids[j.agent_idx]));
+        cs.push(static_cast<uint32_t>(args.base->parent_count));
+        cs.push(static_cast<uint32_t>(args.base->clean_before));
+        d.ctx_flags |= kCtxScanParent;
+      }
       if (cs.failed) return false;
       d.ctx_flags |= kCtxById;
       d.n_ctx = static_cast<uint32_t>(j.n_agents);

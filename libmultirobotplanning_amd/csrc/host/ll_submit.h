@@ -6,7 +6,7 @@
 
 namespace {
 
-// a.tag >= 0: a co-worker's call into a session (mrp_ll_submit_tagged / _scan / _sets), serialised by coMu.
+// a.tag >= 0: a co-worker's call into a session (mrp_ll_submit_tagged / _scan / _sets / _node), serialised by coMu.
 int submitJobs(mrp_ll_ctx* ctx, const SubmitArgs& a, int32_t* ticketOut) {
   if (a.tag < 0) return ctx->env.session.active ? sessionSubmit(ctx, a, ticketOut) : batchSubmit(ctx, a, ticketOut);
   std::lock_guard<std::mutex> lock(ctx->coMu);
@@ -52,6 +52,15 @@ int mrp_ll_submit_sets(mrp_ll_ctx* ctx, int32_t tag, int32_t nJobs, const mrp_ll
   if (!ctx->env.session.active) tag = -1;  // batch mode: the tag names nobody
   else if (tag < 0 || tag >= mrp_ll_ctx::kMaxTags) return MRP_LL_E_INVALID;
   return submitJobs(ctx, SubmitArgs{tag, nJobs, jobs, results, conflicts, sets}, ticketOut);
+}
+
+int mrp_ll_submit_node(mrp_ll_ctx* ctx, int32_t tag, int32_t nJobs, const mrp_ll_job* jobs, mrp_ll_result* results,
+                       mrp_ll_conflict* conflicts, const mrp_ll_constraint_ref* sets, const mrp_ll_scan_base* bases,
+                       int32_t* ticketOut) {
+  if (!ctx || !ticketOut || nJobs < 0 || (nJobs > 0 && (!jobs || !results))) return MRP_LL_E_INVALID;
+  if (!ctx->env.session.active) tag = -1;  // batch mode: the tag names nobody
+  else if (tag < 0 || tag >= mrp_ll_ctx::kMaxTags) return MRP_LL_E_INVALID;
+  return submitJobs(ctx, SubmitArgs{tag, nJobs, jobs, results, conflicts, sets, bases}, ticketOut);
 }
 
 int mrp_ll_poll(mrp_ll_ctx* ctx, int32_t ticket, int32_t* doneOut) {

@@ -80,6 +80,11 @@ constexpr uint32_t kCtxHeavy = 64u;
 // conflicts (ll_node_scan.h) and leaves the ten words of an mrp_ll_conflict in the LAST kScanOutHalfs halfwords of the job's
 // host output area (found = -1, the rest 0, when the search did not end ST_OK).  `reserved` = the searching agent's index.
 constexpr uint32_t kCtxScan = 128u;
+// ctx_flags bit 8 (MRP_LL_JOB_SCAN_FROM_PARENT, mrp_ll_submit_node; only with kCtxScan and kCtxById): the scan starts from
+// what the caller knows of the PARENT node.  Behind the n_ctx ids at cons[path_off] stand three more words: the path-store
+// slot of the replaced path (the searching agent's at the parent; it is NOT part of the focal table), the parent's number of
+// conflicts, and a time before which the parent has none (ll_node_scan.h nodeScanFromParent).
+constexpr uint32_t kCtxScanParent = 256u;
 constexpr uint32_t kScanOutHalfs = 32;                             // (64 bytes: the area stays aligned for the path in front of it)
 constexpr uint32_t kChainEntryWords = 8;
 constexpr uint32_t kChainMaxAgents = 128;                          // (what the compact tier's focal context holds: two 64-lane row loads)

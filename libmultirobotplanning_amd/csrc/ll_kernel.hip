@@ -20,7 +20,8 @@
 //                      arenaAttempt), publishPath and runChain (ECBS root chains)
 //   ll_ta.h            TaEnv, runTaArena / runJobTA, runJobTaEps: the task-assignment low levels
 //   ll_sipp.h          SIPP: its tiers, sippLoop, runSipp, processSippJob
-//   ll_node_scan.h     nodeScan: the conflicts of the conflict-tree node a search has completed (also compiled for the CPU)
+//   ll_node_scan.h     nodeScan, nodeScanFromParent: the conflicts of the conflict-tree node a search has completed (also
+//                      compiled for the CPU)
 //   here               scanNode, processJob, batchLoop, publishDone, residentLoop, the eleven kernels, the launchers
 //
 // Reference semantics implemented (file:line in the reference project, libMultiRobotPlanning):
@@ -56,7 +57,36 @@ namespace mrp {
 // job in the window's control block, behind the job descriptor and the result record, and leaves its answer behind that:
 // the one part of the window every launch has, also one without the compact tier.
 constexpr uint32_t kScanJobOff = ct::oCtl + sizeof(DevJob) + sizeof(DevResult), kScanOutOff = kScanJobOff + sizeof(ns::NsJob);
-static_assert(kScanJobOff % 8 == 0 && kScanOutOff + ns::kOutWords * 4u <= ct::oJob, "the scan's blocks fit the control block");
+// A kCtxScanParent job (mrp_ll_submit_node) scans from what the caller knows of the parent node: that block lies ON the
+// result record's staging block, which only endJob uses, behind the scan (MRP_LL_ASTAR_EPS_TA reads it back in front of it).
+constexpr uint32_t kScanBaseOff = ct::oCtl + sizeof(DevJob);
+static_assert(kScanJobOff % 8 == 0 && kScanOutOff + ns::kOutWords * 4u <= ct::oJob && kScanBaseOff % 8 == 0 &&
+                  sizeof(ns::NsBase) <= sizeof(DevResult),
+              "the scan's blocks fit the control block");
+// The scan of a kCtxScanParent job, behind scanNode's staging of the NsJob.  `words`: the three staged words behind the
+// context's ids (ll_device.h) — the replaced path's slot, the parent's conflict count, the time before which it has none.
+// A slot the store does not have gets the full scan.  A function of its own, with plain values for arguments, so that the
+// kernels' code in front of the call is what it is without it.
+__device__ __attribute__((noinline)) void scanNodeFromParent(uint8_t* smem, const uint32_t* words, const uint16_t* store,
+                                                              uint32_t storeStride, uint32_t storeSlots) {
+  const uint32_t sid = rfl(hostLoad32(words));
+  const uint64_t oldSlot = (uint64_t)(store + (size_t)(sid < storeSlots ? sid : 0u) * storeStride);
+  const uint32_t parentCount = rfl(hostLoad32(words + 1)), cleanBefore = rfl(hostLoad32(words + 2));
+  auto nb = (__attribute__((address_space(3))) uint32_t*)((wv::Lds)smem + kScanBaseOff);  // the NsBase, word by word
+  static_assert(offsetof(ns::NsBase, oldSlot) == 0 && offsetof(ns::NsBase, oldCap) == 8 && offsetof(ns::NsBase, parentCount) == 12 &&
+                    offsetof(ns::NsBase, cleanBefore) == 16 && sizeof(ns::NsBase) == 24, "NsBase as written here");
+  nb[0] = (uint32_t)oldSlot;
+  nb[1] = (uint32_t)(oldSlot >> 32);
+  nb[2] = storeStride - 1u;
+  nb[3] = parentCount;
+  nb[4] = cleanBefore;
+  nb[5] = 0u;
+  __syncthreads();
+  if (sid < storeSlots && storeStride != 0u)
+    ns::nodeScanFromParent<kScanJobOff, kScanOutOff, kScanBaseOff>((wv::Lds)smem);
+  else
+    ns::nodeScan<kScanJobOff, kScanOutOff>((wv::Lds)smem);
+}
 template <bool BG, int TIERS>
 DEVI void scanNode(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t* arenaSlot, int32_t status, uint32_t nStates,
                    const uint16_t* outPath, uint16_t* pathDst) {
@@ -86,7 +116,10 @@ DEVI void scanNode(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_
     for (uint32_t q = 0; q < sizeof(ns::NsJob) / 4; ++q) w32[q] = src[q];
   }
   __syncthreads();
-  ns::nodeScan<kScanJobOff, kScanOutOff>((wv::Lds)smem);
+  if (byId && (J.ctx_flags & kCtxScanParent))
+    scanNodeFromParent(smem, P.cons + J.path_off + J.n_ctx, P.path_store, P.path_store_stride, P.path_store_slots);
+  else
+    ns::nodeScan<kScanJobOff, kScanOutOff>((wv::Lds)smem);
   __syncthreads();
   auto r32 = (__attribute__((address_space(3))) const uint32_t*)((wv::Lds)smem + kScanOutOff);
   if (lane < ns::kOutWords) hostStore32(dst + lane, r32[lane]);

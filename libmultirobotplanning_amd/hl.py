@@ -48,7 +48,8 @@ class mrp_hl_batch_stats(ctypes.Structure):
                 ("ll_expansions", ctypes.c_int64), ("solved", ctypes.c_int64), ("build_seconds", ctypes.c_double),
                 ("ll_call_seconds", ctypes.c_double), ("consume_seconds", ctypes.c_double),
                 ("speculative_searches", ctypes.c_int64), ("wasted_ll_expansions", ctypes.c_int64),
-                ("root_solved", ctypes.c_int64), ("device_scans", ctypes.c_int64)]
+                ("root_solved", ctypes.c_int64), ("device_scans", ctypes.c_int64),
+                ("incremental_scans", ctypes.c_int64)]
 
 
 class mrp_hl_sipp_solution(ctypes.Structure):
@@ -321,7 +322,7 @@ class BatchSolver:
                      ll_expansions=st.ll_expansions, solved=st.solved, build_seconds=st.build_seconds,
                      ll_call_seconds=st.ll_call_seconds, consume_seconds=st.consume_seconds,
                      speculative_searches=st.speculative_searches, wasted_ll_expansions=st.wasted_ll_expansions,
-                     root_solved=st.root_solved, device_scans=st.device_scans)
+                     root_solved=st.root_solved, device_scans=st.device_scans, incremental_scans=st.incremental_scans)
         return (None if raw else self.results_of(prep)), stats
 
     def solve_stream(self, preps, algo: int = ECBS, w: float = 1.3, max_ll_expansions: int = -1,
@@ -344,7 +345,7 @@ class BatchSolver:
                     ll_expansions=st.ll_expansions, solved=st.solved, build_seconds=st.build_seconds,
                     ll_call_seconds=st.ll_call_seconds, consume_seconds=st.consume_seconds,
                     speculative_searches=st.speculative_searches, wasted_ll_expansions=st.wasted_ll_expansions,
-                    root_solved=st.root_solved, device_scans=st.device_scans, batches=n)
+                    root_solved=st.root_solved, device_scans=st.device_scans, incremental_scans=st.incremental_scans, batches=n)
 
     def result_arrays(self, prep) -> Dict[str, np.ndarray]:
         """The results of a prepared batch as numpy arrays (status, cost, makespan, hl_expanded, ll_expanded, ll_searches,

@@ -8,7 +8,7 @@ missing or no GPU is visible, construction raises.
 import ctypes
 import os
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -19,6 +19,7 @@ ASTAR, ASTAR_EPS, SIPP, ASTAR_TA, ASTAR_EPS_TA = 0, 1, 2, 3, 4
 JOB_STORE_RESULT, JOB_NO_GOAL, JOB_ROOT_CHAIN, JOB_HEAVY = 1, 2, 4, 8  # mrp_ll_job.flags (include/mrp_ll.h)
 JOB_SCAN_CONFLICTS = 16  # mrp_ll_job.flags: mrp_ll_submit_scan also returns the conflicts of the node the job completes
 JOB_CONSTRAINT_SET = 32  # mrp_ll_job.flags: mrp_ll_submit_sets' sets[i] names the agent's set in the device constraint store
+JOB_SCAN_FROM_PARENT = 64  # mrp_ll_job.flags: mrp_ll_submit_node's bases[i] holds what the parent node's scan established
 SCAN_UNTOUCHED = -2      # search_batch_scan: what every field of an entry the engine did not write still holds
 OK, NO_SOLUTION, CAP_EXPANSIONS, CAP_NODES, CAP_HORIZON, BAD_JOB, PATH_TRUNCATED, CAP_FOCAL = range(8)
 ACTION_NAMES = ["Up", "Down", "Left", "Right", "Wait"]  # example/ecbs.cpp:49-55
@@ -62,6 +63,10 @@ class mrp_ll_constraint_ref(ctypes.Structure):
     _fields_ = [("base_set_id", ctypes.c_int32), ("result_set_id", ctypes.c_int32)]
 
 
+class mrp_ll_scan_base(ctypes.Structure):
+    _fields_ = [("parent_count", ctypes.c_int32), ("clean_before", ctypes.c_int32)]
+
+
 class mrp_ll_stats(ctypes.Structure):
     _fields_ = [("launches", ctypes.c_int64), ("jobs", ctypes.c_int64), ("expansions", ctypes.c_int64),
                 ("nodes_created", ctypes.c_int64), ("migrated", ctypes.c_int64), ("kernel_ms", ctypes.c_double),
@@ -80,7 +85,8 @@ EXPORTS = ["mrp_ll_create", "mrp_ll_destroy", "mrp_ll_last_error", "mrp_ll_uploa
            "mrp_ll_upload_heuristic", "mrp_ll_session_begin_tiers", "mrp_ll_session_tiers_geometry",
            "mrp_ll_session_begin_tiers_gated", "mrp_ll_submit_tagged", "mrp_ll_poll_any_tagged",
            "mrp_ll_compute_heuristics", "mrp_ll_read_heuristic", "mrp_ll_heuristic_lookup", "mrp_ll_submit_scan",
-           "mrp_ll_constraint_store_reserve", "mrp_ll_submit_sets", "mrp_ll_session_front_tables"]
+           "mrp_ll_constraint_store_reserve", "mrp_ll_submit_sets", "mrp_ll_session_front_tables",
+           "mrp_ll_submit_node"]
 
 _lib = None
 
@@ -167,6 +173,10 @@ def load_library(path: Optional[str] = None):
     lib.mrp_ll_submit_sets.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(mrp_ll_job),
                                        ctypes.POINTER(mrp_ll_result), ctypes.POINTER(mrp_ll_conflict),
                                        ctypes.POINTER(mrp_ll_constraint_ref), I32P]
+    lib.mrp_ll_submit_node.restype = ctypes.c_int
+    lib.mrp_ll_submit_node.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(mrp_ll_job),
+                                       ctypes.POINTER(mrp_ll_result), ctypes.POINTER(mrp_ll_conflict),
+                                       ctypes.POINTER(mrp_ll_constraint_ref), ctypes.POINTER(mrp_ll_scan_base), I32P]
     if path is None:
         _lib = lib
     return lib
@@ -199,6 +209,9 @@ class LLJob:
     # MRP_LL_JOB_CONSTRAINT_SET job, and the call that carries it goes through mrp_ll_submit_sets.
     base_set_id: int = -1
     result_set_id: int = -1
+    # MRP_LL_JOB_SCAN_FROM_PARENT (with scan_conflicts): (parent_count, clean_before) of the parent node; path_ids[agent_idx]
+    # then names the slot of the path this search replaces.  The call goes through mrp_ll_submit_node.
+    scan_base: Optional[Tuple[int, int]] = None
 
 
 @dataclass
@@ -285,7 +298,8 @@ class LowLevelEngine:
             cj.result_path_id = j.result_path_id
             cj.flags = (JOB_STORE_RESULT if j.result_path_id >= 0 else 0) | (JOB_NO_GOAL if j.goal is None else 0) | \
                 (JOB_HEAVY if j.heavy else 0) | (JOB_SCAN_CONFLICTS if j.scan_conflicts else 0) | \
-                (JOB_CONSTRAINT_SET if (j.base_set_id >= 0 or j.result_set_id >= 0) else 0)
+                (JOB_CONSTRAINT_SET if (j.base_set_id >= 0 or j.result_set_id >= 0) else 0) | \
+                (JOB_SCAN_FROM_PARENT if j.scan_base is not None else 0)
             cj.heuristic_id = j.heuristic_id
             if j.path_ids is not None:
                 ids = np.ascontiguousarray(np.asarray(j.path_ids, dtype=np.int32))
@@ -317,7 +331,7 @@ class LowLevelEngine:
     def search_batch(self, jobs: Sequence[LLJob], states_cap: Optional[int] = None) -> List[LLResult]:
         n = len(jobs)
         cap = states_cap or self.max_horizon
-        if any(j.base_set_id >= 0 or j.result_set_id >= 0 for j in jobs):
+        if any(j.base_set_id >= 0 or j.result_set_id >= 0 or j.scan_base is not None for j in jobs):
             return self.wait_sets(self.submit_sets(jobs, states_cap=cap), want_conflicts=False)[0]
         cjobs, cres, (keep, states, actions, costs) = self._marshal(jobs, cap)
         self._check(self._lib.mrp_ll_search_batch(self._h, n, cjobs, cres), "mrp_ll_search_batch")
@@ -326,7 +340,7 @@ class LowLevelEngine:
     def submit_sets(self, jobs: Sequence[LLJob], states_cap: Optional[int] = None, tag: int = 0):
         """mrp_ll_submit_sets, in a batch or inside any session: returns a handle for wait_sets.  Jobs with base_set_id /
         result_set_id name their constraint sets in the device store; jobs with scan_conflicts get their conflicts (the
-        conflicts array is NULL when no job asks for them)."""
+        conflicts array is NULL when no job asks for them).  When a job carries scan_base the call is mrp_ll_submit_node."""
         n = len(jobs)
         cap = states_cap or self.max_horizon
         cjobs, cres, bufs = self._marshal(jobs, cap)
@@ -340,6 +354,14 @@ class LowLevelEngine:
         for i, j in enumerate(jobs):
             sets[i].base_set_id, sets[i].result_set_id = j.base_set_id, j.result_set_id
         ticket = ctypes.c_int32(-1)
+        if any(j.scan_base is not None for j in jobs):
+            bases = (mrp_ll_scan_base * max(n, 1))()
+            for i, j in enumerate(jobs):
+                if j.scan_base is not None:
+                    bases[i].parent_count, bases[i].clean_before = j.scan_base
+            self._check(self._lib.mrp_ll_submit_node(self._h, tag, n, cjobs, cres, conf, sets, bases, ctypes.byref(ticket)),
+                        "mrp_ll_submit_node")
+            return (ticket.value, n, cap, cjobs, cres, conf, (sets, bases), bufs)
         self._check(self._lib.mrp_ll_submit_sets(self._h, tag, n, cjobs, cres, conf, sets, ctypes.byref(ticket)),
                     "mrp_ll_submit_sets")
         return (ticket.value, n, cap, cjobs, cres, conf, sets, bufs)
@@ -361,7 +383,7 @@ class LowLevelEngine:
         with a path); every field of a job without the flag keeps SCAN_UNTOUCHED, the value the array was filled with."""
         n = len(jobs)
         cap = states_cap or self.max_horizon
-        if any(j.base_set_id >= 0 or j.result_set_id >= 0 for j in jobs):
+        if any(j.base_set_id >= 0 or j.result_set_id >= 0 or j.scan_base is not None for j in jobs):
             return self.wait_sets(self.submit_sets(jobs, states_cap=cap, tag=tag))
         cjobs, cres, (keep, states, actions, costs) = self._marshal(jobs, cap)
         conf = (mrp_ll_conflict * max(n, 1))()
