@@ -315,6 +315,81 @@ int mrp_ll_read_heuristic(mrp_ll_ctx* ctx, int32_t heuristic_id, int32_t* dist);
 int mrp_ll_heuristic_lookup(mrp_ll_ctx* ctx, int32_t n, const int32_t* heuristic_ids, const int32_t* cells_xy /* [n][2] */,
                             int32_t* out /* [n] */);
 
+/* ---- min-cost task assignment and its next-best series -------------------------------------------------------
+ * What sits between that cost matrix and the task-assignment searches: Assignment::solve (assignment.hpp:81-118) and
+ * the ordered series NextBestAssignment::solve / nextSolution (next_best_assignment.hpp:49-122) that
+ * Environment::nextTaskAssignment (example/cbs_ta.cpp:442-456) asks for every new root of the conflict tree.  The
+ * reference solves a min-cost flow with Boost.Graph; here ONE wavefront solves one problem (shortest augmenting paths
+ * with potentials, integers only, exact) and a batch of problems is ONE kernel launch.
+ *
+ * A problem: n_agents x n_tasks, 0 .. 64 each.  An edge agent -> task exists where the cost is not
+ * MRP_LL_ASSIGN_NO_EDGE; a cost is 0 .. 16 777 215 (2^24 - 1).  The result is a matching of MAXIMUM CARDINALITY and,
+ * among those, of MINIMUM TOTAL COST; an agent may stay without a task (task_of = -1).  (Not "agents row by row": with
+ * a0->t0: 2 and a1->t0: 1 the answer is {a1: t0}, cost 1.)
+ * The cost rows come from `cost`, or — cost == NULL, the gather form — straight from heuristic tables that live on the
+ * device: cost(a, t) = table heuristic_ids[t] at the cell starts_xy[a], for the tasks t whose bit is set in allowed[a]
+ * (the goals agent a may take, cbs_ta.cpp:272-279; NULL = all).  All tables of one problem belong to one map.
+ * DIFFERENCE from the reference: an unreachable goal (the table says "no path") is NO EDGE — such a pair cannot be
+ * chosen; the reference hands INT_MAX to the flow solver as a cost and then fails in the search.
+ * Constraints (a node of the next-best series; NULL / 0 = none): forbidden[a] is a mask of tasks agent a must not get;
+ * mode[a] is MRP_LL_ASSIGN_FREE, a task the agent is forced to (>= 0), MRP_LL_ASSIGN_NO_TASK (must stay without) or
+ * MRP_LL_ASSIGN_SOME_TASK (must get one); min_matching is the cardinality the matching must reach.
+ * status: MRP_LL_OK; MRP_LL_NO_SOLUTION — infeasible: a forced pair has no edge or is forbidden, two agents are forced to
+ * one task, a must-get agent cannot get one, or fewer than min_matching pairs (matched = 0, cost = 0, task_of all -1);
+ * MRP_LL_BAD_JOB — the problem was rejected on the host and not run, the rest of the batch is unaffected: a dimension
+ * outside 0 .. 64, a cost outside 0 .. 2^24 - 1, a forced task >= n_tasks or an unknown mode, min_matching outside
+ * 0 .. 64, a NULL array the form needs, an unknown heuristic id, a start outside its table's map, tables of different
+ * maps.  A problem's result depends on the problem alone, never on its place in the batch.
+ * n_agents == 0 or n_tasks == 0 is solved with 0 pairs and cost 0. */
+#define MRP_LL_ASSIGN_NO_EDGE INT32_MAX
+#define MRP_LL_ASSIGN_FREE (-1)        /* mode[a]; >= 0: forced to that task */
+#define MRP_LL_ASSIGN_NO_TASK (-2)     /* must stay without a task */
+#define MRP_LL_ASSIGN_SOME_TASK (-3)   /* must get a task */
+typedef struct mrp_ll_assign_problem {
+  int32_t n_agents, n_tasks;
+  const int32_t* cost;            /* [n_agents][n_tasks], or NULL: the gather form below */
+  const int32_t* heuristic_ids;   /* [n_tasks]      gather form */
+  const int32_t* starts_xy;       /* [n_agents][2]  gather form */
+  const uint64_t* allowed;        /* [n_agents] or NULL = all;  gather form */
+  const uint64_t* forbidden;      /* [n_agents] or NULL */
+  const int32_t* mode;            /* [n_agents] or NULL = all free */
+  int32_t min_matching;           /* 0 = none */
+} mrp_ll_assign_problem;
+typedef struct mrp_ll_assign_result {
+  int32_t status;                 /* MRP_LL_OK | MRP_LL_NO_SOLUTION (infeasible) | MRP_LL_BAD_JOB */
+  int32_t matched;                /* pairs */
+  int64_t cost;
+  int32_t* task_of;               /* caller buffer [n_agents]; -1 = none */
+} mrp_ll_assign_result;
+/* n problems in ONE launch, whatever n is (n == 0 succeeds without one).  MRP_LL_E_INVALID: a NULL argument (also a
+ * NULL task_of of a problem with agents).  MRP_LL_E_BUSY while a session is active or a batch is in flight, as
+ * mrp_ll_heuristic_lookup. */
+int mrp_ll_assign_batch(mrp_ll_ctx* ctx, int32_t n, const mrp_ll_assign_problem* problems, mrp_ll_assign_result* results);
+
+/* The next-best series: every matching of the optimum's cardinality K, each exactly once, in non-decreasing order of
+ * total cost.  Many series advance together, because a batched conflict-tree driver asks for "the next assignment" of
+ * whichever instances just exhausted a root.
+ * mrp_ll_assign_series_create copies n problems (mode, forbidden and min_matching must be unset: MRP_LL_E_INVALID
+ * otherwise, and for a problem mrp_ll_assign_batch would reject) and solves the n optima in one launch.  A gather-form
+ * series keeps reading the device's tables for every later step: its cost matrix never visits the host, and its
+ * heuristic ids must stay valid while it lives.
+ * mrp_ll_assign_series_next pops the cheapest open node of each of the n series (distinct: MRP_LL_E_INVALID otherwise),
+ * hands its matching back and solves all children of all n pops in ONE launch (next_best_assignment.hpp:79-119: for
+ * every agent i not fixed by the node, in index order, the agents before i keep what the popped matching gave them and
+ * agent i must differ; a child that is infeasible or has fewer than K pairs is dropped).  An exhausted series returns
+ * MRP_LL_NO_SOLUTION with matched = 0 and keeps doing so; a series whose K is 0 returns the empty matching once.
+ * ORDER AMONG EQUAL COSTS: the series pops the node that was created first.  This rule — and the lowest-lane rule of
+ * the wave program for equally near tasks — replaces the accidental order of Boost's path search in the reference;
+ * with it the whole series is a function of the problem alone.
+ * Both calls: MRP_LL_E_BUSY as mrp_ll_assign_batch.  A series belongs to the context that created it and must be
+ * destroyed before that context. */
+typedef struct mrp_ll_assign_series mrp_ll_assign_series;
+int mrp_ll_assign_series_create(mrp_ll_ctx* ctx, int32_t n, const mrp_ll_assign_problem* problems,
+                                mrp_ll_assign_series** out /* [n] */);
+int mrp_ll_assign_series_next(mrp_ll_ctx* ctx, int32_t n, mrp_ll_assign_series* const* series,
+                              mrp_ll_assign_result* results /* [n] */);
+void mrp_ll_assign_series_destroy(mrp_ll_assign_series* series);
+
 /* Copies every map uploaded so far to the device now (otherwise done lazily by the next submit / session_begin). */
 int mrp_ll_sync_maps(mrp_ll_ctx* ctx);
 

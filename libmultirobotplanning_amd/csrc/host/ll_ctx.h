@@ -19,6 +19,7 @@
 #include "../heur_layout.h"
 #include "../ll_device.h"
 #include "../ll_launch.h"
+#include "assign_pack.h"
 #include "ll_pack.h"
 
 namespace {
@@ -233,6 +234,8 @@ struct mrp_ll_ctx {
   size_t scanDevCap = 0;
   hipStream_t scanStream = nullptr;  // ... and the scan's own stream: a session's resident kernel occupies tickets[0].stream
   std::vector<uint16_t> scanStates;
+  mrp::host::AssignStaging assignStaging;  // mrp_ll_assign_batch / _series_*: the packed batch (kept for its capacity)
+  std::vector<uint32_t> assignOut;         // ... and its result records
 };
 
 namespace {

@@ -1,11 +1,13 @@
-// Everything the host side of the engine launches: the parameter records of the conflict-scan and heuristic kernels and the
-// prototypes of every host-callable function the .hip files define.  Included by ll_kernel.hip, conflict_kernel.hip,
-// heur_kernel.hip (which define them) and by mrp_ll_host.cpp (which calls them): one declaration, checked on both sides.
+// Everything the host side of the engine launches: the parameter records of the conflict-scan, heuristic and assignment
+// kernels and the prototypes of every host-callable function the .hip files define.  Included by ll_kernel.hip,
+// conflict_kernel.hip, heur_kernel.hip, assign_kernel.hip (which define them) and by mrp_ll_host.cpp (which calls them):
+// one declaration, checked on both sides.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/mrp_ll.h"
+#include "assign_layout.h"
 #include "heur_layout.h"
 #include "ll_device.h"
 
@@ -35,6 +37,13 @@ struct LookupParams {
   int32_t* out;               // [n]: the entry, INT32_MAX where the table says 0xFFFF
   uint32_t n;
 };
+struct AssignParams {
+  const uint32_t* maps;       // the maps buffer: the gather form reads the tasks' heuristic tables
+  const as::AssignJob* jobs;  // [n]
+  const uint32_t* data;       // the staged words the jobs' offsets count in
+  uint32_t* out;              // the result records
+  uint32_t n;
+};
 
 }  // namespace mrp
 
@@ -55,4 +64,6 @@ hipError_t mrp_ll_launch_conflict(const mrp::ConflictParams* P, hipStream_t stre
 // heur_kernel.hip
 hipError_t mrp_ll_launch_heur_bfs(const mrp::HeurParams* P, uint32_t ldsBytes, hipStream_t stream);
 hipError_t mrp_ll_launch_heur_lookup(const mrp::LookupParams* P, hipStream_t stream);
+// assign_kernel.hip
+hipError_t mrp_ll_launch_assign(const mrp::AssignParams* P, uint32_t ldsBytes, hipStream_t stream);
 }

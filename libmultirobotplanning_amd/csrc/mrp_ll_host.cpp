@@ -5,6 +5,8 @@
 //   host/ll_ctx.h           mrp_ll_ctx, tickets, the session ring, the per-job record and its collection
 //   host/ll_maps.h          the maps buffer: uploads, copies to the device, release
 //   host/ll_heur_host.h     heuristic tables (upload, compute, read, lookup) and the stand-alone conflict scan
+//   host/ll_assign_host.h   min-cost task assignment and its next-best series, with host/assign_pack.h (HIP-free: problems
+//                           -> device words and back) and host/assign_series.h (HIP-free: open list and partition)
 //   host/ll_stores.h        path store, constraint store, SIPP tables
 //   host/ll_batch.h         batch mode: launch parameters, submit, wait
 //   host/ll_session.h       session mode: begin (allocation, reset, launch), end, heartbeat
@@ -15,6 +17,7 @@
 #include "host/ll_ctx.h"
 #include "host/ll_maps.h"
 #include "host/ll_heur_host.h"
+#include "host/ll_assign_host.h"
 #include "host/ll_stores.h"
 #include "host/ll_batch.h"
 #include "host/ll_session.h"

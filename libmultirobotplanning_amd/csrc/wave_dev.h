@@ -85,6 +85,27 @@ WV_FN V shr1(V v) { return V((uint32_t)__builtin_amdgcn_update_dpp((int)v.v, (in
 WV_FN V rowShl1(V v, uint32_t fill) { return V((uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v.v, 0x101, 0xF, 0xF, false)); }
 // lane i receives the value of lane src[i] (0 .. 63): ds_bpermute_b32 — the crossbar of the LDS unit, no LDS memory
 WV_FN V bpermute(V v, V src) { return V((uint32_t)__builtin_amdgcn_ds_bpermute((int)((src.v & 63u) << 2), (int)v.v)); }
+// the predicate whose lanes are the set bits of a wave-uniform mask
+WV_FN B laneMask(uint64_t m) { return B{m}; }
+// The smallest value of the 64 lanes, as a scalar.  Four row_shr steps (1, 2, 4, 8: a lane without a source keeps all
+// ones) leave every 16-lane row's minimum in its last lane; the four row results meet in scalar registers.
+WV_FN uint32_t waveMinU32(V v) {
+  uint32_t x = v.v;
+#define WV_MIN_STEP(ctrl)                                                                              \
+  {                                                                                                    \
+    const uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFFu, (int)x, ctrl, 0xF, 0xF, false); \
+    x = t < x ? t : x;                                                                                 \
+  }
+  WV_MIN_STEP(0x111)
+  WV_MIN_STEP(0x112)
+  WV_MIN_STEP(0x114)
+  WV_MIN_STEP(0x118)
+#undef WV_MIN_STEP
+  const uint32_t a = __builtin_amdgcn_readlane(x, 15), b = __builtin_amdgcn_readlane(x, 31);
+  const uint32_t c = __builtin_amdgcn_readlane(x, 47), d = __builtin_amdgcn_readlane(x, 63);
+  const uint32_t ab = a < b ? a : b, cd = c < d ? c : d;
+  return ab < cd ? ab : cd;
+}
 WV_FN V clz(V v) { return V((uint32_t)__builtin_clz(v.v)); }          // v != 0
 WV_FN V popc(V v) { return V((uint32_t)__builtin_popcount(v.v)); }
 WV_FN float uintAsFloat(uint32_t v) { return __uint_as_float(v); }

@@ -38,6 +38,24 @@ WV_FN uint32_t first(V v) { return __builtin_amdgcn_readfirstlane(v); }
 // v with lane `lane` replaced by val (both wave-uniform): v_writelane_b32 (this clang has no builtin for the intrinsic)
 extern "C" __device__ int mrp_llvm_writelane(int val, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
 WV_FN V writelane(V v, uint32_t val, uint32_t lane) { return (uint32_t)mrp_llvm_writelane((int)val, (int)lane, (int)v); }
+WV_FN B laneMask(uint64_t m) { return ((m >> threadIdx.x) & 1u) != 0u; }  // this lane's bit of a wave-uniform mask
+WV_FN uint32_t waveMinU32(V v) {  // the smallest value of the 64 lanes (wave_dev.h)
+  uint32_t x = v;
+#define WV_MIN_STEP(ctrl)                                                                              \
+  {                                                                                                    \
+    const uint32_t t = (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFFu, (int)x, ctrl, 0xF, 0xF, false); \
+    x = t < x ? t : x;                                                                                 \
+  }
+  WV_MIN_STEP(0x111)
+  WV_MIN_STEP(0x112)
+  WV_MIN_STEP(0x114)
+  WV_MIN_STEP(0x118)
+#undef WV_MIN_STEP
+  const uint32_t a = __builtin_amdgcn_readlane(x, 15), b = __builtin_amdgcn_readlane(x, 31);
+  const uint32_t c = __builtin_amdgcn_readlane(x, 47), d = __builtin_amdgcn_readlane(x, 63);
+  const uint32_t ab = a < b ? a : b, cd = c < d ? c : d;
+  return ab < cd ? ab : cd;
+}
 WV_FN V shr1(V v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, 0x138, 0xF, 0xF, false); }
 // lane i of every 16-lane row receives lane i + 1's value; the last lane of a row receives `fill`
 WV_FN V rowShl1(V v, uint32_t fill) { return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x101, 0xF, 0xF, false); }

@@ -24,7 +24,11 @@ SCAN_UNTOUCHED = -2      # search_batch_scan: what every field of an entry the e
 OK, NO_SOLUTION, CAP_EXPANSIONS, CAP_NODES, CAP_HORIZON, BAD_JOB, PATH_TRUNCATED, CAP_FOCAL = range(8)
 ACTION_NAMES = ["Up", "Down", "Left", "Right", "Wait"]  # example/ecbs.cpp:49-55
 
+ASSIGN_NO_EDGE = 2 ** 31 - 1  # MRP_LL_ASSIGN_NO_EDGE
+ASSIGN_FREE, ASSIGN_NO_TASK, ASSIGN_SOME_TASK = -1, -2, -3  # mrp_ll_assign_problem.mode[a]; >= 0: forced to that task
+
 I32P = ctypes.POINTER(ctypes.c_int32)
+U64P = ctypes.POINTER(ctypes.c_uint64)
 
 
 class mrp_ll_options(ctypes.Structure):
@@ -67,6 +71,15 @@ class mrp_ll_scan_base(ctypes.Structure):
     _fields_ = [("parent_count", ctypes.c_int32), ("clean_before", ctypes.c_int32)]
 
 
+class mrp_ll_assign_problem(ctypes.Structure):
+    _fields_ = [("n_agents", ctypes.c_int32), ("n_tasks", ctypes.c_int32), ("cost", I32P), ("heuristic_ids", I32P),
+                ("starts_xy", I32P), ("allowed", U64P), ("forbidden", U64P), ("mode", I32P), ("min_matching", ctypes.c_int32)]
+
+
+class mrp_ll_assign_result(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("matched", ctypes.c_int32), ("cost", ctypes.c_int64), ("task_of", I32P)]
+
+
 class mrp_ll_stats(ctypes.Structure):
     _fields_ = [("launches", ctypes.c_int64), ("jobs", ctypes.c_int64), ("expansions", ctypes.c_int64),
                 ("nodes_created", ctypes.c_int64), ("migrated", ctypes.c_int64), ("kernel_ms", ctypes.c_double),
@@ -86,7 +99,8 @@ EXPORTS = ["mrp_ll_create", "mrp_ll_destroy", "mrp_ll_last_error", "mrp_ll_uploa
            "mrp_ll_session_begin_tiers_gated", "mrp_ll_submit_tagged", "mrp_ll_poll_any_tagged",
            "mrp_ll_compute_heuristics", "mrp_ll_read_heuristic", "mrp_ll_heuristic_lookup", "mrp_ll_submit_scan",
            "mrp_ll_constraint_store_reserve", "mrp_ll_submit_sets", "mrp_ll_session_front_tables",
-           "mrp_ll_submit_node"]
+           "mrp_ll_submit_node", "mrp_ll_assign_batch", "mrp_ll_assign_series_create", "mrp_ll_assign_series_next",
+           "mrp_ll_assign_series_destroy"]
 
 _lib = None
 
@@ -177,6 +191,17 @@ def load_library(path: Optional[str] = None):
     lib.mrp_ll_submit_node.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(mrp_ll_job),
                                        ctypes.POINTER(mrp_ll_result), ctypes.POINTER(mrp_ll_conflict),
                                        ctypes.POINTER(mrp_ll_constraint_ref), ctypes.POINTER(mrp_ll_scan_base), I32P]
+    lib.mrp_ll_assign_batch.restype = ctypes.c_int
+    lib.mrp_ll_assign_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(mrp_ll_assign_problem),
+                                        ctypes.POINTER(mrp_ll_assign_result)]
+    lib.mrp_ll_assign_series_create.restype = ctypes.c_int
+    lib.mrp_ll_assign_series_create.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(mrp_ll_assign_problem),
+                                                ctypes.POINTER(ctypes.c_void_p)]
+    lib.mrp_ll_assign_series_next.restype = ctypes.c_int
+    lib.mrp_ll_assign_series_next.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p),
+                                              ctypes.POINTER(mrp_ll_assign_result)]
+    lib.mrp_ll_assign_series_destroy.restype = None
+    lib.mrp_ll_assign_series_destroy.argtypes = [ctypes.c_void_p]
     if path is None:
         _lib = lib
     return lib
@@ -226,6 +251,35 @@ class LLResult:
     tier: int = 0
     action_costs: List[int] = field(default_factory=list)
     n_states: int = 0  # mrp_ll_result.n_states as the library left it (0 unless a path came back)
+
+
+@dataclass
+class AssignResult:
+    status: int          # OK, NO_SOLUTION (infeasible; an exhausted series) or BAD_JOB
+    matched: int         # pairs
+    cost: int
+    task_of: List[int]   # per agent, -1 = none
+
+
+class AssignmentSeries:
+    """One next-best series (mrp_ll_assign_series_*): every matching of the optimum's cardinality once, in non-decreasing
+    order of cost; then NO_SOLUTION with matched = 0, again and again.  Made by LowLevelEngine.assign_series."""
+
+    def __init__(self, engine, handle, n_agents):
+        self._eng, self._h, self.n_agents = engine, handle, n_agents
+
+    def next(self) -> AssignResult:
+        return self._eng.assign_series_next([self])[0]
+
+    @staticmethod
+    def next_many(series: Sequence["AssignmentSeries"]) -> List[AssignResult]:
+        """One step of several series of one engine: all children of all pops are solved by ONE launch."""
+        return series[0]._eng.assign_series_next(series) if series else []
+
+    def close(self):
+        if self._h:
+            self._eng._lib.mrp_ll_assign_series_destroy(self._h)
+            self._h = None
 
 
 class LowLevelEngine:
@@ -474,6 +528,81 @@ class LowLevelEngine:
         self._check(self._lib.mrp_ll_heuristic_lookup(self._h, len(ids), ids.ctypes.data_as(I32P), cxy.ctypes.data_as(I32P),
                                                       out.ctypes.data_as(I32P)), "mrp_ll_heuristic_lookup")
         return out[:len(ids)]
+
+    def _marshal_assign(self, problems):
+        """dicts -> mrp_ll_assign_problem[].  Matrix form: cost ([nA][nT]; None or ASSIGN_NO_EDGE = no edge); gather form:
+        heuristic_ids [nT], starts [nA][2], allowed [nA] (optional).  Both: forbidden [nA], mode [nA], min_matching."""
+        n = len(problems)
+        carr = (mrp_ll_assign_problem * max(n, 1))()
+        keep, dims = [], []
+
+        def arr(v, dtype, ptr, shape=-1):
+            a = np.ascontiguousarray(np.asarray(v, dtype=dtype).reshape(shape))
+            if a.size == 0:
+                a = np.zeros(1, dtype=dtype)
+            keep.append(a)
+            return a.ctypes.data_as(ptr)
+
+        for c, p in zip(carr, problems):
+            cost = p.get("cost")
+            if cost is not None:
+                if not isinstance(cost, np.ndarray):
+                    cost = np.array([[ASSIGN_NO_EDGE if v is None else v for v in row] for row in cost], dtype=np.int64)
+                    cost = cost.reshape((int(p["nA"]), int(p["nT"])) if "nA" in p else (len(cost), -1 if len(cost) else 0))
+                if cost.ndim != 2:
+                    raise ValueError("assign: cost must be [n_agents][n_tasks]")
+                c.n_agents, c.n_tasks = (int(p["nA"]), int(p["nT"])) if "nA" in p else cost.shape
+                if cost.size and (cost.min() < -2 ** 31 or cost.max() >= 2 ** 31):
+                    raise ValueError("assign: a cost does not fit 32 bits")
+                c.cost = arr(cost, np.int32, I32P)
+            else:
+                c.n_agents, c.n_tasks = len(p["starts"]), len(p["heuristic_ids"])
+                c.heuristic_ids = arr(p["heuristic_ids"], np.int32, I32P)
+                c.starts_xy = arr(p["starts"], np.int32, I32P)
+                if p.get("allowed") is not None:
+                    c.allowed = arr(p["allowed"], np.uint64, U64P)
+            if p.get("forbidden") is not None:
+                c.forbidden = arr(p["forbidden"], np.uint64, U64P)
+            if p.get("mode") is not None:
+                c.mode = arr(p["mode"], np.int32, I32P)
+            c.min_matching = int(p.get("min_matching") or 0)
+            dims.append(c.n_agents)
+        return carr, keep, dims
+
+    @staticmethod
+    def _assign_results(dims):
+        cres = (mrp_ll_assign_result * max(len(dims), 1))()
+        task_of = [np.full(max(min(d, 4096), 1), -1, dtype=np.int32) for d in dims]
+        for r, t in zip(cres, task_of):
+            r.task_of = t.ctypes.data_as(I32P)
+        return cres, task_of
+
+    @staticmethod
+    def _assign_unpack(cres, task_of, dims):
+        return [AssignResult(r.status, r.matched, r.cost, t[:max(min(d, len(t)), 0)].tolist()) for r, t, d in zip(cres, task_of, dims)]
+
+    def assign_batch(self, problems: Sequence[dict]) -> List[AssignResult]:
+        """mrp_ll_assign_batch: every problem's maximum-cardinality, minimum-cost matching, the whole batch in ONE launch.
+        A rejected problem comes back with status BAD_JOB; the others are unaffected."""
+        carr, keep, dims = self._marshal_assign(problems)
+        cres, task_of = self._assign_results(dims)
+        self._check(self._lib.mrp_ll_assign_batch(self._h, len(problems), carr, cres), "mrp_ll_assign_batch")
+        return self._assign_unpack(cres, task_of, dims)
+
+    def assign_series(self, problems: Sequence[dict]) -> List[AssignmentSeries]:
+        """mrp_ll_assign_series_create: one next-best series per (unconstrained) problem; the optima in ONE launch."""
+        carr, keep, dims = self._marshal_assign(problems)
+        hs = (ctypes.c_void_p * max(len(problems), 1))()
+        self._check(self._lib.mrp_ll_assign_series_create(self._h, len(problems), carr, hs), "mrp_ll_assign_series_create")
+        return [AssignmentSeries(self, hs[k], dims[k]) for k in range(len(problems))]
+
+    def assign_series_next(self, series: Sequence[AssignmentSeries]) -> List[AssignResult]:
+        """mrp_ll_assign_series_next: the next matching of each series; all children of all pops in ONE launch."""
+        dims = [s.n_agents for s in series]
+        hs = (ctypes.c_void_p * max(len(series), 1))(*[s._h for s in series])
+        cres, task_of = self._assign_results(dims)
+        self._check(self._lib.mrp_ll_assign_series_next(self._h, len(series), hs, cres), "mrp_ll_assign_series_next")
+        return self._assign_unpack(cres, task_of, dims)
 
     def sync_maps(self) -> None:
         """mrp_ll_sync_maps: copy what has been uploaded so far to the device now (otherwise done by the next submit)."""
