@@ -183,6 +183,70 @@ int32_t mrp_hl_ct_round_mine(mrp_hl_ct* ct, mrp_ll_ctx* ll, int32_t rank, int32_
                              int32_t cap_rows, int32_t* rows_per_rank);
 int mrp_hl_ct_deliver_rows(mrp_hl_ct* ct, const int32_t* gathered, int32_t world, int32_t rows_stride, int32_t max_states);
 
+/* ---- CBS with task assignment (cbs_ta.hpp:87-214 over the Environment of example/cbs_ta.cpp), batched --------------------
+ * Every instance is a resumable state machine; every ROUND makes three device calls over all instances at once:
+ * mrp_ll_assign_series_next for the instances that need a root (Environment::nextTaskAssignment, cbs_ta.cpp:442-456),
+ * mrp_ll_ta_root_batch for the new roots (cbs_ta.hpp:98-116,142-172), mrp_ll_search_batch for the two child searches of every
+ * popped node with a conflict (cbs_ta.hpp:179-210).  Before the first round: one mrp_ll_compute_heuristics launch for all
+ * goals of all instances and one mrp_ll_assign_series_create (gather form; an agent may take only its own potential goals,
+ * cbs_ta.cpp:272-280).
+ * Tasks are the distinct potential goal cells in order of first appearance in the input (the reference iterates
+ * unordered_sets: its order is unspecified); a potential goal outside the grid can never be assigned and is dropped.
+ * The open list is ordered by cost alone and replays boost's d_ary_heap (hl/exact_heap.hpp).  A popped root with a conflict
+ * first gets its new root — which takes `id`, advanced only when every agent got a path, and is pushed BEFORE the two
+ * children; the expansions of a failed root count.  Conflicts are Environment::getFirstConflict's of cbs_ta.cpp:369-420, which
+ * also looks at the time step at which the longest path ends (mrp_ll_conflict_scan does not: the driver adds that step).
+ * The cost is the reference's; among assignments of equal cost the series' documented order (cost, then creation number)
+ * stands in for Boost's accidental one, so WHICH of several optimal solutions comes back is this project's own choice.
+ * Limits: at most 64 agents and 64 tasks per instance, assignment costs below 2^24 (the assignment calls'); beyond them the
+ * instance ends MRP_HL_LL_ERROR, as it does when a search comes back with a capacity status other than the expansion cap. */
+typedef struct mrp_hl_ta_instance {
+  int32_t dimx, dimy;
+  int32_t n_obstacles;
+  const int32_t* obstacles_xy;  /* [n][2] */
+  int32_t n_agents;
+  const int32_t* starts_xy;     /* [n_agents][2] */
+  const int32_t* goal_first;    /* [n_agents + 1]: agent a's potential goals are goals_xy[goal_first[a] .. goal_first[a + 1]) */
+  const int32_t* goals_xy;      /* [goal_first[n_agents]][2]  (agents[].potentialGoals, cbs_ta.cpp:560-566) */
+} mrp_hl_ta_instance;
+
+typedef struct mrp_hl_ta_options {
+  int32_t max_task_assignments; /* m_maxTaskAssignments: no further assignment is asked for once MORE than this many non-empty */
+                                /* ones have been handed out (the `>` of cbs_ta.cpp:443)                                          */
+  int32_t use_root_kernel;      /* 1: roots through mrp_ll_ta_root_batch; 0: a root is n ordinary jobs inside the round's batch  */
+                                /* and the driver's own scan.  Same results.  0 is the default of a NULL options pointer and of   */
+                                /* the Python and CLI front-ends: measured faster at the reference shape    */
+  int64_t max_hl_expansions;    /* per instance, < 0 unlimited: one more pop ends the instance MRP_HL_CAP                         */
+  int64_t max_ll_expansions;    /* per instance, summed over its searches, < 0 unlimited -> MRP_HL_CAP; every search of a round   */
+                                /* is issued with what was left when the round began, so the counters of a CAPPED instance may    */
+                                /* differ between use_root_kernel 0 and 1                                                        */
+} mrp_hl_ta_options;
+
+typedef struct mrp_hl_ta_solution {
+  int32_t status;               /* MRP_HL_SOLVED | MRP_HL_NO_SOLUTION (empty first assignment, failed first root, open list empty) */
+                                /* | MRP_HL_CAP | MRP_HL_LL_ERROR                                                                */
+  int32_t n_ll_searches;
+  int64_t cost;                 /* statistics.cost (cbs_ta.cpp:582-587) */
+  int64_t makespan;             /* statistics.makespan: the largest path COST */
+  int64_t high_level_expanded;
+  int64_t low_level_expanded;
+  int64_t num_task_assignments; /* statistics.numTaskAssignments */
+  int32_t n_roots;              /* roots pushed to the open list (diagnostic) */
+  int32_t root_conflicts;       /* popped roots that had a conflict (diagnostic) */
+  int32_t* task_xy;             /* caller buffer [n_agents][2] or NULL: the task of every agent of the solution, -1, -1 = none */
+  int32_t* path_len;            /* caller buffer [n_agents] or NULL */
+  int32_t* paths_xyt;           /* caller buffer [n_agents][path_cap][3] or NULL: x, y and the t the reference writes, which is */
+                                /* the path's cost up to that state (cbs_ta.cpp:606-610), not its index                          */
+  int32_t path_cap;
+  int32_t n_root_searches;      /* of n_ll_searches: the searches that planned a root (diagnostic) */
+  uint64_t schedule_digest;     /* as mrp_hl_solution.schedule_digest */
+} mrp_hl_ta_solution;
+
+/* One engine context on `device`, created and destroyed by the call.  stats (may be NULL): wall_seconds, rounds, ll_searches,
+ * ll_expansions, solved, root_solved (instances solved at their first root).  n_instances == 0 succeeds. */
+int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options* opt, int32_t n_instances,
+                              const mrp_hl_ta_instance* instances, mrp_hl_ta_solution* solutions, mrp_hl_batch_stats* stats);
+
 /* BASELINE.json configs[0] — `./a_star` on a text map (example/a_star.cpp:72-125,190-191) — is host plumbing: a single
  * 2-D A* (AStar::search a_star.hpp:63-161, neighbours Up, Down, Left, Right, unit costs, Manhattan heuristic), run on
  * the CPU with the reference's heap tie-breaks.  obstacle_mask[y * dimx + x] != 0 = '#'.  Returns the number of states

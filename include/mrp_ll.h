@@ -629,6 +629,55 @@ int mrp_ll_submit_node(mrp_ll_ctx* ctx, int32_t tag, int32_t n_jobs, const mrp_l
                        mrp_ll_conflict* conflicts, const mrp_ll_constraint_ref* sets, const mrp_ll_scan_base* bases /* [n_jobs] */,
                        int32_t* ticket);
 
+/* ---- the root node of a CBS-TA conflict tree -------------------------------------------------------------------
+ * CBS with task assignment plans a whole new root for every popped root that still has a conflict (cbs_ta.hpp:142-172): n
+ * unconstrained low-level searches under the next-best assignment, then Environment::getFirstConflict over their paths.
+ * Here ONE workgroup does that for one root and a batch of roots is ONE kernel launch that ends (workgroup b takes roots
+ * b, b + grid, ...; grid = min(n_roots, mrp_ll_options.slots)): no job descriptor and no result round trip per agent, no
+ * scan on the host.
+ * Agents are planned in index order, each with no constraints; agent a's search is exactly the one the ordinary
+ * MRP_LL_ASTAR_TA job {map_id, start = starts_xy[a], goal = goals_xy[a], heuristic_id = heuristic_ids[a], or
+ * MRP_LL_JOB_NO_GOAL where heuristic_ids[a] < 0} runs — the LDS tier where it fits, the arena tier otherwise — and
+ * results[a] is field for field what that job returns: status, cost, fmin, n_states, expanded, tier, states, actions,
+ * action costs (MRP_LL_PATH_TRUNCATED included; the root still counts such an agent as planned).
+ * The root ends BEHIND the first agent whose search does not end MRP_LL_OK (the break at cbs_ta.hpp:159-162): later agents
+ * come back MRP_LL_NOT_RUN with cost, fmin, n_states, expanded and tier 0; planned[r] = results filled in.
+ * max_expansions is the budget of the whole root, shared as a root chain's (MRP_LL_JOB_ROOT_CHAIN): each search gets what
+ * the ones before it left; an empty budget starts the next search with 0, which comes back MRP_LL_CAP_EXPANSIONS with
+ * expanded = 1.
+ * conflicts[r]: when every agent got a path, exactly what mrp_ll_conflict_scan returns for those n_agents paths; otherwise
+ * found = -1 and the other nine fields 0.  The workgroup keeps the paths as a time-major table of  longest path x (n_agents
+ * rounded up to 16) x 2  bytes in its arena slot's path area (128 KiB by default: room for 64 agents and 1024 time steps)
+ * and scans it there; a table beyond that area is not built, and the call completes conflicts[r] with the batch scan
+ * of mrp_ll_conflict_scan on the paths it holds before it returns — the caller always receives the answer.
+ * A root is refused on the host, with nothing run for it and the other roots unaffected — planned[r] = 0, every result
+ * MRP_LL_BAD_JOB, found = -1 — when: map_id is unknown; a start lies outside the grid; a heuristic id is unknown or belongs
+ * to another map, or its goal lies outside the grid (what makes the ordinary job MRP_LL_BAD_JOB); n_agents is outside
+ * 1 .. 64; starts_xy, goals_xy, heuristic_ids or results is NULL.
+ * The refusal is written to results[0 .. n_agents - 1] as the caller counted them, also for a count above 64: `results`
+ * must hold n_agents entries whenever it is not NULL and n_agents is positive.
+ * MRP_LL_E_INVALID: a NULL argument, n_roots < 0.  MRP_LL_E_BUSY while a session is active or a batch is in flight, like
+ * the assignment calls.  n_roots == 0 succeeds without a launch.
+ * On MRP_LL_E_DEVICE / MRP_LL_E_NOMEM (a launch, an allocation or the completing scan failed) the outputs say that nothing
+ * ran, never half of it: planned[r] = 0 and found = -1 for every root, every result of a root that would have been refused
+ * MRP_LL_BAD_JOB and of every other root MRP_LL_NOT_RUN, their other fields 0.
+ * Tuning knob: the environment variable MRP_LL_ARENA_PATHS_BYTES, read by mrp_ll_create, sets the path area of every arena
+ * slot of the contexts created under it (4096 .. 131072 bytes, rounded down to a multiple of 256; unset: 131072).  The area
+ * is shared: it also holds the focal table of an A*-epsilon job that does not fit LDS, a root chain's table in a
+ * mrp_ll_session_front_tables session and the travelling safe-interval table of a SIPP job, so under a smaller value jobs
+ * with larger tables come back MRP_LL_BAD_JOB (path_ids tables, root chains) or are read from host memory (shipped tables)
+ * that a default context serves from the slot.  Results never depend on it; it exists for tests and measurements. */
+typedef struct mrp_ll_ta_root {
+  int32_t map_id, n_agents;        /* 1 .. 64 (the assignment's limit) */
+  const int32_t* starts_xy;        /* [n_agents][2] */
+  const int32_t* goals_xy;         /* [n_agents][2]; ignored where heuristic_ids[a] < 0 */
+  const int32_t* heuristic_ids;    /* [n_agents]; < 0: the agent has no task (MRP_LL_JOB_NO_GOAL) */
+  int64_t max_expansions;          /* budget of the whole root, < 0 unlimited */
+  mrp_ll_result* results;          /* [n_agents], each with its own caller buffers */
+} mrp_ll_ta_root;
+int mrp_ll_ta_root_batch(mrp_ll_ctx* ctx, int32_t n_roots, const mrp_ll_ta_root* roots, int32_t* planned /* [n_roots] */,
+                         mrp_ll_conflict* conflicts /* [n_roots] */);
+
 int mrp_ll_get_stats(const mrp_ll_ctx* ctx, mrp_ll_stats* out);
 int mrp_ll_reset_stats(mrp_ll_ctx* ctx);
 

@@ -2,6 +2,8 @@
 
     python -m libmultirobotplanning_amd.cli ecbs -i in.yaml -o out.yaml -w 1.3     (example/ecbs.cpp:524-623)
     python -m libmultirobotplanning_amd.cli cbs  -i in.yaml -o out.yaml            (example/cbs.cpp:571-667)
+    python -m libmultirobotplanning_amd.cli cbs_ta -i in.yaml -o out.yaml [--maxTaskAssignments N]   (example/cbs_ta.cpp:523-617:
+        agents[].{name,start,potentialGoals}; statistics also has numTaskAssignments, and a state's t is its cost so far)
     python -m libmultirobotplanning_amd.cli sipp -i in.yaml -o out.yaml            (example/sipp.cpp:149-236)
     python -m libmultirobotplanning_amd.cli mapf_prioritized_sipp -i in.yaml -o out.yaml
                                                                                    (example/mapf_prioritized_sipp.cpp:157-295)
@@ -92,6 +94,46 @@ def write_schedule(path: str, res: Dict, runtime: float) -> None:
             out.write("  agent%d:\n" % a)
             for t, (x, y) in enumerate(p):
                 out.write("    - x: %d\n      y: %d\n      t: %d\n" % (x, y, t))
+
+
+def read_ta_instance(path: str) -> Dict:
+    """example/cbs_ta.cpp:543-566: map, agents[].start, agents[].potentialGoals."""
+    cfg = yaml_subset.load(path)
+    dim = cfg["map"]["dimensions"]
+    return dict(dimx=int(dim[0]), dimy=int(dim[1]),
+                obstacles=[[int(o[0]), int(o[1])] for o in (cfg["map"].get("obstacles") or [])],
+                starts=[[int(a["start"][0]), int(a["start"][1])] for a in cfg["agents"]],
+                potential_goals=[[[int(g[0]), int(g[1])] for g in (a.get("potentialGoals") or [])] for a in cfg["agents"]])
+
+
+def main_cbs_ta(args, ap) -> int:
+    """cbs_ta -i in.yaml -o out.yaml [--maxTaskAssignments N]: the output of example/cbs_ta.cpp:589-614."""
+    from . import hl
+    if len(args.input) != len(args.output):
+        ap.error("give one -o per -i")
+    insts = [read_ta_instance(p) for p in args.input]
+    res, st = hl.solve_cbs_ta_batch(insts, max_task_assignments=args.maxTaskAssignments, device=args.device,
+                                    max_ll_expansions=args.max_ll_expansions, path_cap=1024)
+    rc = 0
+    for r, path in zip(res, args.output):
+        if r["status"] != hl.SOLVED:
+            print("Planning NOT successful!" + (" (harness cap)" if r["status"] == hl.CAP else ""))
+            rc = 1 if r["status"] != hl.NO_SOLUTION else rc
+            continue
+        print("Planning successful! ")
+        with open(path, "w") as out:
+            out.write("statistics:\n")
+            out.write("  cost: %d\n" % r["cost"])
+            out.write("  makespan: %d\n" % r["makespan"])
+            out.write("  runtime: %g\n" % st["wall_seconds"])
+            out.write("  highLevelExpanded: %d\n" % r["hl_expanded"])
+            out.write("  lowLevelExpanded: %d\n" % r["ll_expanded"])
+            out.write("  numTaskAssignments: %d\n" % r["num_task_assignments"])
+            out.write("schedule:\n")
+            for a, p in enumerate(r["paths"]):
+                out.write("  agent%d:\n" % a)
+                _write_states(out, p)  # t: the state's cost so far, as the reference writes it (:606-610)
+    return rc
 
 
 def _write_states(out, states_xyt) -> None:
@@ -293,13 +335,14 @@ def main_assignment(args, ap) -> int:
 def main(argv: List[str] = None) -> int:
     ap = argparse.ArgumentParser(prog="libmultirobotplanning_amd.cli")
     ap.add_argument("algo", choices=["ecbs", "cbs", "sipp", "mapf_prioritized_sipp", "a_star", "shortest_path_heuristic",
-                                     "assignment", "next_best_assignment"])
+                                     "assignment", "next_best_assignment", "cbs_ta"])
     ap.add_argument("-i", "--input", action="append", default=[], help="input file (YAML)")
     ap.add_argument("-o", "--output", action="append", default=[], help="output file (YAML)")
     ap.add_argument("-w", "--suboptimality", type=float, default=1.0, help="suboptimality bound (ecbs)")
     ap.add_argument("-m", "--map", help="input map (txt) (a_star)")
     for k in ("startX", "startY", "goalX", "goalY"):
         ap.add_argument("--" + k, type=int, help="a_star: %s" % k)
+    ap.add_argument("--maxTaskAssignments", type=int, default=10 ** 9, help="cbs_ta: maximum number of task assignments to try")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--max-ll-expansions", type=int, default=-1, help="harness cap per instance (reference: none)")
     args = ap.parse_args(argv)
@@ -311,6 +354,8 @@ def main(argv: List[str] = None) -> int:
         ap.error("the following arguments are required: -o/--output")
     if args.algo in ("assignment", "next_best_assignment"):
         return main_assignment(args, ap)
+    if args.algo == "cbs_ta":
+        return main_cbs_ta(args, ap)
     if args.algo in ("ecbs", "cbs"):
         return main_mapf(args, ap)
     if args.algo == "mapf_prioritized_sipp":

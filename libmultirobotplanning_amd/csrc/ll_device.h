@@ -108,6 +108,34 @@ constexpr uint32_t kTaNoGoal = 16u;                                // MRP_LL_AST
                                                                    // MRP_LL_ASTAR_TA: path_off = word offset of the goal's heuristic
                                                                    // table in the maps buffer (MRP_LL_ASTAR_EPS_TA: heur_off)
 constexpr uint32_t kHeurWords = 512;                               // a heuristic table: [32][32] halfwords (0xFFFF: unreachable)
+// The root node of a CBS-TA conflict tree (mrp_ll_ta_root_batch; ll_ta_root.h): the root's record is a DevJob — map fields,
+// algo MRP_LL_ASTAR_TA, max_expansions = the budget of the whole root, n_ctx = its agents (1 .. kTaRootMaxAgents), reserved =
+// the index of its first result, everything else as packJob leaves it for an unconstrained MRP_LL_ASTAR_TA job — and
+// cons[vc_off + kTaRootAgentWords * a ..] = {sx | sy << 8 | gx << 16 | gy << 24, word offset of the goal's table in the maps
+// buffer, kTaNoGoal or 0} of agent a (an agent without a task: goal 0, 0 and offset 0, as packJob).  Agent a's DevResult
+// and path go to results / out_paths [reserved + a]; the last kScanOutHalfs halfwords of out_paths[reserved] receive the
+// root's answer: the ten words of an mrp_ll_conflict (found = -1, the rest 0: not every agent got a path; found =
+// kTaRootScanSkipped: all did, and the table did not fit the slot's path area) and, in word kTaRootPlannedWord, the number
+// of results filled in.
+constexpr uint32_t kTaRootAgentWords = 3;
+constexpr uint32_t kTaRootMaxAgents = 64;                          // (the assignment's limit)
+constexpr uint32_t kTaRootPlannedWord = 10;
+constexpr uint32_t kTaRootScanSkipped = 0xFFFFFFFEu;
+#ifdef __HIP__  // (the language mode of hipcc: a .hip source, device and host pass)
+#define MRP_DEV_FN __host__ __device__ inline
+#else
+#define MRP_DEV_FN inline
+#endif
+// Agent a's descriptor out of the root's record `d` (in place) and the agent's three words: word for word what packJob makes
+// for the ordinary unconstrained MRP_LL_ASTAR_TA job with `budget` as its max_expansions.  ONE definition for the workgroup
+// (ll_ta_root.h runTaRoot) and for the check that compares it with packJob's (tests/support/ta_root_pack_check.cpp).
+MRP_DEV_FN void taRootAgentJob(DevJob& d, uint32_t startGoal, uint32_t heurOff, uint32_t flags, int64_t budget) {
+  d.sx = startGoal & 0xFFu; d.sy = (startGoal >> 8) & 0xFFu; d.gx = (startGoal >> 16) & 0xFFu; d.gy = startGoal >> 24;
+  d.path_off = heurOff;
+  d.ctx_flags = flags & kTaNoGoal;
+  d.max_expansions = budget;
+  d.n_ctx = 0; d.reserved = 0;
+}
 constexpr uint32_t kSippResident = 2u;
 constexpr uint32_t kSippCommit = 8u;                               // ctx_flags bit 3: on success the workgroup adds the path's stays to the table
 constexpr uint32_t kSippTierCommitFailed = 0x100u;                 // DevResult.tier flag: a stay did not fit (more than kSippCap intervals,

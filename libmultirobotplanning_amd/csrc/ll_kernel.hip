@@ -19,10 +19,11 @@
 //   ll_jobs.h          job staging and bracket, the arena slot's cut, baseCJob, runJob (stageFocalTable, compactAttempt,
 //                      arenaAttempt), publishPath and runChain (ECBS root chains)
 //   ll_ta.h            TaEnv, runTaArena / runJobTA, runJobTaEps: the task-assignment low levels
+//   ll_ta_root.h       runTaRoot, taRootLoop: the root node of a CBS-TA conflict tree, searches and scan, by one workgroup
 //   ll_sipp.h          SIPP: its tiers, sippLoop, runSipp, processSippJob
 //   ll_node_scan.h     nodeScan, nodeScanFromParent: the conflicts of the conflict-tree node a search has completed (also
 //                      compiled for the CPU)
-//   here               scanNode, processJob, batchLoop, publishDone, residentLoop, the eleven kernels, the launchers
+//   here               scanNode, processJob, batchLoop, publishDone, residentLoop, the twelve kernels, the launchers
 //
 // Reference semantics implemented (file:line in the reference project, libMultiRobotPlanning):
 //   AStarEpsilon::search   include/libMultiRobotPlanning/a_star_epsilon.hpp:86-285
@@ -45,6 +46,7 @@
 #include "ll_arena_search.h"
 #include "ll_jobs.h"
 #include "ll_ta.h"
+#include "ll_ta_root.h"
 #include "ll_sipp.h"
 #include "ll_node_scan.h"
 
@@ -241,6 +243,7 @@ DEVI void batchLoop(const LaunchParams& P, uint8_t* smem, DevJob& jobS, DevResul
 MRP_LL_WINDOW_KERNEL(mrp_ll_search_kernel, batchLoop<0>)  // mixed batches
 MRP_LL_WINDOW_KERNEL(mrp_ll_ecbs_search_kernel, batchLoop<1>)  // A*-epsilon jobs only
 MRP_LL_WINDOW_KERNEL(mrp_ll_cbs_search_kernel, batchLoop<2>)  // A* jobs only
+MRP_LL_WINDOW_KERNEL(mrp_ll_ta_root_kernel, taRootLoop)  // roots of CBS-TA conflict trees (ll_ta_root.h), the A* kernels' window
 
 // SIPP batches (MRP_LL_SIPP jobs only) run in their own kernels so that the CBS/ECBS kernels' register allocation is
 // not widened by a path they never take.  Same queue discipline as mrp_ll_search_kernel.
@@ -527,16 +530,18 @@ extern "C" __global__ void __launch_bounds__(64) mrp_ll_sipp_persistent_kernel(L
 // The CBS / ECBS kernels by role and kind (0 = mixed, 1 = A*-epsilon jobs only, 2 = A* jobs only, see processJob; the front /
 // heavy pair exists for kind 1 alone).  `slot` numbers the kernel for allowFullLds.
 typedef void (*Kern)(LaunchParams);
-enum Role : int { kBatch = 0, kResident = 1, kFront = 2, kHeavy = 3, kFront4 = 4 };
+enum Role : int { kBatch = 0, kResident = 1, kFront = 2, kHeavy = 3, kFront4 = 4, kTaRoot = 5 };
 struct KernelRef {
   Kern fn;
   int slot;
 };
 static KernelRef kernelFor(Role role, int kind) {
-  static const Kern table[9] = {mrp_ll_search_kernel,     mrp_ll_ecbs_search_kernel,     mrp_ll_cbs_search_kernel,
-                                mrp_ll_persistent_kernel, mrp_ll_ecbs_persistent_kernel, mrp_ll_cbs_persistent_kernel,
-                                mrp_ll_ecbs_front_kernel, mrp_ll_ecbs_heavy_kernel,      mrp_ll_ecbs_front4_kernel};
-  const int slot = role == kFront ? 6 : role == kHeavy ? 7 : role == kFront4 ? 8 : 3 * role + (kind == 1 || kind == 2 ? kind : 0);
+  static const Kern table[10] = {mrp_ll_search_kernel,     mrp_ll_ecbs_search_kernel,     mrp_ll_cbs_search_kernel,
+                                 mrp_ll_persistent_kernel, mrp_ll_ecbs_persistent_kernel, mrp_ll_cbs_persistent_kernel,
+                                 mrp_ll_ecbs_front_kernel, mrp_ll_ecbs_heavy_kernel,      mrp_ll_ecbs_front4_kernel,
+                                 mrp_ll_ta_root_kernel};
+  const int slot = role == kFront ? 6 : role == kHeavy ? 7 : role == kFront4 ? 8 : role == kTaRoot ? 9
+                   : 3 * role + (kind == 1 || kind == 2 ? kind : 0);
   return KernelRef{table[slot], slot};
 }
 
@@ -545,7 +550,7 @@ static KernelRef kernelFor(Role role, int kind) {
 // launches through here, and the attribute is per device.
 static hipError_t allowFullLds(const KernelRef& k) {
   static std::mutex mu;
-  static bool done[9][64] = {};
+  static bool done[10][64] = {};
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
@@ -607,6 +612,12 @@ extern "C" hipError_t mrp_ll_launch_front_heavy(const mrp::LaunchParams* P, uint
 // Resident workgroups per CU of that kernel alone (0 on error).
 extern "C" int mrp_ll_front_heavy_occupancy(int heavy, uint32_t ldsBytes) {
   return mrp::occupancyOf(frontHeavyKernel(heavy), heavy == 1 ? mrp_ll_heavy_lds_bytes() : ldsBytes);
+}
+
+// The roots of CBS-TA conflict trees (ll_ta_root.h): `grid` workgroups share P->n_jobs roots; the window of the A* kernels
+// (mrp_ll_lds_bytes(kind = 2)), so that every search meets the tiers an ordinary MRP_LL_ASTAR_TA batch gives it.
+extern "C" hipError_t mrp_ll_launch_ta_root(const mrp::LaunchParams* P, uint32_t grid, uint32_t ldsBytes, hipStream_t stream) {
+  return mrp::launchWithLds(mrp::kernelFor(mrp::kTaRoot, 0), P, grid, ldsBytes, stream);
 }
 
 // The SIPP kernels' LDS is static: no attribute to set.

@@ -9,6 +9,8 @@
 //                           -> device words and back) and host/assign_series.h (HIP-free: open list and partition)
 //   host/ll_stores.h        path store, constraint store, SIPP tables
 //   host/ll_batch.h         batch mode: launch parameters, submit, wait
+//   host/ll_ta_root_host.h  the roots of CBS-TA conflict trees in one launch, with host/ta_root_pack.h (HIP-free: roots ->
+//                           device words and back)
 //   host/ll_session.h       session mode: begin (allocation, reset, launch), end, heartbeat
 //   host/ll_session_jobs.h  session mode: submit, poll, completion queue
 //   host/ll_submit.h        the submit / poll / wait entry points
@@ -20,6 +22,7 @@
 #include "host/ll_assign_host.h"
 #include "host/ll_stores.h"
 #include "host/ll_batch.h"
+#include "host/ll_ta_root_host.h"
 #include "host/ll_session.h"
 #include "host/ll_session_jobs.h"
 #include "host/ll_submit.h"
@@ -74,6 +77,8 @@ int mrp_ll_create(const mrp_ll_options* optIn, mrp_ll_ctx** out) {
   }
   ctx->arenaRowWords = (static_cast<uint32_t>(o.max_cells) + 31u) / 32u;
   ctx->env.arenaPathsBytes = 128 * 1024;
+  if (const char* e = std::getenv("MRP_LL_ARENA_PATHS_BYTES"))  // tuning knob (tests: a path area too small for a root's table)
+    ctx->env.arenaPathsBytes = static_cast<uint32_t>(std::min(std::max(std::atoi(e), 4096), 128 * 1024)) & ~255u;
   ctx->arenaScratchOff = static_cast<uint32_t>(mrp::slot::scratchOff(o.arena_nodes, o.max_horizon, ctx->arenaRowWords));
   const uint64_t stride = mrp::slot::stride(o.arena_nodes, o.max_horizon, ctx->arenaRowWords, ctx->env.arenaPathsBytes);
   ctx->arenaStride = stride;

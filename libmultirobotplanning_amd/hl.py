@@ -63,9 +63,29 @@ EXPORTS = ["mrp_hl_solver_prioritized_sipp", "mrp_hl_solver_preload", "mrp_hl_so
            "mrp_hl_preloaded_free", "mrp_hl_solve_batch", "mrp_hl_solver_create", "mrp_hl_solver_destroy", "mrp_hl_solver_solve",
            "mrp_hl_solver_ll_stats", "mrp_hl_solver_last_error", "mrp_hl_generate_instance", "mrp_hl_generate_instances", "mrp_hl_astar_grid2d",
            "mrp_hl_ct_create", "mrp_hl_ct_destroy", "mrp_hl_ct_n_requests", "mrp_hl_ct_request", "mrp_hl_ct_deliver",
-           "mrp_hl_ct_done", "mrp_hl_ct_solution"]
+           "mrp_hl_ct_done", "mrp_hl_ct_solution", "mrp_hl_solve_cbs_ta_batch"]
 
 _lib = None
+
+
+class mrp_hl_ta_instance(ctypes.Structure):
+    _fields_ = [("dimx", ctypes.c_int32), ("dimy", ctypes.c_int32), ("n_obstacles", ctypes.c_int32),
+                ("obstacles_xy", I32P), ("n_agents", ctypes.c_int32), ("starts_xy", I32P), ("goal_first", I32P),
+                ("goals_xy", I32P)]
+
+
+class mrp_hl_ta_options(ctypes.Structure):
+    _fields_ = [("max_task_assignments", ctypes.c_int32), ("use_root_kernel", ctypes.c_int32),
+                ("max_hl_expansions", ctypes.c_int64), ("max_ll_expansions", ctypes.c_int64)]
+
+
+class mrp_hl_ta_solution(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_int32), ("n_ll_searches", ctypes.c_int32), ("cost", ctypes.c_int64),
+                ("makespan", ctypes.c_int64), ("high_level_expanded", ctypes.c_int64),
+                ("low_level_expanded", ctypes.c_int64), ("num_task_assignments", ctypes.c_int64),
+                ("n_roots", ctypes.c_int32), ("root_conflicts", ctypes.c_int32), ("task_xy", I32P), ("path_len", I32P),
+                ("paths_xyt", I32P), ("path_cap", ctypes.c_int32), ("n_root_searches", ctypes.c_int32),
+                ("schedule_digest", ctypes.c_uint64)]
 
 
 def load_library(path: Optional[str] = None):
@@ -136,6 +156,11 @@ def load_library(path: Optional[str] = None):
         lib.mrp_hl_generate_instances.restype = ctypes.c_int
         lib.mrp_hl_generate_instances.argtypes = [ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                   ctypes.c_int32, ctypes.c_int32, I32P, I32P, I32P]
+        if hasattr(lib, "mrp_hl_solve_cbs_ta_batch"):  # (a test build of mrp_hl.cpp alone has no task-assignment driver)
+            lib.mrp_hl_solve_cbs_ta_batch.restype = ctypes.c_int
+            lib.mrp_hl_solve_cbs_ta_batch.argtypes = [ctypes.c_int32, ctypes.POINTER(mrp_hl_ta_options), ctypes.c_int32,
+                                                      ctypes.POINTER(mrp_hl_ta_instance), ctypes.POINTER(mrp_hl_ta_solution),
+                                                      ctypes.POINTER(mrp_hl_batch_stats)]
         if path is not None:
             return lib
         _lib = lib
@@ -539,3 +564,51 @@ class ConflictTree:
         if sol.status == SOLVED:
             rec["paths"] = [pxy[a, :plen[a]].tolist() for a in range(self.n_agents)]
         return rec
+
+
+def solve_cbs_ta_batch(instances: Sequence[Dict], max_task_assignments: int = 2 ** 30, use_root_kernel: bool = False,
+                       max_hl_expansions: int = -1, max_ll_expansions: int = -1, device: int = 0, path_cap: int = 256,
+                       _lib_path: Optional[str] = None):
+    """mrp_hl_solve_cbs_ta_batch: CBS with task assignment (cbs_ta.hpp:87-214) for a batch of instances, each a dict with
+    dimx, dimy, obstacles [[x, y]], starts [[x, y]] and potential_goals (per agent a list of [x, y]).  Returns (results,
+    stats): per instance status, cost, makespan, hl_expanded, ll_expanded, num_task_assignments, n_roots, root_conflicts,
+    n_ll_searches, n_root_searches, digest, tasks (per agent [x, y] or None) and paths (per agent [[x, y, t]], t = the path's cost up to that
+    state, as the reference writes it)."""
+    lib = load_library(_lib_path)
+    n = len(instances)
+    cinst = (mrp_hl_ta_instance * max(n, 1))()
+    csol = (mrp_hl_ta_solution * max(n, 1))()
+    keep = []
+    for k, inst in enumerate(instances):
+        na = len(inst["starts"])
+        ob = np.ascontiguousarray(np.asarray(inst["obstacles"], dtype=np.int32).reshape(-1, 2))
+        st = np.ascontiguousarray(np.asarray(inst["starts"], dtype=np.int32).reshape(-1, 2))
+        first = np.zeros(na + 1, dtype=np.int32)
+        np.cumsum([len(g) for g in inst["potential_goals"]], out=first[1:])
+        gl = np.ascontiguousarray(np.asarray([c for g in inst["potential_goals"] for c in g], dtype=np.int32).reshape(-1, 2))
+        tasks = np.full((max(na, 1), 2), -7, dtype=np.int32)
+        plen = np.zeros(max(na, 1), dtype=np.int32)
+        paths = np.zeros((max(na, 1), path_cap, 3), dtype=np.int32)
+        c = cinst[k]
+        c.dimx, c.dimy, c.n_obstacles, c.n_agents = inst["dimx"], inst["dimy"], len(ob), na
+        c.obstacles_xy, c.starts_xy = ob.ctypes.data_as(I32P), st.ctypes.data_as(I32P)
+        c.goal_first, c.goals_xy = first.ctypes.data_as(I32P), gl.ctypes.data_as(I32P)
+        csol[k].task_xy, csol[k].path_len = tasks.ctypes.data_as(I32P), plen.ctypes.data_as(I32P)
+        csol[k].paths_xyt, csol[k].path_cap = paths.ctypes.data_as(I32P), path_cap
+        keep.append((ob, st, first, gl, tasks, plen, paths))
+    opt = mrp_hl_ta_options(max_task_assignments, 1 if use_root_kernel else 0, max_hl_expansions, max_ll_expansions)
+    stats = mrp_hl_batch_stats()
+    rc = lib.mrp_hl_solve_cbs_ta_batch(device, ctypes.byref(opt), n, cinst, csol, ctypes.byref(stats))
+    if rc != 0:
+        raise RuntimeError(f"mrp_hl_solve_cbs_ta_batch failed rc={rc}")
+    out = []
+    for k in range(n):
+        s, (_, st, _, _, tasks, plen, paths) = csol[k], keep[k]
+        na = len(st)
+        solved = s.status == SOLVED
+        out.append(dict(status=s.status, cost=s.cost, makespan=s.makespan, hl_expanded=s.high_level_expanded,
+                        ll_expanded=s.low_level_expanded, num_task_assignments=s.num_task_assignments, n_roots=s.n_roots,
+                        root_conflicts=s.root_conflicts, n_ll_searches=s.n_ll_searches, n_root_searches=s.n_root_searches, digest=s.schedule_digest,
+                        tasks=[None if tasks[a][0] < 0 else tasks[a].tolist() for a in range(na)] if solved else None,
+                        paths=[paths[a, :min(int(plen[a]), path_cap)].tolist() for a in range(na)] if solved else None))
+    return out, {f: getattr(stats, f) for f, _ in mrp_hl_batch_stats._fields_}

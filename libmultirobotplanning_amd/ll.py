@@ -22,6 +22,8 @@ JOB_CONSTRAINT_SET = 32  # mrp_ll_job.flags: mrp_ll_submit_sets' sets[i] names t
 JOB_SCAN_FROM_PARENT = 64  # mrp_ll_job.flags: mrp_ll_submit_node's bases[i] holds what the parent node's scan established
 SCAN_UNTOUCHED = -2      # search_batch_scan: what every field of an entry the engine did not write still holds
 OK, NO_SOLUTION, CAP_EXPANSIONS, CAP_NODES, CAP_HORIZON, BAD_JOB, PATH_TRUNCATED, CAP_FOCAL = range(8)
+NOT_RUN = 8              # a root ended before this agent's search (mrp_ll_ta_root_batch, root chains)
+E_INVALID, E_DEVICE, E_NOMEM, E_BUSY = -1, -2, -3, -4  # return codes of the API calls
 ACTION_NAMES = ["Up", "Down", "Left", "Right", "Wait"]  # example/ecbs.cpp:49-55
 
 ASSIGN_NO_EDGE = 2 ** 31 - 1  # MRP_LL_ASSIGN_NO_EDGE
@@ -80,6 +82,11 @@ class mrp_ll_assign_result(ctypes.Structure):
     _fields_ = [("status", ctypes.c_int32), ("matched", ctypes.c_int32), ("cost", ctypes.c_int64), ("task_of", I32P)]
 
 
+class mrp_ll_ta_root(ctypes.Structure):
+    _fields_ = [("map_id", ctypes.c_int32), ("n_agents", ctypes.c_int32), ("starts_xy", I32P), ("goals_xy", I32P),
+                ("heuristic_ids", I32P), ("max_expansions", ctypes.c_int64), ("results", ctypes.POINTER(mrp_ll_result))]
+
+
 class mrp_ll_stats(ctypes.Structure):
     _fields_ = [("launches", ctypes.c_int64), ("jobs", ctypes.c_int64), ("expansions", ctypes.c_int64),
                 ("nodes_created", ctypes.c_int64), ("migrated", ctypes.c_int64), ("kernel_ms", ctypes.c_double),
@@ -100,7 +107,7 @@ EXPORTS = ["mrp_ll_create", "mrp_ll_destroy", "mrp_ll_last_error", "mrp_ll_uploa
            "mrp_ll_compute_heuristics", "mrp_ll_read_heuristic", "mrp_ll_heuristic_lookup", "mrp_ll_submit_scan",
            "mrp_ll_constraint_store_reserve", "mrp_ll_submit_sets", "mrp_ll_session_front_tables",
            "mrp_ll_submit_node", "mrp_ll_assign_batch", "mrp_ll_assign_series_create", "mrp_ll_assign_series_next",
-           "mrp_ll_assign_series_destroy"]
+           "mrp_ll_assign_series_destroy", "mrp_ll_ta_root_batch"]
 
 _lib = None
 
@@ -200,6 +207,9 @@ def load_library(path: Optional[str] = None):
     lib.mrp_ll_assign_series_next.restype = ctypes.c_int
     lib.mrp_ll_assign_series_next.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p),
                                               ctypes.POINTER(mrp_ll_assign_result)]
+    lib.mrp_ll_ta_root_batch.restype = ctypes.c_int
+    lib.mrp_ll_ta_root_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(mrp_ll_ta_root), I32P,
+                                         ctypes.POINTER(mrp_ll_conflict)]
     lib.mrp_ll_assign_series_destroy.restype = None
     lib.mrp_ll_assign_series_destroy.argtypes = [ctypes.c_void_p]
     if path is None:
@@ -251,6 +261,24 @@ class LLResult:
     tier: int = 0
     action_costs: List[int] = field(default_factory=list)
     n_states: int = 0  # mrp_ll_result.n_states as the library left it (0 unless a path came back)
+
+
+@dataclass
+class TaRoot:
+    """One root node of a CBS-TA conflict tree (mrp_ll_ta_root): the agents' starts, and per agent its task — goal cell and
+    the heuristic id of that cell's table — or None / a negative id for an agent without a task."""
+    map_id: int
+    starts: Sequence[Sequence[int]]
+    goals: Sequence[Optional[Sequence[int]]]
+    heuristic_ids: Sequence[int]
+    max_expansions: int = -1
+
+
+@dataclass
+class TaRootResult:
+    planned: int               # results filled in
+    results: List[LLResult]    # per agent; NOT_RUN behind the agent the root ended at, BAD_JOB for a refused root
+    conflict: dict             # as conflict_scan returns it; found = -1, the rest 0, when not every agent got a path
 
 
 @dataclass
@@ -481,6 +509,50 @@ class LowLevelEngine:
                                                    path_first.ctypes.data_as(I32P), xy.ctypes.data_as(I32P), out),
                     "mrp_ll_conflict_scan")
         return [{k: getattr(out[i], k) for k, _ in mrp_ll_conflict._fields_} for i in range(n)]
+
+    def _marshal_ta_roots(self, roots: Sequence[TaRoot], cap: int):
+        """The ctypes arrays of mrp_ll_ta_root_batch for `roots`: (croots, planned, conflicts, per-root result buffers, keepalive)."""
+        n = len(roots)
+        croots = (mrp_ll_ta_root * max(n, 1))()
+        planned = np.full(max(n, 1), -7, dtype=np.int32)
+        conf = (mrp_ll_conflict * max(n, 1))()
+        keep, per_root = [], []
+        for i, r in enumerate(roots):
+            na = len(r.starts)
+            st = np.ascontiguousarray(np.asarray(r.starts, dtype=np.int32).reshape(-1, 2))
+            hid = np.ascontiguousarray(np.asarray(r.heuristic_ids, dtype=np.int32).reshape(-1))
+            gl = np.ascontiguousarray(np.asarray([g if g is not None else (0, 0) for g in r.goals], dtype=np.int32).reshape(-1, 2))
+            cres = (mrp_ll_result * max(na, 1))()
+            states = np.zeros((max(na, 1), cap, 3), dtype=np.int32)
+            actions = np.zeros((max(na, 1), cap), dtype=np.int32)
+            costs = np.zeros((max(na, 1), cap), dtype=np.int32)
+            for a in range(na):
+                cres[a].states_txy = states[a].ctypes.data_as(I32P)
+                cres[a].actions = actions[a].ctypes.data_as(I32P)
+                cres[a].states_cap = cap
+                cres[a].action_costs = costs[a].ctypes.data_as(I32P)
+            c = croots[i]
+            c.map_id, c.n_agents, c.max_expansions = r.map_id, na, r.max_expansions
+            c.starts_xy, c.goals_xy, c.heuristic_ids = st.ctypes.data_as(I32P), gl.ctypes.data_as(I32P), hid.ctypes.data_as(I32P)
+            c.results = ctypes.cast(cres, ctypes.POINTER(mrp_ll_result))
+            keep.append((st, hid, gl))
+            per_root.append((na, cres, states, actions, costs))
+        return croots, planned, conf, per_root, keep
+
+    def ta_root_batch(self, roots: Sequence[TaRoot], states_cap: Optional[int] = None, raw_rc: bool = False):
+        """mrp_ll_ta_root_batch: the roots of CBS-TA conflict trees, one workgroup each, in one launch.  Returns one
+        TaRootResult per root; with raw_rc the call's return code instead of raising (E_BUSY inside a session)."""
+        n = len(roots)
+        cap = states_cap or self.max_horizon
+        croots, planned, conf, per_root, keep = self._marshal_ta_roots(roots, cap)
+        rc = self._lib.mrp_ll_ta_root_batch(self._h, n, croots, planned.ctypes.data_as(I32P), conf)
+        if raw_rc and rc != 0:
+            return rc
+        self._check(rc, "mrp_ll_ta_root_batch")
+        names = [k for k, _ in mrp_ll_conflict._fields_]
+        return [TaRootResult(planned=int(planned[i]), results=self._results(na, cap, cres, states, actions, costs),
+                             conflict={k: getattr(conf[i], k) for k in names})
+                for i, (na, cres, states, actions, costs) in enumerate(per_root)]
 
     def upload_heuristic(self, map_id: int, dist) -> int:
         """MRP_LL_ASTAR_TA: the shortest-path table of one goal cell, dist[dimy][dimx] (INT32_MAX = unreachable)."""
