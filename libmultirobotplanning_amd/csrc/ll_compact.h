@@ -39,6 +39,11 @@ namespace ct {
 
 using namespace wv;
 
+#ifndef WV_HAS_UNMASKED_GLOADS  // a vocabulary without the unmasked loads: the masked ones with every lane on
+WV_FN V gLoadU16(const uint16_t* base, V idx) { return gLoadU16m(base, idx, bsplat(true)); }
+WV_FN V gLoad32(const uint32_t* base, V idx) { return gLoad32m(base, idx, bsplat(true)); }
+#endif
+
 // ---- LDS window of one search (byte offsets) ------------------------------------------------------------------
 // A heap area: element i at byte 4 * (i + 1), so that the children (2i + 1, 2i + 2) of any node are one aligned 8-byte
 // pair and lane L's 16-byte group of 256-entry group g holds elements 256 g + 4L - 1 .. 256 g + 4L + 2.
@@ -683,7 +688,9 @@ WV_ENTRY int32_t compactSearch(Lds window) {
     const uint32_t t1 = t + 1u;
     if (C::kLongT && t1 >= rowsReady) moreRows();  // (t1 <= maxT + 1 < the job's rows; the walk queue is empty here)
     // the five successor probes: bounds, then ONE bit of the (time, cell) bitmap = obstacle | vertex constraint | already
-    // discovered; requested before the pops so that the latency hides behind them
+    // discovered; requested before the pops so that the latency hides behind them.  It hides only while nothing in front of
+    // the pops USES what a vector load of this block returns (`word`, a0 .. b1 of a table in memory): one use, a select
+    // included, and the compiler waits for every load of the block right here (tests/test_probe_wait_placement_cpu.py)
     const V nx = splat(x) + dx, ny = splat(y) + dy;
     const B inb = (nx < dimx) & (ny < dimy);
     const V ncell = (nx & 31u) | ((ny & 31u) << 5);
@@ -693,13 +700,13 @@ WV_ENTRY int32_t compactSearch(Lds window) {
     // wave's own stores are what its later loads see; an agent-scope load goes past the XCD's L2 to memory and cost
     // 0.9 us per expansion, measured)
     // (unmasked: the lanes that probe nothing look at the word of the Wait successor — the same cache line, no branch)
-    const V word = BG ? gLoad32m(bitsG, wordIdx, bsplat(true)) : ldsLoad32(lds, wordAddr);
+    const V word = BG ? gLoad32(bitsG, wordIdx) : ldsLoad32(lds, wordAddr);
     // other agents' positions at t (a) and t + 1 (b), one agent per lane
     V a0 = splat(0xFFFFu), b0 = splat(0xFFFFu), a1 = splat(0xFFFFu), b1 = splat(0xFFFFu);
     if (EPS && nAgentsPad) {
       const uint32_t ra = t < tPad ? t : tPad - 1u;
       const uint32_t rb = t1 < tPad ? t1 : tPad - 1u;
-      // (lanes beyond a row's end look at the row's last agent instead, and are masked: every read stays inside the table)
+      // (lanes beyond a row's end look at the row's last agent instead: every read stays inside the table)
       if (PLDS) {
         a0 = sel(in0, ldsLoadU16(lds, splat(oPathsX + ra * nAgentsPad * 2u) + col0 * 2u), splat(0xFFFFu));
         b0 = sel(in0, ldsLoadU16(lds, splat(oPathsX + rb * nAgentsPad * 2u) + col0 * 2u), splat(0xFFFFu));
@@ -708,11 +715,14 @@ WV_ENTRY int32_t compactSearch(Lds window) {
           b1 = sel(in1, ldsLoadU16(lds, splat(oPathsX + rb * nAgentsPad * 2u) + col1 * 2u), splat(0xFFFFu));
         }
       } else {
-        a0 = sel(in0, gLoadU16m(pathsG, splat(ra * nAgentsPad) + col0, in0), splat(0xFFFFu));
-        b0 = sel(in0, gLoadU16m(pathsG, splat(rb * nAgentsPad) + col0, in0), splat(0xFFFFu));
+        // the table is in memory: unmasked loads whose values nothing touches before the pops are done — what a lane
+        // beyond the row's end has loaded is left out where the values are counted (valid0 / valid1 below), not here,
+        // so that no select, and with it no wait for the loads, stands in front of the pops
+        a0 = gLoadU16(pathsG, splat(ra * nAgentsPad) + col0);
+        b0 = gLoadU16(pathsG, splat(rb * nAgentsPad) + col0);
         if (nAgentsPad > 64u) {
-          a1 = sel(in1, gLoadU16m(pathsG, splat(ra * nAgentsPad) + col1, in1), splat(0xFFFFu));
-          b1 = sel(in1, gLoadU16m(pathsG, splat(rb * nAgentsPad) + col1, in1), splat(0xFFFFu));
+          a1 = gLoadU16(pathsG, splat(ra * nAgentsPad) + col1);
+          b1 = gLoadU16(pathsG, splat(rb * nAgentsPad) + col1);
         }
       }
     }
@@ -790,13 +800,18 @@ WV_ENTRY int32_t compactSearch(Lds window) {
       // stands on the successor's cell at t + 1 and once more if it swaps places with this agent
       const V nxy = nx | (ny << 8);
       const uint32_t curXy = x | (y << 8);
-      const uint64_t swap0 = ballot(b0 == curXy);
-      const uint64_t swap1 = nAgentsPad > 64u ? ballot(b1 == curXy) : 0ull;
+      // (the lanes that hold an agent: a PLDS instance has put 0xFFFF, which is no cell, into the others already)
+      // (made here from in0 / in1, one compare each, not kept beside col0 / col1 across the search: a scalar pair held
+      // through the whole loop is one more spill in functions that spill scalar registers already)
+      const uint64_t valid0 = PLDS ? ~0ull : ballot(in0);
+      const uint64_t valid1 = PLDS ? ~0ull : nAgentsPad > 64u ? ballot(in1) : 0ull;
+      const uint64_t swap0 = ballot(b0 == curXy) & valid0;
+      const uint64_t swap1 = nAgentsPad > 64u ? ballot(b1 == curXy) & valid1 : 0ull;
       for (uint32_t mm = mask; mm; mm &= mm - 1u) {
         const uint32_t k = ctz32(mm);
         const uint32_t cc = readlane(nxy, k);
-        uint32_t cnt = popc64(ballot(b0 == cc)) + popc64(ballot(a0 == cc) & swap0);
-        if (nAgentsPad > 64u) cnt += popc64(ballot(b1 == cc)) + popc64(ballot(a1 == cc) & swap1);
+        uint32_t cnt = popc64(ballot(b0 == cc) & valid0) + popc64(ballot(a0 == cc) & swap0);
+        if (nAgentsPad > 64u) cnt += popc64(ballot(b1 == cc) & valid1) + popc64(ballot(a1 == cc) & swap1);
         fhV = writelane(fhV, curFh + cnt, k);
       }
     }

@@ -171,6 +171,11 @@ WV_FN void gStore8m(uint8_t* base, V off, V val, B m) {
 }
 WV_FN V gLoadU16m(const uint16_t* base, V idx, B m) { return V(lanePred(m) ? (uint32_t)WV_G(const uint16_t, base)[idx.v] : 0u); }
 WV_FN V gLoad32m(const uint32_t* base, V idx, B m) { return V(lanePred(m) ? WV_G(const uint32_t, base)[idx.v] : 0u); }
+// the unmasked forms, for loads whose every lane names a valid address: no exec region around the load, and nothing that
+// uses the value before the caller does (a vocabulary without them: ll_compact.h falls back to the masked forms, all lanes on)
+#define WV_HAS_UNMASKED_GLOADS 1
+WV_FN V gLoadU16(const uint16_t* base, V idx) { return V((uint32_t)WV_G(const uint16_t, base)[idx.v]); }
+WV_FN V gLoad32(const uint32_t* base, V idx) { return V(WV_G(const uint32_t, base)[idx.v]); }
 // a load that must see what other lanes of this wave (or other workgroups, earlier) stored: an agent-scope load goes
 // past this CU's L1 to the coherent level
 WV_FN V gLoad32Coherent(const uint32_t* base, V idx) {

@@ -125,6 +125,10 @@ WV_FN void gStore8m(uint8_t* base, V off, V val, B m) {
 }
 WV_FN V gLoadU16m(const uint16_t* base, V idx, B m) { return m ? (uint32_t)WV_G(const uint16_t, base)[idx] : 0u; }
 WV_FN V gLoad32m(const uint32_t* base, V idx, B m) { return m ? WV_G(const uint32_t, base)[idx] : 0u; }
+// the unmasked forms (wave_dev.h): every lane's address is valid
+#define WV_HAS_UNMASKED_GLOADS 1
+WV_FN V gLoadU16(const uint16_t* base, V idx) { return (uint32_t)WV_G(const uint16_t, base)[idx]; }
+WV_FN V gLoad32(const uint32_t* base, V idx) { return WV_G(const uint32_t, base)[idx]; }
 // a load that must see what other lanes of this wave (or other workgroups, earlier) stored: an agent-scope load goes
 // past this CU's L1 to the coherent level
 WV_FN V gLoad32Coherent(const uint32_t* base, V idx) {
