@@ -194,6 +194,13 @@ struct CRes {              // at oRes
 #endif
 static_assert(sizeof(CRes) <= 32 && oRes + 64 <= oOpen, "CRes fits its block of the window");
 
+// counting hook of the emulator's drivers (0 erases at the root, 1 group reads of the erase scan, 2 / 3 expansions whose
+// focal counts took the grid / the loop, 4 erases at a position from 256 on, 5 erases of the last element, 6 erases at the
+// root of an open list of more than 512 entries): nothing in the product
+#ifndef MRP_CT_COUNT
+#define MRP_CT_COUNT(k, v) do { } while (0)
+#endif
+
 #define MRP_CT_JOB_U32(lds, field) ldsLoadS(lds, oJob + (uint32_t)offsetof(CJob, field))
 template <class T>
 WV_FN T* jobPtr(Lds lds, uint32_t off) {
@@ -208,6 +215,13 @@ WV_FN uint32_t ctz32(uint32_t v) { return (uint32_t)__builtin_ctz(v); }
 WV_FN uint32_t lg2(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }  // v != 0
 WV_FN uint32_t lo32(uint64_t v) { return (uint32_t)v; }
 WV_FN uint32_t hi32(uint64_t v) { return (uint32_t)(v >> 32); }
+
+#ifndef WV_HAS_MASK_SLICES  // a vocabulary without the slices of wave-uniform masks
+// (what the tier asks of maskShr: sixteen bits of m from bit sh on, sh a multiple of 16 below 64)
+WV_FN V maskShr(uint64_t m, V sh) { return sel((sh & 32u) != 0u, splat(hi32(m)), splat(lo32(m))) >> (sh & 16u); }
+WV_FN V bitSel(V pick, V a, V b) { return (a & pick) | (b & ~pick); }
+WV_FN B lowLanes(uint32_t m) { return (((splat(m) >> laneId()) & 1u) != 0u) & (laneId() < 32u); }
+#endif
 
 // Per-lane constants of the two-heaps-in-one-wave steps: lanes 0..31 ("side A") work on one heap, lanes 32..63 ("side B")
 // on another.  Inside a side, lane l5 owns node l5 of a 31-node (five-level) subtree below the sift-down's hole, and
@@ -334,7 +348,11 @@ WV_FN void pushPairs(Lds lds, const Rows& R, uint32_t hbX, uint32_t kmX, uint32_
   ldsStore32m(lds, dest, sel((R.l4 + 1u) == stop1, e, ae), (!R.isSecond) & (R.l4 < stop1));
   if (nX >= 2u || nY >= 2u) {
     // chains of p and p + 1 have the same depth unless p + 2 is a power of two (p + 1 starts a new level)
+#ifndef MRP_CT_PLAIN_EXPANSION
+    const uint32_t ddX = ((pX + 2u) & (pX + 1u)) == 0u ? 1u : 0u, ddY = ((pY + 2u) & (pY + 1u)) == 0u ? 1u : 0u;
+#else
     const uint32_t ddX = lg2(pX + 2u) - lg2(pX + 1u), ddY = lg2(pY + 2u) - lg2(pY + 1u);
+#endif
     const V dd = sel(R.isY, splat(ddY), splat(ddX));
     const V e1 = sel(R.isY, splat(eY1), splat(eX1));
     const V j1p1 = R.l4 + 1u - dd;                      // index + 1 of the same position on the first chain
@@ -481,9 +499,24 @@ WV_ENTRY int32_t compactSearch(Lds window) {
   const V dx = sel(lane == 1u, splat(0xFFFFFFFFu), sel(lane == 2u, splat(1u), sel(lane < 5u, splat(0u), splat(0x4000u))));
   const V dy = sel(lane == 3u, splat(1u), sel(lane == 4u, splat(0xFFFFFFFFu), splat(0u)));
   // focal context: this lane's agents (columns of the path table)
-  const B in0 = lane < nAgentsPad, in1 = (lane + 64u) < nAgentsPad;
-  const V col0 = sel(in0, lane, splat(nAgentsPad ? nAgentsPad - 1u : 0u));
+  // A table of at most sixteen columns is looked at by the wave as four rows of sixteen lanes ("the grid"): every row holds
+  // all the columns, and row r compares them with the cell of successor r + 1 — Left, Right, Up, Down — which is the popped
+  // cell x | y << 8 plus this lane's gridD (a successor off the map gives a cell no agent stands on, or one that is not
+  // counted: it is not `mine`).  Wait, whose cell is the popped one, shares its first ballot with the swap test and gets
+  // a second of its own.  Lanes 1 .. 4 take slice gridSh of the rows' ballots, lane 0 (gridWait) takes Wait's.
+  // Wider tables: one column per lane, a loop over the successors.
+#ifndef MRP_CT_PLAIN_EXPANSION
+  const bool grid = EPS && nAgentsPad != 0u && nAgentsPad <= 16u;
+#else
+  const bool grid = false;
+#endif
+  const V agent0 = grid ? Rw.l4 : lane;
+  const B in0 = agent0 < nAgentsPad, in1 = (lane + 64u) < nAgentsPad;
+  const V col0 = sel(in0, agent0, splat(nAgentsPad ? nAgentsPad - 1u : 0u));
   const V col1 = sel(in1, lane + 64u, splat(nAgentsPad ? nAgentsPad - 1u : 0u));
+  const V gridD = perRow(Rw, 0xFFFFFFFFu, 1u, 256u, 0xFFFFFF00u);
+  const V gridSh = ((lane - 1u) & 3u) << 4;
+  const V gridWait = sel(lane == 0u, splat(0xFFFFFFFFu), splat(0u));
   const uint32_t tPad = EPS ? MRP_CT_JOB_U32(lds, tPad) : 0u;
   const uint16_t* pathsG = PLDS ? nullptr : MRP_CT_JOB_PTR(const uint16_t, lds, pathsG);
   const int32_t lastGoal = (int32_t)MRP_CT_JOB_U32(lds, lastGoal);
@@ -737,11 +770,23 @@ WV_ENTRY int32_t compactSearch(Lds window) {
       const V lastAddr = hb + bothSides(S, nOpen, nFocal) * 4u;
       const V lastV = ldsLoad32(lds, lastAddr);
       uint32_t p = 0;
-      if (EPS) {  // where is the popped node in the open array?  Lane L looks at elements 4L - 1 .. 4L + 2 of a group.
+      // The popped focal node is very often the open list's top as well (about half of the expansions of a ten-agent
+      // search): a state is in the open array exactly once and the walk leaves the open list alone, so topO is still
+      // element 0, the erase is a plain pop — p = 0, nothing bubbles — and neither the scan nor the bubble is needed.
+      // (-DMRP_CT_PLAIN_EXPANSION: the forms without this and without the grid — the emulator's A/B)
+#ifndef MRP_CT_PLAIN_EXPANSION
+      const bool atRoot = EPS && ((curE ^ topO) & C::kStateMask) == 0u;
+#else
+      const bool atRoot = false;
+#endif
+      MRP_CT_COUNT(0, atRoot ? 1u : 0u);
+      MRP_CT_COUNT(6, atRoot && nOld > 512u ? 1u : 0u);
+      if (EPS && !atRoot) {  // where is the popped node in the open array?  Lane L looks at elements 4L - 1 .. 4L + 2 of a group.
         const V key = splat(curE & C::kStateMask);
         // (narrow geometry: no early exit — a state is in the open array exactly once, and a loop with one exit compiles to
         // half the scalar bookkeeping; the groups behind the hit cost one LDS read each)
         for (uint32_t g = 0; g < kGroups && g * 256u <= nOld; ++g) {  // (element 256 g - 1 belongs to group g)
+          MRP_CT_COUNT(1, 1u);
           const V4 grp = ldsLoad128(lds, splat(oOpen + g * 1024u) + lane * 16u);
           const B m0 = (grp.x & C::kStateMask) == key, m1 = (grp.y & C::kStateMask) == key, m2 = (grp.z & C::kStateMask) == key,
                   m3 = (grp.w & C::kStateMask) == key;
@@ -756,8 +801,10 @@ WV_ENTRY int32_t compactSearch(Lds window) {
       uint32_t lastO = readlane(lastV, 0);
       const uint32_t lastF = EPS ? readlane(lastV, 32) : kFront;  // (no focal list: a key nothing is better than)
       ldsStore32m(lds, lastAddr, splat(kEmpty), S.l5 == 0u);  // the vacated slots: "no element"
-      if (EPS) {  // boost erase = bubble to the root (every ancestor of p moves down one level), then pop
+      if (EPS && !atRoot) {  // boost erase = bubble to the root (every ancestor of p moves down one level), then pop
         const uint32_t depth = lg2(p + 1u);
+        MRP_CT_COUNT(4, p >= 256u ? 1u : 0u);
+        MRP_CT_COUNT(5, p == nOld - 1u && depth != 0u ? 1u : 0u);
         const B act = !S.isB & (S.l5 < depth);
         const V ancPos = (splat(p + 1u) >> (S.l5 + 1u)) - 1u;
         const V ae = ldsLoad32(lds, splat(oOpen + 4u) + ancPos * 4u);
@@ -792,27 +839,44 @@ WV_ENTRY int32_t compactSearch(Lds window) {
     }
 
     // ---- the successors' entries, one per lane 0..4
+#ifndef MRP_CT_PLAIN_EXPANSION
+    const B mine = lowLanes(mask);  // (mask has five bits)
+#else
     const B mine = (lane < 5u) & (((splat(mask) >> lane) & 1u) != 0u);
+#endif
     const V f = sad(nx, splat(gx), sad(ny, splat(gy), splat(t1)));  // g + admissibleHeuristic (ecbs.cpp:276-279)
     V fhV = splat(curFh);
     if (EPS && nAgentsPad) {
       // focalStateHeuristic (ecbs.cpp:282-295) + focalTransitionHeuristic (ecbs.cpp:298-312): an agent counts once if it
       // stands on the successor's cell at t + 1 and once more if it swaps places with this agent
-      const V nxy = nx | (ny << 8);
       const uint32_t curXy = x | (y << 8);
       // (the lanes that hold an agent: a PLDS instance has put 0xFFFF, which is no cell, into the others already)
       // (made here from in0 / in1, one compare each, not kept beside col0 / col1 across the search: a scalar pair held
       // through the whole loop is one more spill in functions that spill scalar registers already)
       const uint64_t valid0 = PLDS ? ~0ull : ballot(in0);
-      const uint64_t valid1 = PLDS ? ~0ull : nAgentsPad > 64u ? ballot(in1) : 0ull;
-      const uint64_t swap0 = ballot(b0 == curXy) & valid0;
-      const uint64_t swap1 = nAgentsPad > 64u ? ballot(b1 == curXy) & valid1 : 0ull;
-      for (uint32_t mm = mask; mm; mm &= mm - 1u) {
-        const uint32_t k = ctz32(mm);
-        const uint32_t cc = readlane(nxy, k);
-        uint32_t cnt = popc64(ballot(b0 == cc) & valid0) + popc64(ballot(a0 == cc) & swap0);
-        if (nAgentsPad > 64u) cnt += popc64(ballot(b1 == cc) & valid1) + popc64(ballot(a1 == cc) & swap1);
-        fhV = writelane(fhV, curFh + cnt, k);
+      const uint64_t swap0 = ballot(b0 == curXy) & valid0;  // on the popped cell at t + 1: in the way of Wait, partner of a swap
+      if (grid) {
+        // every successor at once: sixteen bits of a ballot per successor — the four rows of the two wave-wide ballots, the
+        // first row of Wait's — and lanes 0 .. 4 count their own slices: no loop, no lane read, no lane write
+        MRP_CT_COUNT(2, 1u);
+        const V gcell = splat(curXy) + gridD;
+        const uint64_t vM = ballot(b0 == gcell) & valid0, sM = ballot(a0 == gcell) & swap0;
+        const uint64_t sWait = ballot(a0 == curXy) & swap0;
+        const V ofRows = (maskShr(vM, gridSh) & 0xFFFFu) | (maskShr(sM, gridSh) << 16);
+        const uint32_t ofWait = (lo32(swap0) & 0xFFFFu) | (lo32(sWait) << 16);
+        fhV = splat(curFh) + popc(bitSel(gridWait, splat(ofWait), ofRows));
+      } else {
+        MRP_CT_COUNT(3, 1u);
+        const V nxy = nx | (ny << 8);
+        const uint64_t valid1 = PLDS ? ~0ull : nAgentsPad > 64u ? ballot(in1) : 0ull;
+        const uint64_t swap1 = nAgentsPad > 64u ? ballot(b1 == curXy) & valid1 : 0ull;
+        for (uint32_t mm = mask; mm; mm &= mm - 1u) {
+          const uint32_t k = ctz32(mm);
+          const uint32_t cc = readlane(nxy, k);
+          uint32_t cnt = popc64(ballot(b0 == cc) & valid0) + popc64(ballot(a0 == cc) & swap0);
+          if (nAgentsPad > 64u) cnt += popc64(ballot(b1 == cc) & valid1) + popc64(ballot(a1 == cc) & swap1);
+          fhV = writelane(fhV, curFh + cnt, k);
+        }
       }
     }
     if (EPS && C::kExactFhCheck && ballot(mine & (fhV > kFhMax))) {  // a focalH beyond the entry's field: not a search of this tier
@@ -829,8 +893,14 @@ WV_ENTRY int32_t compactSearch(Lds window) {
     }
     // discovered: stands for stateToHeap / closedSet membership (a_star_epsilon.hpp:224-227)
     if (BG) {  // Wait, Left and Right (lanes 0..2) share the word of row y: each of them stores all of their bits
+#ifndef MRP_CT_PLAIN_EXPANSION
+      // bits x - 1, x, x + 1 for Left, Wait, Right: the low three bits of `mask` with Wait and Left exchanged (a nibble of
+      // the constant), shifted to their place (a successor off the map is not in `mask`: nothing leaves the word)
+      const uint32_t rowBits = (uint32_t)(((uint64_t)((0x75643120u >> ((mask & 7u) << 2)) & 7u) << x) >> 1);
+#else
       const uint32_t bx = 1u << x;
       const uint32_t rowBits = ((mask & 1u) ? bx : 0u) | ((mask & 2u) ? bx >> 1 : 0u) | ((mask & 4u) ? bx << 1 : 0u);
+#endif
       // ... together with cameFrom (a_star_epsilon.hpp:275-279): the action that led here — one masked region
       gStore32and8m(bitsG, wordIdx, word | sel(lane < 3u, splat(rowBits), splat(1u) << (nx & 31u)), parentTab,
                     splat(t1 << 10) + ncell, lane, mine);

@@ -87,6 +87,14 @@ WV_FN V rowShl1(V v, uint32_t fill) { return V((uint32_t)__builtin_amdgcn_update
 WV_FN V bpermute(V v, V src) { return V((uint32_t)__builtin_amdgcn_ds_bpermute((int)((src.v & 63u) << 2), (int)v.v)); }
 // the predicate whose lanes are the set bits of a wave-uniform mask
 WV_FN B laneMask(uint64_t m) { return B{m}; }
+// Slices of wave-uniform masks, per lane (a vocabulary without them: ll_compact.h has both in terms of sel and lane tests).
+// maskShr: the low word of m >> sh, sh < 64 per lane — one v_lshrrev_b64; bitSel: the bits of a where pick is set, of b
+// elsewhere — v_bfi_b32 or a select
+#define WV_HAS_MASK_SLICES 1
+WV_FN V maskShr(uint64_t m, V sh) { return V((uint32_t)(m >> (sh.v & 63u))); }
+WV_FN V bitSel(V pick, V a, V b) { return V((a.v & pick.v) | (b.v & ~pick.v)); }
+// lowLanes: the predicate whose lanes are the set bits of a wave-uniform 32-bit mask — the mask itself
+WV_FN B lowLanes(uint32_t m) { return B{(uint64_t)m}; }
 // The smallest value of the 64 lanes, as a scalar.  Four row_shr steps (1, 2, 4, 8: a lane without a source keeps all
 // ones) leave every 16-lane row's minimum in its last lane; the four row results meet in scalar registers.
 WV_FN uint32_t waveMinU32(V v) {
