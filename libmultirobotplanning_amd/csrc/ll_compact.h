@@ -200,6 +200,12 @@ static_assert(sizeof(CRes) <= 32 && oRes + 64 <= oOpen, "CRes fits its block of 
 #ifndef MRP_CT_COUNT
 #define MRP_CT_COUNT(k, v) do { } while (0)
 #endif
+// ... and the counters of the pushes and the kept roots, from 7 on, for a driver whose hook has room for them
+// (MRP_CT_COUNT_SLOTS; tests/support/emu_push.cpp names them)
+#ifndef MRP_CT_COUNT_SLOTS
+#define MRP_CT_COUNT_SLOTS 7
+#endif
+#define MRP_CT_COUNTX(k, v) do { if ((k) < MRP_CT_COUNT_SLOTS) MRP_CT_COUNT(k, v); } while (0)
 
 #define MRP_CT_JOB_U32(lds, field) ldsLoadS(lds, oJob + (uint32_t)offsetof(CJob, field))
 template <class T>
@@ -215,6 +221,38 @@ WV_FN uint32_t ctz32(uint32_t v) { return (uint32_t)__builtin_ctz(v); }
 WV_FN uint32_t lg2(uint32_t v) { return 31u - (uint32_t)__builtin_clz(v); }  // v != 0
 WV_FN uint32_t lo32(uint64_t v) { return (uint32_t)v; }
 WV_FN uint32_t hi32(uint64_t v) { return (uint32_t)(v >> 32); }
+
+#ifndef WV_HAS_CTZ  // a vocabulary without the find-first-bit: the lowest set bit alone, then its index from the top (v != 0)
+WV_FN V ctz(V v) { return splat(31u) - clz(v & (splat(0u) - v)); }
+#endif
+
+// The two short cuts of the expansion's heap bookkeeping, each with a macro of its own that turns it off alone
+// (-DMRP_CT_PLAIN_EXPANSION turns every short cut off, these two included):
+//   MRP_CT_SCALAR_PUSHES  the successor loop pushes through pushPairs / dualSiftUp, positions and stops in scalar registers
+//   MRP_CT_LOAD_TOPS      the loop top loads the two heap roots from the window instead of keeping them in a register
+// The kept roots measured slower than the load they replace, so they are OFF in the product:
+// -DMRP_CT_KEEP_TOPS turns them on (MRP_CT_LOAD_TOPS, where both are given, wins).
+// -DMRP_CT_CHECK_TOPS (emulator only, implies MRP_CT_KEEP_TOPS): the loop top loads the roots as well and counts every
+// disagreement with the kept ones
+#ifdef MRP_CT_PLAIN_EXPANSION
+#ifndef MRP_CT_SCALAR_PUSHES
+#define MRP_CT_SCALAR_PUSHES
+#endif
+#ifndef MRP_CT_LOAD_TOPS
+#define MRP_CT_LOAD_TOPS
+#endif
+#endif
+#if !defined(MRP_CT_LOAD_TOPS) && !defined(MRP_CT_KEEP_TOPS) && !defined(MRP_CT_CHECK_TOPS)
+#define MRP_CT_LOAD_TOPS
+#endif
+#ifdef MRP_CT_LOAD_TOPS
+#define MRP_CT_KEPT_TOPS false
+#else
+#define MRP_CT_KEPT_TOPS true
+#endif
+#if defined(MRP_CT_CHECK_TOPS) && (defined(MRP_CT_LOAD_TOPS) || defined(__HIP_DEVICE_COMPILE__))
+#error "MRP_CT_CHECK_TOPS checks the kept heap roots: an emulator build without MRP_CT_LOAD_TOPS"
+#endif
 
 #ifndef WV_HAS_MASK_SLICES  // a vocabulary without the slices of wave-uniform masks
 // (what the tier asks of maskShr: sixteen bits of m from bit sh on, sh a multiple of 16 below 64)
@@ -260,7 +298,10 @@ WV_FN V bothSides(const Sides& S, uint32_t a, uint32_t b) { return sel(S.isB, sp
 // chosen child up in one store.  Slots past a heap's end hold "no element" (a key below every real key): the hole stops
 // by itself at a leaf, and a side with nothing (left) to do repeats a block in which nothing moves.  Returns the holes
 // (per lane: the hole of the lane's side).
-WV_FN V dualDescend(Lds lds, const Sides& S, V hb, V km, V cMax, V xk) {
+// TOP: `top` arrives as the element x that fills the hole in the end and leaves, on the root lane of each side (lanes 0 and
+// 32), as the side's new root: the child that node 0 pulled up if the hole left the root, x if it stayed there.
+template <bool TOP>
+WV_FN V dualDescendT(Lds lds, const Sides& S, V hb, V km, V cMax, V xk, V& top) {
   V idx = splat(0u);
   for (;;) {
     const V node = ((idx + 1u) << S.lvl) + S.off1;
@@ -272,6 +313,7 @@ WV_FN V dualDescend(Lds lds, const Sides& S, V hb, V km, V cMax, V xk) {
     const V pe = sel(right, pr.y, pr.x);
     const V pk = sel(right, kr, kl);
     const B go = pk >= xk;                              // the hole moves below this node
+    if (TOP) top = sel(go & (node == 0u), pe, top);     // (node 0 is looked at by the root lane of the first block alone)
     const uint64_t goM = ballot(go), rM = ballot(right);
     const V g32 = bothSides(S, lo32(goM), hi32(goM));
     const V r32 = bothSides(S, lo32(rM), hi32(rM));
@@ -288,6 +330,10 @@ WV_FN V dualDescend(Lds lds, const Sides& S, V hb, V km, V cMax, V xk) {
     if (ballot(steps == 5u) == 0ull) break;
   }
   return idx;
+}
+WV_FN V dualDescend(Lds lds, const Sides& S, V hb, V km, V cMax, V xk) {
+  V none = splat(0u);
+  return dualDescendT<false>(lds, S, hb, km, cMax, xk, none);
 }
 
 // Sift-ups of two heaps at once (boost siftup / libstdc++ __push_heap: while less(parent, e) the parent moves down): a
@@ -311,6 +357,7 @@ WV_FN void dualSiftUp(Lds lds, const Sides& S, V hb, V km, V p1, uint32_t e, boo
 struct Rows {
   V l4;
   B isY, isSecond;   // rows 2, 3 / rows 1, 3
+  V rowSh, heapSh;   // first lane of the row; first lane of the heap's first row
 };
 WV_FN Rows makeRows() {
   Rows r;
@@ -318,6 +365,8 @@ WV_FN Rows makeRows() {
   r.l4 = lane & 15u;
   r.isY = (lane >> 5) != 0u;
   r.isSecond = ((lane >> 4) & 1u) != 0u;
+  r.rowSh = lane & 48u;
+  r.heapSh = lane & 32u;
   return r;
 }
 WV_FN V perRow(const Rows& R, uint32_t x1, uint32_t x2, uint32_t y1, uint32_t y2) {  // rows 0, 1, 2, 3
@@ -365,6 +414,52 @@ WV_FN void pushPairs(Lds lds, const Rows& R, uint32_t hbX, uint32_t kmX, uint32_
     const V stop2 = sel(R.isY, splat(sY2), splat(sX2));
     ldsStore32m(lds, dest, sel((R.l4 + 1u) == stop2, e, now), R.isSecond & (R.l4 < stop2));
   }
+}
+
+// this lane's row of a ballot: first lane of the row's sixteen whose bit is off, plus one.  (A sift-up row always has one:
+// the lanes beyond the chain's root read the word in front of the array, which no element is better than.)
+WV_FN V rowStop(uint64_t worse, V rowSh) { return ctz(~maskShr(worse, rowSh)) + 1u; }
+
+// One turn of the expansion's successor loop: pushPairs' step — up to two consecutive pushes into the open list (rows 0, 1)
+// and the focal pushes of those of the two that are within the bound (rows 2, 3), all four chains loaded before anything
+// moves, the same fix-up of a heap's second chain — with the bookkeeping per lane instead of per wave: what is left in scalar
+// registers is the turn's two successor bits (`pair`, `low` its lower one), the two lane reads and one branch.
+//   sideBits  the successors of the expansion that go into this lane's heap: `mask` on the open side, `maskF` on the focal
+//   n         entries of this lane's heap before the turn; counted up here
+//   tops      the root of this lane's heap (what counts is the root lane of each side, lanes 0 and 32), kept current: a
+//             push becomes the root exactly when the root's key is less than its own — every ancestor's key is <= the
+//             root's, so the sift-up runs to the top then, and stops at the root or below otherwise; equal keys stay
+// A row without a push (position + 1 = 1: its lanes read the word in front of the array) stores nothing.
+template <bool TOPS>
+WV_FN void pushTurn(Lds lds, const Rows& R, V hb, V km, V sideBits, uint32_t pair, uint32_t low, uint32_t e1s, uint32_t e2s, V& n,
+                    V& tops) {
+  const V pf = sideBits & pair;
+  const V cnt = popc(pf);                                 // pushes into this lane's heap: 0, 1, 2
+  // (a heap's second row pushes when there are two: no per-lane constant beside the predicate the rows have already)
+  const B act = sel(R.isSecond, cnt >> 1u, cnt) != 0u;
+  const V p1 = sel(act, sel(R.isSecond, n + 2u, n + 1u), splat(1u));  // position + 1 of this row's push
+  const V e1 = sel((pf & low) != 0u, splat(e1s), splat(e2s));  // the first (or only) element of this lane's heap
+  const V e = sel(R.isSecond, splat(e2s), e1);
+  const V ek = e & km;
+  const V ancIdx = p1 >> (R.l4 + 1u);
+  const V ae = ldsLoad32(lds, hb + ancIdx * 4u - 4u);   // (lanes beyond the root: the word in front of the array)
+  const V dest = hb + (p1 >> R.l4) * 4u - 4u;           // lane l4 < stop: ancestor l4 moves down to here; lane == stop: e
+  const V stop1 = rowStop(ballot((ae & km) < ek), R.heapSh);  // (of the heap's FIRST row: the second row's fix-up asks for it)
+  ldsStore32m(lds, dest, sel((R.l4 + 1u) == stop1, e, ae), (!R.isSecond) & act & (R.l4 < stop1));
+  if (TOPS) tops = sel(((tops & km) < (e1 & km)) & (cnt != 0u), e1, tops);
+  if ((pair ^ low) != 0u) {
+    // chains of p and p + 1 have the same depth unless p + 2 (the second row's p1) is a power of two
+    const V dd = sel((p1 & (p1 - 1u)) == 0u, splat(1u), splat(0u));
+    const V j1p1 = R.l4 + 1u - dd;                      // index + 1 of the same position on the first chain
+    const B shared = (R.l4 >= dd) & (ancIdx == ((p1 - 1u) >> j1p1));
+    const V up = rowShl1(ae, kFront);                   // the parent of this lane's ancestor
+    // (p = 0: the first push IS the root, the parent of position 1)
+    const V now = sel(shared, sel((j1p1 + 1u) < stop1, up, sel((j1p1 + 1u) == stop1, e1, ae)), sel((p1 == 2u) & (R.l4 == 0u), e1, ae));
+    const V stop2 = rowStop(ballot((now & km) < ek), R.rowSh);
+    ldsStore32m(lds, dest, sel((R.l4 + 1u) == stop2, e, now), R.isSecond & act & (R.l4 < stop2));
+    if (TOPS) tops = sel(((tops & km) < (splat(e2s) & km)) & (cnt > 1u), splat(e2s), tops);  // (a heap's second element is e2s)
+  }
+  n += cnt;
 }
 
 // ---- one search ------------------------------------------------------------------------------------------------
@@ -525,6 +620,7 @@ WV_ENTRY int32_t compactSearch(Lds window) {
   uint8_t* parentTab = MRP_CT_JOB_PTR(uint8_t, lds, parentTab);
   const uint32_t goalCell = gx | (gy << 5);
   int32_t bestF;
+  V tops;  // the roots: lane 0 open.top(), lane 32 focal.top() (an empty list: kEmpty, whose key every push is better than)
   {
     const uint32_t sx = MRP_CT_JOB_U32(lds, sx), sy = MRP_CT_JOB_U32(lds, sy);
     const uint32_t h0 = (sx > gx ? sx - gx : gx - sx) + (sy > gy ? sy - gy : gy - sy);
@@ -532,6 +628,7 @@ WV_ENTRY int32_t compactSearch(Lds window) {
     const uint32_t e0 = (kFhMax << kFhShift) | ((kFMax - h0) << kFShift) | ((C::kLongT ? 63u - h0 : 0u) << 10) | (sx | (sy << 5));
     ldsStoreS(lds, oOpen + 4u, e0);
     if (EPS) ldsStoreS(lds, oFocal + 4u, e0);
+    tops = splat(e0);
   }
   sync();
   MRP_CT_PROF_MARK(0);
@@ -541,8 +638,16 @@ WV_ENTRY int32_t compactSearch(Lds window) {
       status = C_NO_SOLUTION;
       break;
     }
-    const V tops = ldsLoad32(lds, hb);                   // lanes 0..31: open.top(), lanes 32..63: focal.top()
-    const uint32_t topO = readlane(tops, 0);
+#ifdef MRP_CT_LOAD_TOPS
+    tops = ldsLoad32(lds, hb);                           // lanes 0..31: open.top(), lanes 32..63: focal.top()
+#elif defined(MRP_CT_CHECK_TOPS)
+    {
+      const V seen = ldsLoad32(lds, hb);
+      MRP_CT_COUNTX(8, 1u);
+      MRP_CT_COUNTX(9, (readlane(seen, 0) != readlane(tops, 0) || (EPS && readlane(seen, 32) != readlane(tops, 32))) ? 1u : 0u);
+    }
+#endif
+    const uint32_t topO = readlane(tops, 0);             // (kept across the loop: the pop and the pushes say what the roots become)
     uint32_t curE = EPS ? readlane(tops, 32) : topO;
     if (EPS) {
       const int32_t fTop = (int32_t)(kFMax - ((topO >> kFShift) & kFMax));
@@ -661,6 +766,9 @@ WV_ENTRY int32_t compactSearch(Lds window) {
         }
         if (status == C_OVERFLOW) break;
         curE = ldsLoadS(lds, oFocal + 4u);
+#ifndef MRP_CT_LOAD_TOPS
+        tops = sel(S.isB, splat(curE), tops);            // the walk has pushed into the focal list (and left the open list alone)
+#endif
         }
         MRP_CT_PROF_MARK(1);
       }
@@ -817,8 +925,22 @@ WV_ENTRY int32_t compactSearch(Lds window) {
         }
       }
       const V xk = bothSides(S, lastO & kMO, lastF & kMF);
+      const V x = bothSides(S, lastO, lastF);
+      const B some = bothSides(S, nOpen, EPS ? nFocal : 0u) != 0u;
+#ifdef MRP_CT_LOAD_TOPS
       const V hole = dualDescend(lds, S, hb, km, splat(kHeapClamp), xk);
-      ldsStore32m(lds, hb + hole * 4u, bothSides(S, lastO, lastF), (S.l5 == 0u) & (bothSides(S, nOpen, EPS ? nFocal : 0u) != 0u));
+#else
+      // the new roots: what node 0 pulled up in the first block of the way down, or the re-inserted last element
+      V top = x;
+      const V hole = dualDescendT<true>(lds, S, hb, km, splat(kHeapClamp), xk, top);
+      MRP_CT_COUNTX(10, nOpen != 0u && readlane(top, 0) == lastO ? 1u : 0u);
+      MRP_CT_COUNTX(11, nOpen != 0u && readlane(top, 0) != lastO ? 1u : 0u);
+      MRP_CT_COUNTX(12, EPS && nFocal != 0u && readlane(top, 32) == lastF ? 1u : 0u);
+      MRP_CT_COUNTX(13, EPS && nFocal != 0u && readlane(top, 32) != lastF ? 1u : 0u);
+      tops = sel(some, top, splat(kEmpty));
+#endif
+      MRP_CT_COUNTX(7, EPS && !atRoot ? 1u : 0u);
+      ldsStore32m(lds, hb + hole * 4u, x, (S.l5 == 0u) & some);
     }
 
     MRP_CT_PROF_MARK(3);
@@ -912,6 +1034,49 @@ WV_ENTRY int32_t compactSearch(Lds window) {
     MRP_CT_PROF_MARK(4);
     // ---- openSet.push for every successor, focalSet.push for those within the bound, in successor order — two successors
     // per step (pushes into different lists do not see each other, so the four chains of a step are loaded together)
+#ifndef MRP_CT_SCALAR_PUSHES
+    // (pushTurn: positions, elements' rows, stops and the kept roots per lane; one form for one and for two successors)
+    {
+      const V sideBits = bothSides(S, mask, maskF);
+      V nV = bothSides(S, nOpen, nFocal);
+      const uint32_t nSucc = (uint32_t)__builtin_popcount(mask);
+      MRP_CT_COUNTX(16, nSucc == 3u ? 1u : 0u);
+      MRP_CT_COUNTX(17, nSucc == 4u ? 1u : 0u);
+      MRP_CT_COUNTX(18, nSucc == 5u ? 1u : 0u);
+      for (uint32_t mm = mask; mm;) {
+        const uint32_t rest1 = mm & (mm - 1u);
+        const uint32_t rest2 = rest1 & (rest1 - 1u);       // (0 stays 0)
+        const uint32_t low = mm ^ rest1, pair = mm ^ rest2;
+        // (one successor: the second lane read looks at lane 5, whose entry no row takes)
+        const uint32_t e1 = readlane(eV, ctz32(mm)), e2 = readlane(eV, ctz32(rest1 | 32u));
+        if (MRP_CT_COUNT_SLOTS > 14) {  // what the turn is, for the emulator's drivers: nothing of this in the product
+          const bool two = rest1 != 0u, f1 = (maskF & low) != 0u, f2 = (maskF & pair & ~low) != 0u;
+          const uint32_t pO = readlane(nV, 0), pF = readlane(nV, 32), rO = readlane(tops, 0), rF = readlane(tops, 32);
+          MRP_CT_COUNTX(14, two ? 0u : 1u);
+          MRP_CT_COUNTX(15, two ? 1u : 0u);
+          MRP_CT_COUNTX(19, f1 != f2 ? 1u : 0u);             // a focal row 2 alone
+          MRP_CT_COUNTX(20, f1 && f2 ? 1u : 0u);             // rows 2 and 3
+          MRP_CT_COUNTX(21, !f1 && f2 ? 1u : 0u);            // the pair's first successor outside the bound, its second inside
+          MRP_CT_COUNTX(22, two && ((pO + 2u) & (pO + 1u)) == 0u ? 1u : 0u);       // the second chain one level deeper: open
+          MRP_CT_COUNTX(23, f1 && f2 && ((pF + 2u) & (pF + 1u)) == 0u ? 1u : 0u);  // ... focal
+          MRP_CT_COUNTX(24, (pO == 0u ? 1u : 0u) + ((f1 || f2) && pF == 0u ? 1u : 0u));  // pushes into position 0
+          const uint32_t eF1 = f1 ? e1 : e2;
+          const bool o1 = pO == 0u || (rO & kMO) < (e1 & kMO), fr1 = (f1 || f2) && (pF == 0u || (rF & kMF) < (eF1 & kMF));
+          MRP_CT_COUNTX(25, o1 ? 1u : 0u);                   // a first push that becomes the root: open
+          MRP_CT_COUNTX(26, fr1 ? 1u : 0u);                  // ... focal
+          MRP_CT_COUNTX(27, two && o1 && (e1 & kMO) < (e2 & kMO) ? 1u : 0u);       // a second push that displaces the first: open
+          MRP_CT_COUNTX(28, f1 && f2 && fr1 && (e1 & kMF) < (e2 & kMF) ? 1u : 0u);  // ... focal
+          const uint32_t rO2 = o1 ? e1 : rO, rF2 = fr1 ? eF1 : rF;
+          MRP_CT_COUNTX(29, (pO != 0u && (rO & kMO) == (e1 & kMO) ? 1u : 0u) + (two && (rO2 & kMO) == (e2 & kMO) ? 1u : 0u));  // a key equal to the root's: open
+          MRP_CT_COUNTX(30, ((f1 || f2) && pF != 0u && (rF & kMF) == (eF1 & kMF) ? 1u : 0u) + (f1 && f2 && (rF2 & kMF) == (e2 & kMF) ? 1u : 0u));  // ... focal
+        }
+        pushTurn<MRP_CT_KEPT_TOPS>(lds, Rw, hb, km, sideBits, pair, low, e1, e2, nV, tops);
+        mm = rest2;
+      }
+      nOpen += nSucc;
+      nFocal += (uint32_t)__builtin_popcount(maskF);
+    }
+#else
     for (uint32_t mm = mask; mm;) {
       const uint32_t k1 = ctz32(mm);
       mm &= mm - 1u;
@@ -927,9 +1092,17 @@ WV_ENTRY int32_t compactSearch(Lds window) {
       else
 #endif
         pushPairs(lds, Rw, oOpen + 4u, kMO, nOpen, nX, e1, e2, oFocal + 4u, kMF, nFocal, nY, f1 ? e1 : e2, e2);
+#ifndef MRP_CT_LOAD_TOPS
+      {  // the kept roots: each push becomes its list's root exactly when the root's key is less than its own
+        const V cntS = bothSides(S, nX, nY), first = bothSides(S, e1, f1 ? e1 : e2);
+        tops = sel(((tops & km) < (first & km)) & (cntS != 0u), first, tops);
+        tops = sel(((tops & km) < (splat(e2) & km)) & (cntS > 1u), splat(e2), tops);
+      }
+#endif
       nOpen += nX;
       nFocal += nY;
     }
+#endif
     MRP_CT_PROF_MARK(5);
   }
   // the result block of the window

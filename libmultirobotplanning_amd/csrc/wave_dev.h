@@ -116,6 +116,9 @@ WV_FN uint32_t waveMinU32(V v) {
 }
 WV_FN V clz(V v) { return V((uint32_t)__builtin_clz(v.v)); }          // v != 0
 WV_FN V popc(V v) { return V((uint32_t)__builtin_popcount(v.v)); }
+// index of the lowest set bit, v != 0 — v_ffbl_b32 (a vocabulary without it: ll_compact.h has it in terms of clz)
+#define WV_HAS_CTZ 1
+WV_FN V ctz(V v) { return V((uint32_t)__builtin_ctz(v.v)); }
 WV_FN float uintAsFloat(uint32_t v) { return __uint_as_float(v); }
 WV_FN V sad(V a, V b, V c) { return V(((a.v > b.v ? a.v : b.v) - (a.v > b.v ? b.v : a.v)) + c.v); }  // |a - b| + c  (v_sad_u32)
 WV_FN float fmulRn(float a, float b) { return __fmul_rn(a, b); }  // binary32 product, no contraction

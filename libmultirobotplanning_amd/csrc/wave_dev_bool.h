@@ -61,6 +61,8 @@ WV_FN V shr1(V v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v,
 WV_FN V rowShl1(V v, uint32_t fill) { return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x101, 0xF, 0xF, false); }
 WV_FN V clz(V v) { return (uint32_t)__builtin_clz(v); }          // v != 0
 WV_FN V popc(V v) { return (uint32_t)__builtin_popcount(v); }
+#define WV_HAS_CTZ 1
+WV_FN V ctz(V v) { return (uint32_t)__builtin_ctz(v); }               // v != 0
 WV_FN float uintAsFloat(uint32_t v) { return __uint_as_float(v); }
 WV_FN V sad(V a, V b, V c) { return ((a > b ? a : b) - (a > b ? b : a)) + c; }  // |a - b| + c  (v_sad_u32)
 WV_FN float fmulRn(float a, float b) { return __fmul_rn(a, b); }  // binary32 product, no contraction

@@ -87,7 +87,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--tag", default="this tree")
-    ap.add_argument("--define", action="append", default=[], help="a further -D macro, e.g. MRP_CT_PLAIN_EXPANSION")
+    ap.add_argument("--define", action="append", default=[],
+                    help="a further -D macro: MRP_CT_PLAIN_EXPANSION, MRP_CT_SCALAR_PUSHES, MRP_CT_LOAD_TOPS, MRP_CT_KEEP_TOPS ...")
     a = ap.parse_args()
     tmp = tempfile.mkdtemp(prefix="phase_mix_")
     try:
