@@ -247,6 +247,37 @@ typedef struct mrp_hl_ta_solution {
 int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options* opt, int32_t n_instances,
                               const mrp_hl_ta_instance* instances, mrp_hl_ta_solution* solutions, mrp_hl_batch_stats* stats);
 
+/* ---- ECBS with task assignment (ecbs_ta.hpp:94-352 over the Environment of example/ecbs_ta.cpp), batched ------------------
+ * The reference as example/ecbs_ta.cpp compiles it: REBUILT_FOCAL_LIST and STYLE_MINROOT, Cost = int, low level AStarEpsilon
+ * (MRP_LL_ASTAR_EPS_TA) under the same weight w.  Instances, options, solutions, tasks, the tie order among assignments of
+ * equal cost, the limits and the error statuses are CBS-TA's above.  What differs:
+ *   - A root plans its agents in index order, each against the paths of the agents before it only; a node's cost is the sum of
+ *     its paths' costs, its LB the sum of their fmin, its focalHeuristic the number of all conflicts (mrp_ll_conflict's count).
+ *   - The FIRST root is planned even when the first assignment is empty — every agent is then without a task and
+ *     num_task_assignments stays 0 (ecbs_ta.hpp:104,117-137; CBS-TA gives up there).
+ *   - The open list is ordered by cost alone; the focal list is rebuilt before every expansion from the open list's ordered
+ *     walk, up to the first node with (float)cost > nextRootNodeCost, and is ordered by focalHeuristic, then cost.
+ *     nextRootNodeCost is an int: LB * w, multiplied in binary32 and truncated, of the first root and then of the open
+ *     list's top after every new-root attempt.
+ *   - AFTER the two children of an expanded node are pushed, open.top().cost > nextRootNodeCost asks for the next assignment;
+ *     a non-empty one is planned as a new root, which takes `id` and is pushed only when every agent got a path.
+ * The reference reads three things it may not have; here they are defined:
+ *   - an empty open list at the new-root test (ecbs_ta.hpp:302) counts as "ask for a new root";
+ *   - an open list that is still empty after the attempt (:344) ends the instance MRP_HL_NO_SOLUTION;
+ *   - an empty focal list at an expansion (:238; the truncation can leave the top's cost above nextRootNodeCost) ends the
+ *     instance MRP_HL_LL_ERROR.
+ * Round-based over all instances; a round makes at most one mrp_ll_assign_series_next, one mrp_ll_ta_eps_root_batch for the
+ * new roots and one mrp_ll_search_batch of MRP_LL_ASTAR_EPS_TA jobs: for every expanded node its two child searches with the
+ * node's paths as the shipped focal context.  With options.use_root_kernel = 0 a root is n_agents dependent jobs of that
+ * batch instead, one agent per round, each with the paths before it as its context, and the driver scans and counts
+ * itself; the results are the same.  One expansion can take several rounds either way (children, then assignment and root).
+ * A NULL options pointer means use_root_kernel = 0, as do the Python and CLI front-ends: roots as jobs measured faster at
+ * the reference shape with thousands of instances, the root call at a few hundred.
+ * w >= 1 (else MRP_LL_E_INVALID).  root_conflicts counts the expanded nodes with a conflict that carry the root flag (a
+ * child is a copy of its parent, flag included). */
+int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_ta_options* opt, int32_t n_instances,
+                               const mrp_hl_ta_instance* instances, mrp_hl_ta_solution* solutions, mrp_hl_batch_stats* stats);
+
 /* BASELINE.json configs[0] — `./a_star` on a text map (example/a_star.cpp:72-125,190-191) — is host plumbing: a single
  * 2-D A* (AStar::search a_star.hpp:63-161, neighbours Up, Down, Left, Right, unit costs, Manhattan heuristic), run on
  * the CPU with the reference's heap tie-breaks.  obstacle_mask[y * dimx + x] != 0 = '#'.  Returns the number of states

@@ -678,6 +678,25 @@ typedef struct mrp_ll_ta_root {
 int mrp_ll_ta_root_batch(mrp_ll_ctx* ctx, int32_t n_roots, const mrp_ll_ta_root* roots, int32_t* planned /* [n_roots] */,
                          mrp_ll_conflict* conflicts /* [n_roots] */);
 
+/* ---- the root node of an ECBS-TA conflict tree ------------------------------------------------------------------
+ * ECBS with task assignment plans a root agent after agent (ecbs_ta.hpp:117-138, :306-343): agent a's AStarEpsilon search
+ * under weight w has no constraints and sees the paths of agents 0 .. a - 1 as its focal context; then
+ * Environment::focalHeuristic counts the conflicts of the n paths.  As with mrp_ll_ta_root_batch ONE workgroup does that for
+ * one root, and a batch of roots is ONE kernel launch that ends (mrp_ll_ta_eps_root_kernel).  The roots are mrp_ll_ta_root
+ * records; what is said there holds here, with these differences:
+ * results[a] is field for field what the ordinary MRP_LL_ASTAR_EPS_TA job {map_id, w, agent_idx = a, start, goal,
+ * heuristic_id or MRP_LL_JOB_NO_GOAL, no constraints, n_agents, and as shipped context the paths of agents 0 .. a - 1, the
+ * others empty} returns — fmin included, whose sum is the node's LB.
+ * conflicts[r].count is the node's focalHeuristic (ecbs_ta.cpp:347-382).
+ * The workgroup keeps ONE time-major table in its arena slot's path area: the focal context of the next search and the
+ * scan's input.  If a path would make the table outgrow the area (only under MRP_LL_ARENA_PATHS_BYTES: by default 64 agents
+ * x 1024 steps fit), the kernel stops behind that agent and the CALL completes the root before it returns — the remaining
+ * agents as ordinary jobs with shipped contexts, one after the other under what is left of the budget, and the scan by
+ * mrp_ll_conflict_scan.  The caller always receives the same answer.
+ * MRP_LL_E_INVALID also for w < 1 or NaN. */
+int mrp_ll_ta_eps_root_batch(mrp_ll_ctx* ctx, float w, int32_t n_roots, const mrp_ll_ta_root* roots,
+                             mrp_ll_conflict* conflicts /* [n_roots] */, int32_t* planned /* [n_roots] */);
+
 int mrp_ll_get_stats(const mrp_ll_ctx* ctx, mrp_ll_stats* out);
 int mrp_ll_reset_stats(mrp_ll_ctx* ctx);
 

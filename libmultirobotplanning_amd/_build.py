@@ -20,14 +20,15 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-f
 TARGETS = {
     "libmrp_ll.so": dict(srcs=["ll_kernel.hip", "conflict_kernel.hip", "heur_kernel.hip", "assign_kernel.hip", "mrp_ll_host.cpp"],
                          deps=["ll_device.h", "ll_slot.h", "ll_compact.h", "ll_arena_heap.h", "ll_arena_search.h", "ll_jobs.h", "ll_ta.h",
-                               "ll_ta_root.h", "ll_sipp.h", "ll_node_scan.h", "wave_dev.h", "wave_dev_bool.h", "heur_bfs.h", "heur_layout.h",
+                               "ll_ta_root.h", "ll_ta_eps_root.h", "ll_sipp.h", "ll_node_scan.h", "wave_dev.h", "wave_dev_bool.h", "heur_bfs.h", "heur_layout.h",
                                "assign_wave.h", "assign_layout.h", "host/assign_pack.h", "host/assign_series.h",
-                               "host/ll_assign_host.h", "host/ta_root_pack.h", "host/ll_ta_root_host.h",
+                               "host/ll_assign_host.h", "host/ta_root_pack.h", "host/ll_ta_root_host.h", "host/ta_eps_root_pack.h", "host/ll_ta_eps_root_host.h",
                                "ll_launch.h", "host/ll_pack.h", "host/ll_sipp_table.h", "host/ll_unpack.h", "host/ll_ctx.h",
                                "host/ll_maps.h", "host/ll_heur_host.h", "host/ll_stores.h", "host/ll_batch.h",
                                "host/ll_session.h", "host/ll_session_jobs.h", "host/ll_submit.h", "../../include/mrp_ll.h"],
                          extra=[]),
-    "libmrp_hl.so": dict(srcs=["hl/mrp_hl.cpp", "hl/mrp_hl_ta.cpp"], deps=["hl/exact_heap.hpp", "hl/cbs_ta_tree.hpp", "hl/grid_mapf.hpp", "hl/ct_solver.hpp",
+    "libmrp_hl.so": dict(srcs=["hl/mrp_hl.cpp", "hl/mrp_hl_ta.cpp", "hl/mrp_hl_ecbs_ta.cpp"],
+                         deps=["hl/exact_heap.hpp", "hl/cbs_ta_tree.hpp", "hl/ecbs_ta_tree.hpp", "hl/ta_batch_setup.hpp", "hl/grid_mapf.hpp", "hl/ct_solver.hpp",
                                                        "hl/ct_session.hpp", "hl/grid2d_astar.hpp", "hl/instance_io.hpp",
                                                        "hl/solve_knobs.hpp", "hl/launch_plan.hpp", "hl/rounds_driver.hpp",
                                                        "hl/sipp_drivers.hpp", "hl/ct_stepped.hpp",

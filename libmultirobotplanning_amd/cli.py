@@ -4,6 +4,8 @@
     python -m libmultirobotplanning_amd.cli cbs  -i in.yaml -o out.yaml            (example/cbs.cpp:571-667)
     python -m libmultirobotplanning_amd.cli cbs_ta -i in.yaml -o out.yaml [--maxTaskAssignments N]   (example/cbs_ta.cpp:523-617:
         agents[].{name,start,potentialGoals}; statistics also has numTaskAssignments, and a state's t is its cost so far)
+    python -m libmultirobotplanning_amd.cli ecbs_ta -i in.yaml -o out.yaml -w 1.3 [--maxTaskAssignments N]
+                                                                                   (example/ecbs_ta.cpp:587-695, as cbs_ta)
     python -m libmultirobotplanning_amd.cli sipp -i in.yaml -o out.yaml            (example/sipp.cpp:149-236)
     python -m libmultirobotplanning_amd.cli mapf_prioritized_sipp -i in.yaml -o out.yaml
                                                                                    (example/mapf_prioritized_sipp.cpp:157-295)
@@ -107,13 +109,19 @@ def read_ta_instance(path: str) -> Dict:
 
 
 def main_cbs_ta(args, ap) -> int:
-    """cbs_ta -i in.yaml -o out.yaml [--maxTaskAssignments N]: the output of example/cbs_ta.cpp:589-614."""
+    """cbs_ta -i in.yaml -o out.yaml [--maxTaskAssignments N]: the output of example/cbs_ta.cpp:589-614.
+    ecbs_ta -i in.yaml -o out.yaml -w W [--maxTaskAssignments N]: the output of example/ecbs_ta.cpp:655-689, which has the
+    same form."""
     from . import hl
     if len(args.input) != len(args.output):
         ap.error("give one -o per -i")
     insts = [read_ta_instance(p) for p in args.input]
-    res, st = hl.solve_cbs_ta_batch(insts, max_task_assignments=args.maxTaskAssignments, device=args.device,
-                                    max_ll_expansions=args.max_ll_expansions, path_cap=1024)
+    if args.algo == "ecbs_ta":
+        res, st = hl.solve_ecbs_ta_batch(insts, args.suboptimality, max_task_assignments=args.maxTaskAssignments, device=args.device,
+                                         max_ll_expansions=args.max_ll_expansions, path_cap=1024)
+    else:
+        res, st = hl.solve_cbs_ta_batch(insts, max_task_assignments=args.maxTaskAssignments, device=args.device,
+                                        max_ll_expansions=args.max_ll_expansions, path_cap=1024)
     rc = 0
     for r, path in zip(res, args.output):
         if r["status"] != hl.SOLVED:
@@ -335,14 +343,14 @@ def main_assignment(args, ap) -> int:
 def main(argv: List[str] = None) -> int:
     ap = argparse.ArgumentParser(prog="libmultirobotplanning_amd.cli")
     ap.add_argument("algo", choices=["ecbs", "cbs", "sipp", "mapf_prioritized_sipp", "a_star", "shortest_path_heuristic",
-                                     "assignment", "next_best_assignment", "cbs_ta"])
+                                     "assignment", "next_best_assignment", "cbs_ta", "ecbs_ta"])
     ap.add_argument("-i", "--input", action="append", default=[], help="input file (YAML)")
     ap.add_argument("-o", "--output", action="append", default=[], help="output file (YAML)")
-    ap.add_argument("-w", "--suboptimality", type=float, default=1.0, help="suboptimality bound (ecbs)")
+    ap.add_argument("-w", "--suboptimality", type=float, default=1.0, help="suboptimality bound (ecbs, ecbs_ta)")
     ap.add_argument("-m", "--map", help="input map (txt) (a_star)")
     for k in ("startX", "startY", "goalX", "goalY"):
         ap.add_argument("--" + k, type=int, help="a_star: %s" % k)
-    ap.add_argument("--maxTaskAssignments", type=int, default=10 ** 9, help="cbs_ta: maximum number of task assignments to try")
+    ap.add_argument("--maxTaskAssignments", type=int, default=10 ** 9, help="cbs_ta, ecbs_ta: maximum number of task assignments to try")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--max-ll-expansions", type=int, default=-1, help="harness cap per instance (reference: none)")
     args = ap.parse_args(argv)
@@ -354,7 +362,7 @@ def main(argv: List[str] = None) -> int:
         ap.error("the following arguments are required: -o/--output")
     if args.algo in ("assignment", "next_best_assignment"):
         return main_assignment(args, ap)
-    if args.algo == "cbs_ta":
+    if args.algo in ("cbs_ta", "ecbs_ta"):
         return main_cbs_ta(args, ap)
     if args.algo in ("ecbs", "cbs"):
         return main_mapf(args, ap)

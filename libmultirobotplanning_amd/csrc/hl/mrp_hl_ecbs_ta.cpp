@@ -1,29 +1,31 @@
-// mrp_hl_solve_cbs_ta_batch (include/mrp_hl.h): CBS with task assignment for a batch of instances, round-based.  The trees are
-// hl/cbs_ta_tree.hpp's state machines (speculation width 1); a round makes three engine calls over ALL instances:
-//   1. mrp_ll_assign_series_next  for the trees that need a root (one launch for all their series' children)
-//   2. mrp_ll_ta_root_batch       for the new roots (use_root_kernel = 0: their n searches join call 3, the tree scans itself)
-//   3. mrp_ll_search_batch        for the child searches
-// and then lets every tree run up to its next request.  A translation unit of its own: csrc/hl/mrp_hl.cpp neither includes nor
-// calls it, so the drivers there still link against engines that have no table, assignment or root calls.
+// mrp_hl_solve_ecbs_ta_batch (include/mrp_hl.h): ECBS with task assignment for a batch of instances, round-based.  The trees
+// are hl/ecbs_ta_tree.hpp's state machines; a round makes at most three engine calls over ALL instances:
+//   1. mrp_ll_assign_series_next   for the trees whose new-root test (or start) asks for an assignment
+//   2. mrp_ll_ta_eps_root_batch    for the new roots, one workgroup each (use_root_kernel = 0: a root is n dependent jobs of
+//                                  call 3, one agent per round, each with the paths of the agents before it as its shipped
+//                                  focal context, and the tree scans and counts itself)
+//   3. mrp_ll_search_batch         MRP_LL_ASTAR_EPS_TA jobs: for every tree with an expanded node, its two child searches with
+//                                  the node's paths as the context
+// and then lets every tree run up to its next request.  The trees scan and count their children's conflicts themselves.
+// A translation unit of its own, like csrc/hl/mrp_hl_ta.cpp.
 #include <chrono>
 #include <cstring>
 #include <memory>
 #include <vector>
 
 #include "../../../include/mrp_hl.h"
-#include "cbs_ta_tree.hpp"
+#include "ecbs_ta_tree.hpp"
 #include "ta_batch_setup.hpp"
 
 namespace {
 
-using mrp_hl::ta::Conflict;
+using mrp_hl::ecbs_ta::Tree;
+using mrp_hl::ta::Cons;
 using mrp_hl::ta::Engine;
 using mrp_hl::ta::kPathCap;
-using mrp_hl::ta::Path;
 using mrp_hl::ta::PathP;
 using mrp_hl::ta::pathOf;
 using mrp_hl::ta::ResultPool;
-using mrp_hl::ta::Tree;
 
 // What a search's status means to its tree: 0 a path, 1 no path (the reference's `success == false`), else the tree ends.
 int verdict(Tree& t, const mrp_ll_result& r) {
@@ -33,15 +35,35 @@ int verdict(Tree& t, const mrp_ll_result& r) {
   return 2;
 }
 
-void taskJob(mrp_ll_job& j, const Tree& t, int agent, int32_t task, const mrp_hl::ta::Cons* cons, int64_t budget) {
+// The focal context of one job: the solution vector the search sees (its own entry is ignored, an empty path is skipped).
+struct Context {
+  std::vector<int32_t> len;
+  std::vector<const int32_t*> xy;
+  void of(const std::vector<PathP>& sol) {
+    static const int32_t none[2] = {0, 0};
+    len.assign(sol.size(), 0);
+    xy.assign(sol.size(), none);
+    for (size_t a = 0; a < sol.size(); ++a)
+      if (sol[a]) {
+        len[a] = sol[a]->len();
+        xy[a] = sol[a]->xy.data();
+      }
+  }
+};
+
+void epsJob(mrp_ll_job& j, const Tree& t, int agent, int32_t task, const Cons* cons, const Context& ctx, int64_t budget) {
   std::memset(&j, 0, sizeof(j));
   j.map_id = t.mapId;
-  j.algo = MRP_LL_ASTAR_TA;
-  j.w = 1.0f;
+  j.algo = MRP_LL_ASTAR_EPS_TA;
+  j.w = t.w;
+  j.agent_idx = agent;
   j.start_x = t.starts[2 * agent];
   j.start_y = t.starts[2 * agent + 1];
   j.result_path_id = -1;
   j.max_expansions = budget;
+  j.n_agents = static_cast<int32_t>(ctx.len.size());
+  j.path_len = ctx.len.data();
+  j.path_xy = ctx.xy.data();
   if (task >= 0) {
     j.goal_x = t.taskXY[2 * task];
     j.goal_y = t.taskXY[2 * task + 1];
@@ -60,17 +82,17 @@ void taskJob(mrp_ll_job& j, const Tree& t, int agent, int32_t task, const mrp_hl
 
 }  // namespace
 
-extern "C" int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options* optIn, int32_t n, const mrp_hl_ta_instance* inst,
-                                         mrp_hl_ta_solution* sols, mrp_hl_batch_stats* stats) {
-  if (n < 0 || (n > 0 && (!inst || !sols))) return MRP_LL_E_INVALID;
-  if (stats) std::memset(stats, 0, sizeof(*stats));
-  if (n == 0) return MRP_LL_SUCCESS;
+extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_ta_options* optIn, int32_t n,
+                                          const mrp_hl_ta_instance* inst, mrp_hl_ta_solution* sols, mrp_hl_batch_stats* stats) {
+  if (n < 0 || (n > 0 && (!inst || !sols)) || !(w >= 1.0f)) return MRP_LL_E_INVALID;
   mrp_hl_ta_options opt;
   std::memset(&opt, 0, sizeof(opt));
   opt.max_task_assignments = 1 << 30;
-  opt.use_root_kernel = 0;  // (measured slower in the driver at the reference shape: DESIGN.md section 5)
   opt.max_hl_expansions = opt.max_ll_expansions = -1;
+  opt.use_root_kernel = 0;  // (measured slower in the driver at the reference shape: DESIGN.md section 5)
   if (optIn) opt = *optIn;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (n == 0) return MRP_LL_SUCCESS;
 
   Engine eng;
   mrp_ll_options lo;
@@ -84,6 +106,7 @@ extern "C" int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options
   std::vector<std::unique_ptr<Tree>> trees;
   rc = mrp_hl::ta::setUpBatch(eng, n, inst, trees);
   if (rc != MRP_LL_SUCCESS) return rc;
+  for (int32_t k = 0; k < n; ++k) trees[k]->w = w;
 
   // ---- the rounds
   const auto t0 = std::chrono::steady_clock::now();
@@ -95,7 +118,7 @@ extern "C" int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options
       if (trees[k]->running()) live.push_back(k);
     if (live.empty()) break;
     rounds += 1;
-    // 1. the next assignment of every tree that needs a root
+    // 1. the next assignment of every tree that asks for one
     {
       std::vector<mrp_ll_assign_series*> ask;
       std::vector<int32_t> who;
@@ -128,31 +151,25 @@ extern "C" int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options
       return opt.max_ll_expansions > t.llExpanded ? opt.max_ll_expansions - t.llExpanded : 0;
     };
     std::vector<int32_t> rootOf, childOf;  // trees with a pending root / pending children
-    size_t nRootSearches = 0;
     for (int32_t k : live) {
-      Tree& t = *trees[k];
+      const Tree& t = *trees[k];
       if (!t.running()) continue;
-      if (t.wantRoot) {
-        rootOf.push_back(k);
-        nRootSearches += static_cast<size_t>(t.nAgents);
-      }
+      if (t.wantRoot) rootOf.push_back(k);
       if (t.wantChildren) childOf.push_back(k);
     }
-    const size_t nResults = nRootSearches + 2 * childOf.size();
+    // the results of the round: the roots' (n each through the root call, one each as jobs), then two per pair of children
+    std::vector<size_t> rootFirst(rootOf.size() + 1, 0);
+    for (size_t q = 0; q < rootOf.size(); ++q)
+      rootFirst[q + 1] = rootFirst[q] + (opt.use_root_kernel ? static_cast<size_t>(trees[rootOf[q]]->nAgents) : 1u);
+    const size_t nRootResults = rootFirst[rootOf.size()], nRootJobs = opt.use_root_kernel ? 0u : rootOf.size();
+    const size_t nResults = nRootResults + 2 * childOf.size(), nJobs = nRootJobs + 2 * childOf.size();
     pool.reserve(nResults);
     std::vector<mrp_ll_result> res(nResults + 1);
     for (size_t q = 0; q < nResults; ++q) pool.attach(res[q], q);
-    std::vector<size_t> rootFirst(rootOf.size());
-    {
-      size_t at = 0;
-      for (size_t q = 0; q < rootOf.size(); ++q) {
-        rootFirst[q] = at;
-        at += static_cast<size_t>(trees[rootOf[q]]->nAgents);
-      }
-    }
+    std::vector<Context> ctx(rootOf.size() + childOf.size());
+    std::vector<mrp_ll_job> jobs(nJobs);
     std::vector<int32_t> planned(rootOf.size() + 1, 0);
-    std::vector<mrp_ll_conflict> rootConf(rootOf.size() + 1);
-    std::vector<mrp_ll_job> jobs;
+    std::vector<mrp_ll_conflict> rootScan(rootOf.size() + 1);
     std::vector<std::vector<int32_t>> rootGoals(rootOf.size()), rootHeur(rootOf.size());
     if (opt.use_root_kernel) {
       // 2. the new roots, one workgroup each
@@ -177,68 +194,78 @@ extern "C" int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options
         r.results = res.data() + rootFirst[q];
       }
       if (!rootOf.empty()) {
-        rc = mrp_ll_ta_root_batch(eng.ctx, static_cast<int32_t>(rootOf.size()), roots.data(), planned.data(), rootConf.data());
+        rc = mrp_ll_ta_eps_root_batch(eng.ctx, w, static_cast<int32_t>(rootOf.size()), roots.data(), rootScan.data(), planned.data());
         if (rc != MRP_LL_SUCCESS) return rc;
       }
     } else {
       for (size_t q = 0; q < rootOf.size(); ++q) {
         const Tree& t = *trees[rootOf[q]];
-        for (int a = 0; a < t.nAgents; ++a) {
-          jobs.emplace_back();
-          taskJob(jobs.back(), t, a, t.rootTasks[a], nullptr, budgetOf(t));
-        }
+        ctx[q].of(t.rootPaths);
+        epsJob(jobs[q], t, t.rootAgent, t.rootTasks[t.rootAgent], nullptr, ctx[q], budgetOf(t));
       }
     }
-    // 3. the child searches (and, without the root kernel, the roots' searches in front of them)
-    for (int32_t k : childOf) {
-      const Tree& t = *trees[k];
-      for (int c = 0; c < 2; ++c) {
-        jobs.emplace_back();
-        taskJob(jobs.back(), t, t.childAgent[c], t.nodes[t.popped].taskOf[t.childAgent[c]], t.childCons[c].get(), budgetOf(t));
-      }
+    // 3. the child searches (and, without the root call, the roots' next searches in front of them)
+    for (size_t q = 0; q < childOf.size(); ++q) {
+      const Tree& t = *trees[childOf[q]];
+      Context& c = ctx[rootOf.size() + q];
+      c.of(t.nodes[t.popped].sol);
+      for (int s = 0; s < 2; ++s)
+        epsJob(jobs[nRootJobs + 2 * q + s], t, t.childAgent[s], t.nodes[t.popped].taskOf[t.childAgent[s]], t.childCons[s].get(), c,
+               budgetOf(t));
     }
     if (!jobs.empty()) {
-      mrp_ll_result* out = opt.use_root_kernel ? res.data() + nRootSearches : res.data();
-      rc = mrp_ll_search_batch(eng.ctx, static_cast<int32_t>(jobs.size()), jobs.data(), out);
+      rc = mrp_ll_search_batch(eng.ctx, static_cast<int32_t>(jobs.size()), jobs.data(), res.data() + (nRootResults - nRootJobs));
       if (rc != MRP_LL_SUCCESS) return rc;
     }
-    // the roots first: a new root is pushed BEFORE the two children (cbs_ta.hpp:165-168 in front of :179-210)
     for (size_t q = 0; q < rootOf.size(); ++q) {
       Tree& t = *trees[rootOf[q]];
-      std::vector<PathP> paths(static_cast<size_t>(t.nAgents));
-      int done = 0;
-      bool all = true;
-      for (int a = 0; a < t.nAgents && t.running(); ++a) {
-        const mrp_ll_result& r = res[rootFirst[q] + a];
-        if (opt.use_root_kernel && a >= planned[q]) break;
-        done += 1;
+      if (!opt.use_root_kernel) {
+        const mrp_ll_result& r = res[rootFirst[q]];
         t.nSearches += 1;
         t.nRootSearches += 1;
         t.llExpanded += r.expanded;  // (the expansions of a failed root count)
         const int v = verdict(t, r);
-        if (v == 0) paths[a] = pathOf(r);
-        if (v != 0) {
-          all = false;
-          break;  // the root ends behind this agent (cbs_ta.hpp:159-162): later answers, if any, are not looked at
+        if (v != 2) t.gotRootSearch(v == 0 ? pathOf(r) : nullptr, r.fmin);
+        continue;
+      }
+      std::vector<PathP> paths(static_cast<size_t>(t.nAgents));
+      std::vector<int32_t> fmin(static_cast<size_t>(t.nAgents), 0);
+      int done = 0;
+      bool all = true;
+      for (int a = 0; a < t.nAgents && a < planned[q] && all && t.running(); ++a) {
+        const mrp_ll_result& r = res[rootFirst[q] + a];
+        done += 1;
+        t.nSearches += 1;
+        t.nRootSearches += 1;
+        t.llExpanded += r.expanded;
+        const int v = verdict(t, r);
+        if (v == 0) {
+          paths[a] = pathOf(r);
+          fmin[a] = r.fmin;
+        } else {
+          all = false;  // the root ends behind this agent (ecbs_ta.hpp:323-326)
         }
       }
       if (!t.running()) continue;
-      Conflict c;
-      if (all && done == t.nAgents)
-        c = opt.use_root_kernel ? mrp_hl::ta::conflictFromScan(rootConf[q], paths) : mrp_hl::ta::firstConflict(paths);
-      t.gotRoot(paths, done, c);
+      if (all && done != t.nAgents)
+        t.end(MRP_HL_LL_ERROR);  // (the call completes every root it accepts: a refused one)
+      else
+        t.gotRoot(paths, fmin, done, rootScan[q]);
     }
     for (size_t q = 0; q < childOf.size(); ++q) {
       Tree& t = *trees[childOf[q]];
-      if (!t.running()) continue;
       PathP path[2];
-      for (int c = 0; c < 2 && t.running(); ++c) {
-        const mrp_ll_result& r = res[nRootSearches + 2 * q + c];
+      int32_t fmin[2] = {0, 0};
+      for (int s = 0; s < 2 && t.running(); ++s) {
+        const mrp_ll_result& r = res[nRootResults + 2 * q + s];
         t.nSearches += 1;
         t.llExpanded += r.expanded;
-        if (verdict(t, r) == 0) path[c] = pathOf(r);
+        if (verdict(t, r) == 0) {
+          path[s] = pathOf(r);
+          fmin[s] = r.fmin;
+        }
       }
-      if (t.running()) t.gotChildren(path);
+      if (t.running()) t.gotChildren(path, fmin);
     }
     for (int32_t k : live) {
       Tree& t = *trees[k];

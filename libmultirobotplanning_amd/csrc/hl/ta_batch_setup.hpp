@@ -1,0 +1,135 @@
+// What the two task-assignment drivers (csrc/hl/mrp_hl_ta.cpp: CBS-TA, csrc/hl/mrp_hl_ecbs_ta.cpp: ECBS-TA) share around their
+// trees: the engine context with its assignment series, the caller-side result buffers of a round, a result turned into a
+// tree's path, and the set-up of a batch — maps, tasks, one launch for all shortest-path tables, one for all optima.
+#pragma once
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "../../../include/mrp_hl.h"
+#include "cbs_ta_tree.hpp"
+
+namespace mrp_hl {
+namespace ta {
+
+constexpr int32_t kPathCap = 512;  // the engine's default max_horizon: no path is longer
+
+// The caller-side buffers of one round's results: states and action costs, kPathCap per search.
+struct ResultPool {
+  std::vector<int32_t> states, costs;
+  void reserve(size_t n) {
+    if (states.size() < n * kPathCap * 3) states.resize(n * kPathCap * 3);
+    if (costs.size() < n * kPathCap) costs.resize(n * kPathCap);
+  }
+  void attach(mrp_ll_result& r, size_t k) {
+    std::memset(&r, 0, sizeof(r));
+    r.states_txy = states.data() + k * kPathCap * 3;
+    r.action_costs = costs.data() + k * kPathCap;
+    r.states_cap = kPathCap;
+  }
+};
+
+inline PathP pathOf(const mrp_ll_result& r) {
+  auto p = std::make_shared<Path>();
+  p->cost = r.cost;
+  int32_t g = 0;
+  for (int k = 0; k < r.n_states; ++k) {
+    p->xy.push_back(r.states_txy[3 * k + 1]);
+    p->xy.push_back(r.states_txy[3 * k + 2]);
+    p->g.push_back(g);
+    if (k + 1 < r.n_states) g += r.action_costs[k];
+  }
+  return p;
+}
+
+struct Engine {
+  mrp_ll_ctx* ctx = nullptr;
+  std::vector<mrp_ll_assign_series*> series;
+  ~Engine() {
+    for (mrp_ll_assign_series* s : series)
+      if (s) mrp_ll_assign_series_destroy(s);
+    if (ctx) mrp_ll_destroy(ctx);
+  }
+};
+
+// Fills trees[k] (TreeT: ta::Tree or ecbs_ta::Tree) from inst[k]; an instance beyond the limits ends MRP_HL_LL_ERROR.
+// Returns MRP_LL_SUCCESS or the engine's error.
+template <typename TreeT>
+int setUpBatch(Engine& eng, int32_t n, const mrp_hl_ta_instance* inst, std::vector<std::unique_ptr<TreeT>>& trees) {
+  typedef TreeT Tree;
+  int rc = MRP_LL_SUCCESS;
+  // ---- the instances: maps, tasks, one launch for all tables, one for all optima
+  trees.clear();
+  trees.resize(static_cast<size_t>(n));
+  std::vector<int32_t> tabMap, tabGoal;
+  for (int32_t k = 0; k < n; ++k) {
+    const mrp_hl_ta_instance& I = inst[k];
+    trees[k].reset(new Tree());
+    Tree& t = *trees[k];
+    t.nAgents = I.n_agents;
+    if (I.n_agents < 1 || I.n_agents > 64 || !I.starts_xy || !I.goal_first || (I.goal_first[I.n_agents] > 0 && !I.goals_xy) ||
+        mrp_ll_upload_map(eng.ctx, I.dimx, I.dimy, I.n_obstacles, I.obstacles_xy, &t.mapId) != MRP_LL_SUCCESS) {
+      t.nAgents = I.n_agents > 0 && I.n_agents <= 64 ? I.n_agents : 0;
+      t.end(MRP_HL_LL_ERROR);
+      continue;
+    }
+    t.starts.assign(I.starts_xy, I.starts_xy + 2 * I.n_agents);
+    t.allowed.assign(static_cast<size_t>(I.n_agents), 0);
+    bool tooMany = false;
+    for (int a = 0; a < I.n_agents; ++a) {
+      if (t.starts[2 * a] < 0 || t.starts[2 * a] >= I.dimx || t.starts[2 * a + 1] < 0 || t.starts[2 * a + 1] >= I.dimy) tooMany = true;
+      for (int q = I.goal_first[a]; q < I.goal_first[a + 1]; ++q) {
+        const int32_t gx = I.goals_xy[2 * q], gy = I.goals_xy[2 * q + 1];
+        if (gx < 0 || gx >= I.dimx || gy < 0 || gy >= I.dimy) continue;  // can never be assigned
+        size_t task = 0;
+        while (task < t.taskXY.size() / 2 && !(t.taskXY[2 * task] == gx && t.taskXY[2 * task + 1] == gy)) ++task;
+        if (task == t.taskXY.size() / 2) t.taskXY.insert(t.taskXY.end(), {gx, gy});
+        if (task >= 64) {
+          tooMany = true;
+          break;
+        }
+        t.allowed[a] |= 1ull << task;
+      }
+    }
+    if (tooMany) {
+      t.end(MRP_HL_LL_ERROR);
+      continue;
+    }
+    for (size_t task = 0; task < t.taskXY.size() / 2; ++task) {
+      tabMap.push_back(t.mapId);
+      tabGoal.insert(tabGoal.end(), {t.taskXY[2 * task], t.taskXY[2 * task + 1]});
+    }
+  }
+  std::vector<int32_t> tabIds(tabMap.size() + 1, -1);
+  rc = mrp_ll_compute_heuristics(eng.ctx, static_cast<int32_t>(tabMap.size()), tabMap.data(), tabGoal.data(), tabIds.data());
+  if (rc != MRP_LL_SUCCESS) return rc;
+  {
+    std::vector<mrp_ll_assign_problem> probs;
+    std::vector<int32_t> treeOf;
+    size_t next = 0;
+    for (int32_t k = 0; k < n; ++k) {
+      Tree& t = *trees[k];
+      if (!t.running()) continue;
+      t.taskHeur.assign(tabIds.begin() + next, tabIds.begin() + next + t.taskXY.size() / 2);
+      next += t.taskXY.size() / 2;
+      mrp_ll_assign_problem p;
+      std::memset(&p, 0, sizeof(p));
+      p.n_agents = t.nAgents;
+      p.n_tasks = static_cast<int32_t>(t.taskHeur.size());
+      p.heuristic_ids = t.taskHeur.data();
+      p.starts_xy = t.starts.data();
+      p.allowed = t.allowed.data();
+      probs.push_back(p);
+      treeOf.push_back(k);
+    }
+    eng.series.assign(static_cast<size_t>(n), nullptr);
+    std::vector<mrp_ll_assign_series*> made(probs.size() + 1, nullptr);
+    rc = mrp_ll_assign_series_create(eng.ctx, static_cast<int32_t>(probs.size()), probs.data(), made.data());
+    if (rc != MRP_LL_SUCCESS) return rc;
+    for (size_t q = 0; q < treeOf.size(); ++q) eng.series[treeOf[q]] = made[q];
+  }
+  return MRP_LL_SUCCESS;
+}
+
+}  // namespace ta
+}  // namespace mrp_hl

@@ -1,0 +1,198 @@
+// mrp_ll_ta_eps_root_batch: the roots of ECBS-TA conflict trees, one workgroup each, in ONE launch of
+// mrp_ll_ta_eps_root_kernel (ll_ta_eps_root.h).  ll_ta_root_host.h's shape: the packer of ta_eps_root_pack.h, the first
+// ticket's staging buffers and stream, the launch parameters of an ordinary batch, unpackResult on the way back.  A root
+// whose table outgrew its arena slot's path area is finished here before the call returns: the agents the kernel did not
+// reach as ordinary MRP_LL_ASTAR_EPS_TA jobs with shipped contexts, one after the other, and the scan by mrp_ll_conflict_scan.
+#pragma once
+#include "ll_batch.h"
+#include "ll_ctx.h"
+#include "ll_heur_host.h"
+#include "ll_maps.h"
+#include "ta_eps_root_pack.h"
+
+namespace {
+
+// The agents planned[k] .. n - 1 of root R as ordinary jobs; paths: the planned agents' ([x, y] per state), extended here.
+// Returns an engine error, or MRP_LL_SUCCESS with `all` = every agent has a path.
+int taEpsRootRest(mrp_ll_ctx* ctx, float w, const mrp_ll_ta_root& R, int32_t& planned, std::vector<std::vector<int32_t>>& paths, bool& all) {
+  const int32_t cap = ctx->env.maxHorizon;
+  std::vector<int32_t> st(static_cast<size_t>(cap) * 3), ac(cap), co(cap), len(R.n_agents, 0);
+  std::vector<const int32_t*> xy(R.n_agents, nullptr);
+  int64_t budget = R.max_expansions;
+  for (int a = 0; a < planned && budget >= 0; ++a) budget = budget > R.results[a].expanded ? budget - R.results[a].expanded : 0;
+  all = true;
+  while (planned < R.n_agents) {
+    const int a = planned;
+    for (int q = 0; q < R.n_agents; ++q) {
+      len[q] = q < a ? static_cast<int32_t>(paths[q].size() / 2) : 0;
+      xy[q] = q < a ? paths[q].data() : st.data();
+    }
+    mrp_ll_job j;
+    std::memset(&j, 0, sizeof(j));
+    j.map_id = R.map_id;
+    j.algo = MRP_LL_ASTAR_EPS_TA;
+    j.w = w;
+    j.agent_idx = a;
+    j.start_x = R.starts_xy[2 * a];
+    j.start_y = R.starts_xy[2 * a + 1];
+    j.n_agents = R.n_agents;
+    j.path_len = len.data();
+    j.path_xy = xy.data();
+    j.max_expansions = budget;
+    j.result_path_id = -1;
+    j.heuristic_id = R.heuristic_ids[a];
+    if (R.heuristic_ids[a] >= 0) {
+      j.goal_x = R.goals_xy[2 * a];
+      j.goal_y = R.goals_xy[2 * a + 1];
+    } else {
+      j.flags = MRP_LL_JOB_NO_GOAL;
+    }
+    mrp_ll_result full;
+    std::memset(&full, 0, sizeof(full));
+    full.states_txy = st.data();
+    full.actions = ac.data();
+    full.action_costs = co.data();
+    full.states_cap = cap;
+    const int rc = mrp_ll_search_batch(ctx, 1, &j, &full);
+    if (rc != MRP_LL_SUCCESS) return rc;
+    mrp_ll_result& out = R.results[a];  // what the caller's buffers hold of it, as unpackResult fills them
+    out.status = full.status; out.cost = full.cost; out.fmin = full.fmin; out.n_states = full.n_states;
+    out.expanded = full.expanded; out.tier = full.tier;
+    planned += 1;
+    if (full.status != MRP_LL_OK) {
+      all = false;
+      break;
+    }
+    const int lim = std::min(full.n_states, out.states_cap);
+    if (out.states_txy) std::memcpy(out.states_txy, st.data(), static_cast<size_t>(lim) * 12);
+    for (int k = 0; k + 1 < full.n_states && k < out.states_cap; ++k) {
+      if (out.actions) out.actions[k] = ac[k];
+      if (out.action_costs) out.action_costs[k] = co[k];
+    }
+    if ((out.states_txy || out.actions) && out.states_cap < full.n_states) out.status = MRP_LL_PATH_TRUNCATED;
+    paths.emplace_back();
+    for (int k = 0; k < full.n_states; ++k) paths.back().insert(paths.back().end(), {st[3 * k + 1], st[3 * k + 2]});
+    if (budget >= 0) budget = budget > full.expanded ? budget - full.expanded : 0;
+  }
+  for (int a = planned; a < R.n_agents; ++a) mrp::host::notRunResult(R.results[a], MRP_LL_NOT_RUN);
+  return MRP_LL_SUCCESS;
+}
+
+int taEpsRootLaunch(mrp_ll_ctx* ctx, float w, int32_t n, const mrp_ll_ta_root* roots, int32_t* planned, mrp_ll_conflict* conflicts) {
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  int rc = syncMaps(ctx);
+  if (rc != MRP_LL_SUCCESS) return rc;
+  rc = reserveMapsDev(ctx, 1);
+  if (rc != MRP_LL_SUCCESS) return rc;
+  Ticket& t = ctx->tickets[0];  // idle: no session, no batch in flight
+  auto packT0 = std::chrono::steady_clock::now();
+  mrp::host::TaRootStaging st;
+  mrp::host::packTaEpsRoots(ctx->env, w, n, roots, 0, st);
+  const uint32_t outStride = static_cast<uint32_t>(ctx->env.maxHorizon) + mrp::kScanOutHalfs;
+  const uint32_t nDev = static_cast<uint32_t>(st.recs.size());
+  std::vector<int32_t> needScan, needRest;
+  if (nDev == 0) {
+    mrp::host::unpackTaEpsRoots(ctx->stats, st, n, roots, nullptr, nullptr, outStride, planned, conflicts, needScan, needRest);
+    return MRP_LL_SUCCESS;
+  }
+  t.jobs.clear();
+  t.cons.clear();
+  t.paths.clear();
+  HIPCHK(ctx, t.jobs.resize(nDev));
+  HIPCHK(ctx, t.cons.resize(std::max<size_t>(st.words.size(), 16)));
+  HIPCHK(ctx, t.paths.reserve(16));
+  HIPCHK(ctx, t.results.resize(st.nResults));
+  HIPCHK(ctx, t.outPaths.resize(static_cast<size_t>(st.nResults) * outStride));
+  std::memcpy(t.jobs.host, st.recs.data(), nDev * sizeof(DevJob));
+  std::memcpy(t.cons.host, st.words.data(), st.words.size() * 4);
+  mrp::host::blankTaRootAnswers(st, t.outPaths.host, outStride);
+  ctx->stats.pack_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - packT0).count();
+  ctx->stats.staged_bytes += static_cast<int64_t>(nDev * sizeof(DevJob) + st.words.size() * 4);
+
+  mrp::LaunchParams P;
+  std::memset(&P, 0, sizeof(P));
+  P.jobs = t.jobs.dev;
+  P.results = t.results.dev;
+  P.out_paths = t.outPaths.dev;
+  P.cons = t.cons.dev;
+  P.paths = t.paths.dev;
+  P.queue_base = t.queueBase;  // (the kernel takes no tickets)
+  P.n_jobs = nDev;
+  uint32_t ldsBytes = 0;
+  rc = fillCommonParams(ctx, t, P, ldsBytes, 0);  // the mixed kernel's window: what an MRP_LL_ASTAR_EPS_TA batch is launched with
+  if (rc != MRP_LL_SUCCESS) return rc;
+  const uint32_t grid = std::min<uint32_t>(nDev, static_cast<uint32_t>(ctx->opt.slots));
+  HIPCHK(ctx, hipEventRecord(t.evK0, t.stream));
+  HIPCHK(ctx, mrp_ll_launch_ta_eps_root(&P, grid, ldsBytes, t.stream));
+  HIPCHK(ctx, hipEventRecord(t.evK1, t.stream));
+  HIPCHK(ctx, hipEventSynchronize(t.evK1));
+  ctx->stats.launches += 1;
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, t.evK0, t.evK1) == hipSuccess) ctx->stats.kernel_ms += ms;
+
+  auto unpackT0 = std::chrono::steady_clock::now();
+  mrp::host::unpackTaEpsRoots(ctx->stats, st, n, roots, t.results.host, t.outPaths.host, outStride, planned, conflicts, needScan,
+                              needRest);
+  ctx->stats.unpack_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - unpackT0).count();
+  if (needScan.empty() && needRest.empty()) return MRP_LL_SUCCESS;
+  // The paths of those roots as the device returned them, taken out of the ticket's buffers before the next batch uses them.
+  std::vector<int32_t> todo = needScan;
+  todo.insert(todo.end(), needRest.begin(), needRest.end());
+  std::vector<std::vector<std::vector<int32_t>>> paths(todo.size());
+  for (size_t q = 0; q < todo.size(); ++q) {
+    const int32_t k = todo[q];
+    for (int a = 0; a < planned[k]; ++a) {
+      const uint32_t ri = st.firstResult[k] + static_cast<uint32_t>(a);
+      const uint16_t* p = t.outPaths.host + static_cast<size_t>(ri) * outStride;
+      const int32_t len = std::min<int32_t>(t.results.host[ri].n_states, ctx->env.maxHorizon);
+      paths[q].emplace_back();
+      for (int32_t s = 0; s < len; ++s) paths[q].back().insert(paths[q].back().end(), {p[s] & 0xFF, p[s] >> 8});
+    }
+  }
+  std::vector<int32_t> setFirst(1, 0), pathFirst(1, 0), states, scanned;
+  for (size_t q = 0; q < todo.size(); ++q) {
+    const int32_t k = todo[q];
+    bool all = true;
+    if (q >= needScan.size()) {
+      rc = taEpsRootRest(ctx, w, roots[k], planned[k], paths[q], all);
+      if (rc != MRP_LL_SUCCESS) return rc;
+    }
+    if (!all) continue;  // no node: found stays -1
+    for (const std::vector<int32_t>& p : paths[q]) {
+      states.insert(states.end(), p.begin(), p.end());
+      pathFirst.push_back(static_cast<int32_t>(states.size() / 2));
+    }
+    setFirst.push_back(static_cast<int32_t>(pathFirst.size()) - 1);
+    scanned.push_back(k);
+  }
+  if (scanned.empty()) return MRP_LL_SUCCESS;
+  std::vector<mrp_ll_conflict> found(scanned.size());
+  rc = mrp_ll_conflict_scan(ctx, static_cast<int32_t>(scanned.size()), setFirst.data(), pathFirst.data(), states.data(), found.data());
+  if (rc != MRP_LL_SUCCESS) return rc;
+  for (size_t q = 0; q < scanned.size(); ++q) conflicts[scanned[q]] = found[q];
+  return MRP_LL_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrp_ll_ta_eps_root_batch(mrp_ll_ctx* ctx, float w, int32_t nRoots, const mrp_ll_ta_root* roots, mrp_ll_conflict* conflicts,
+                             int32_t* planned) {
+  if (!ctx) return MRP_LL_E_INVALID;
+  if (nRoots < 0 || !(w >= 1.0f) || (nRoots > 0 && (!roots || !planned || !conflicts))) {
+    ctx->err = "mrp_ll_ta_eps_root_batch: invalid argument";
+    return MRP_LL_E_INVALID;
+  }
+  if (engineBusy(ctx)) {
+    ctx->err = "mrp_ll_ta_eps_root_batch: a session is active or a batch is in flight";
+    return MRP_LL_E_BUSY;
+  }
+  if (nRoots == 0) return MRP_LL_SUCCESS;
+  mrp::host::blankTaRootOutputs(ctx->env, nRoots, roots, planned, conflicts);
+  const int rc = taEpsRootLaunch(ctx, w, nRoots, roots, planned, conflicts);
+  if (rc != MRP_LL_SUCCESS) mrp::host::blankTaRootOutputs(ctx->env, nRoots, roots, planned, conflicts);  // nothing half-told
+  return rc;
+}
+
+}  // extern "C"

@@ -42,8 +42,10 @@ static inline bool taRootValid(const PackEnv& env, const mrp_ll_ta_root& r) {
   return true;
 }
 
-// wordBase: where st.words will stand in the launch's constraint-word buffer.
-static inline void packTaRoots(const PackEnv& env, int32_t n, const mrp_ll_ta_root* roots, uint32_t wordBase, TaRootStaging& st) {
+// wordBase: where st.words will stand in the launch's constraint-word buffer.  algo / w: MRP_LL_ASTAR_TA (w unused) for
+// mrp_ll_ta_root_batch, MRP_LL_ASTAR_EPS_TA and its weight for mrp_ll_ta_eps_root_batch (ll_device.h taEpsRootAgentJob).
+static inline void packTaRootsAs(const PackEnv& env, uint32_t algo, float w, int32_t n, const mrp_ll_ta_root* roots, uint32_t wordBase,
+                                 TaRootStaging& st) {
   st.recs.clear();
   st.words.clear();
   st.devRootOf.assign(n, -1);
@@ -59,7 +61,8 @@ static inline void packTaRoots(const PackEnv& env, int32_t n, const mrp_ll_ta_ro
     d.dimx = mp.dimx;
     d.dimy = mp.dimy;
     d.words_per_row = mp.wpr;
-    d.algo = MRP_LL_ASTAR_TA;
+    d.algo = algo;
+    d.w = w;
     d.max_expansions = r.max_expansions;
     d.last_goal_constraint = -1;  // no constraints
     d.vc_off = wordBase + static_cast<uint32_t>(st.words.size());
@@ -80,6 +83,10 @@ static inline void packTaRoots(const PackEnv& env, int32_t n, const mrp_ll_ta_ro
     st.nResults += static_cast<uint32_t>(r.n_agents);
     st.recs.push_back(d);
   }
+}
+
+static inline void packTaRoots(const PackEnv& env, int32_t n, const mrp_ll_ta_root* roots, uint32_t wordBase, TaRootStaging& st) {
+  packTaRootsAs(env, MRP_LL_ASTAR_TA, 0.0f, n, roots, wordBase, st);
 }
 
 // The answer words of a root in its first result's output area.

@@ -136,6 +136,19 @@ MRP_DEV_FN void taRootAgentJob(DevJob& d, uint32_t startGoal, uint32_t heurOff, 
   d.max_expansions = budget;
   d.n_ctx = 0; d.reserved = 0;
 }
+// The root node of an ECBS-TA conflict tree (mrp_ll_ta_eps_root_batch; ll_ta_eps_root.h): the record and the agent words are
+// the CBS-TA root's above, with algo MRP_LL_ASTAR_EPS_TA and w.  Agent a's descriptor: what packJob makes for the ordinary
+// unconstrained MRP_LL_ASTAR_EPS_TA job whose shipped context is the paths of agents 0 .. a - 1 — the table's width and rows
+// (0, 0 for agent 0, whose context is empty) —, except path_off: the workgroup's table lies in its slot already.
+MRP_DEV_FN void taEpsRootAgentJob(DevJob& d, uint32_t startGoal, uint32_t heurOff, uint32_t flags, int64_t budget, uint32_t nAgentsPad,
+                                  uint32_t tPad) {
+  d.sx = startGoal & 0xFFu; d.sy = (startGoal >> 8) & 0xFFu; d.gx = (startGoal >> 16) & 0xFFu; d.gy = startGoal >> 24;
+  d.heur_off = heurOff;
+  d.ctx_flags = flags & kTaNoGoal;
+  d.max_expansions = budget;
+  d.n_agents_pad = nAgentsPad; d.t_pad = tPad; d.path_off = 0;
+  d.n_ctx = 0; d.reserved = 0;
+}
 constexpr uint32_t kSippResident = 2u;
 constexpr uint32_t kSippCommit = 8u;                               // ctx_flags bit 3: on success the workgroup adds the path's stays to the table
 constexpr uint32_t kSippTierCommitFailed = 0x100u;                 // DevResult.tier flag: a stay did not fit (more than kSippCap intervals,

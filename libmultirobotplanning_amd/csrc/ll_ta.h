@@ -364,6 +364,10 @@ DEVI bool orderedWalkTaEps(Mem<TierHbm>& m, Mem<TierFocalPos>& mf, SState& s, fl
 
 // A real function (its own register allocation): the kernels that host it keep theirs.  The job is read where the kernel
 // staged it, the result goes to `out` (status, cost, fmin, n_states, expanded, nodes_created, tier).
+// IN_PLACE (ll_ta_eps_root.h): the focal table [t_pad][n_agents_pad] already lies in the slot's path area — where the
+// ordinary job copies its shipped one — and is taken as it is; nothing is copied, path_off is not looked at.  The ordinary
+// job is the IN_PLACE = false instance, unchanged.
+template <bool IN_PLACE>
 __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResult* out, uint8_t* arenaSlot, const uint32_t* maps,
                                                       const uint32_t* consHost, const uint16_t* pathsHost,
                                                       uint32_t scratchOff, uint32_t outStride, uint32_t arenaNodes,
@@ -397,6 +401,8 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
     if (pathBytes == 0) {
       c.paths = nullptr;
       c.nAgentsPad = 0;
+    } else if constexpr (IN_PLACE) {
+      c.paths = (const uint16_t*)pathsArena;  // (its writer made sure that it fits)
     } else if (pathBytes <= arenaPathsBytes) {
       const uint32_t* psrc = (const uint32_t*)(pathsHost + pathOff);
       uint32_t* dst = (uint32_t*)pathsArena;

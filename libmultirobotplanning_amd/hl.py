@@ -63,7 +63,7 @@ EXPORTS = ["mrp_hl_solver_prioritized_sipp", "mrp_hl_solver_preload", "mrp_hl_so
            "mrp_hl_preloaded_free", "mrp_hl_solve_batch", "mrp_hl_solver_create", "mrp_hl_solver_destroy", "mrp_hl_solver_solve",
            "mrp_hl_solver_ll_stats", "mrp_hl_solver_last_error", "mrp_hl_generate_instance", "mrp_hl_generate_instances", "mrp_hl_astar_grid2d",
            "mrp_hl_ct_create", "mrp_hl_ct_destroy", "mrp_hl_ct_n_requests", "mrp_hl_ct_request", "mrp_hl_ct_deliver",
-           "mrp_hl_ct_done", "mrp_hl_ct_solution", "mrp_hl_solve_cbs_ta_batch"]
+           "mrp_hl_ct_done", "mrp_hl_ct_solution", "mrp_hl_solve_cbs_ta_batch", "mrp_hl_solve_ecbs_ta_batch"]
 
 _lib = None
 
@@ -161,6 +161,11 @@ def load_library(path: Optional[str] = None):
             lib.mrp_hl_solve_cbs_ta_batch.argtypes = [ctypes.c_int32, ctypes.POINTER(mrp_hl_ta_options), ctypes.c_int32,
                                                       ctypes.POINTER(mrp_hl_ta_instance), ctypes.POINTER(mrp_hl_ta_solution),
                                                       ctypes.POINTER(mrp_hl_batch_stats)]
+        if hasattr(lib, "mrp_hl_solve_ecbs_ta_batch"):
+            lib.mrp_hl_solve_ecbs_ta_batch.restype = ctypes.c_int
+            lib.mrp_hl_solve_ecbs_ta_batch.argtypes = [ctypes.c_int32, ctypes.c_float, ctypes.POINTER(mrp_hl_ta_options), ctypes.c_int32,
+                                                       ctypes.POINTER(mrp_hl_ta_instance), ctypes.POINTER(mrp_hl_ta_solution),
+                                                       ctypes.POINTER(mrp_hl_batch_stats)]
         if path is not None:
             return lib
         _lib = lib
@@ -566,15 +571,8 @@ class ConflictTree:
         return rec
 
 
-def solve_cbs_ta_batch(instances: Sequence[Dict], max_task_assignments: int = 2 ** 30, use_root_kernel: bool = False,
-                       max_hl_expansions: int = -1, max_ll_expansions: int = -1, device: int = 0, path_cap: int = 256,
-                       _lib_path: Optional[str] = None):
-    """mrp_hl_solve_cbs_ta_batch: CBS with task assignment (cbs_ta.hpp:87-214) for a batch of instances, each a dict with
-    dimx, dimy, obstacles [[x, y]], starts [[x, y]] and potential_goals (per agent a list of [x, y]).  Returns (results,
-    stats): per instance status, cost, makespan, hl_expanded, ll_expanded, num_task_assignments, n_roots, root_conflicts,
-    n_ll_searches, n_root_searches, digest, tasks (per agent [x, y] or None) and paths (per agent [[x, y, t]], t = the path's cost up to that
-    state, as the reference writes it)."""
-    lib = load_library(_lib_path)
+def _solve_ta_batch(call, name, instances, opt, device, path_cap):
+    """The marshalling the two task-assignment drivers share: `call(device, opt, n, instances, solutions, stats)`."""
     n = len(instances)
     cinst = (mrp_hl_ta_instance * max(n, 1))()
     csol = (mrp_hl_ta_solution * max(n, 1))()
@@ -596,11 +594,10 @@ def solve_cbs_ta_batch(instances: Sequence[Dict], max_task_assignments: int = 2 
         csol[k].task_xy, csol[k].path_len = tasks.ctypes.data_as(I32P), plen.ctypes.data_as(I32P)
         csol[k].paths_xyt, csol[k].path_cap = paths.ctypes.data_as(I32P), path_cap
         keep.append((ob, st, first, gl, tasks, plen, paths))
-    opt = mrp_hl_ta_options(max_task_assignments, 1 if use_root_kernel else 0, max_hl_expansions, max_ll_expansions)
     stats = mrp_hl_batch_stats()
-    rc = lib.mrp_hl_solve_cbs_ta_batch(device, ctypes.byref(opt), n, cinst, csol, ctypes.byref(stats))
+    rc = call(device, ctypes.byref(opt), n, cinst, csol, ctypes.byref(stats))
     if rc != 0:
-        raise RuntimeError(f"mrp_hl_solve_cbs_ta_batch failed rc={rc}")
+        raise RuntimeError(f"{name} failed rc={rc}")
     out = []
     for k in range(n):
         s, (_, st, _, _, tasks, plen, paths) = csol[k], keep[k]
@@ -612,3 +609,33 @@ def solve_cbs_ta_batch(instances: Sequence[Dict], max_task_assignments: int = 2 
                         tasks=[None if tasks[a][0] < 0 else tasks[a].tolist() for a in range(na)] if solved else None,
                         paths=[paths[a, :min(int(plen[a]), path_cap)].tolist() for a in range(na)] if solved else None))
     return out, {f: getattr(stats, f) for f, _ in mrp_hl_batch_stats._fields_}
+
+
+def solve_cbs_ta_batch(instances: Sequence[Dict], max_task_assignments: int = 2 ** 30, use_root_kernel: bool = False,
+                       max_hl_expansions: int = -1, max_ll_expansions: int = -1, device: int = 0, path_cap: int = 256,
+                       _lib_path: Optional[str] = None):
+    """mrp_hl_solve_cbs_ta_batch: CBS with task assignment (cbs_ta.hpp:87-214) for a batch of instances, each a dict with
+    dimx, dimy, obstacles [[x, y]], starts [[x, y]] and potential_goals (per agent a list of [x, y]).  Returns (results,
+    stats): per instance status, cost, makespan, hl_expanded, ll_expanded, num_task_assignments, n_roots, root_conflicts,
+    n_ll_searches, n_root_searches, digest, tasks (per agent [x, y] or None) and paths (per agent [[x, y, t]], t = the path's cost up to that
+    state, as the reference writes it)."""
+    lib = load_library(_lib_path)
+    opt = mrp_hl_ta_options(max_task_assignments, 1 if use_root_kernel else 0, max_hl_expansions, max_ll_expansions)
+    return _solve_ta_batch(lib.mrp_hl_solve_cbs_ta_batch, "mrp_hl_solve_cbs_ta_batch", instances, opt, device, path_cap)
+
+
+def solve_ecbs_ta_batch(instances: Sequence[Dict], w: float, max_task_assignments: int = 2 ** 30, use_root_kernel: bool = False,
+                        max_hl_expansions: int = -1, max_ll_expansions: int = -1, device: int = 0, path_cap: int = 256,
+                        _lib_path: Optional[str] = None):
+    """mrp_hl_solve_ecbs_ta_batch: ECBS with task assignment (ecbs_ta.hpp:94-352, low level AStarEpsilon under the same
+    weight w >= 1) for a batch of instances; instances and results as solve_cbs_ta_batch.  use_root_kernel: roots through
+    mrp_ll_ta_eps_root_batch (one workgroup each) or, False (the default: measured faster for thousands of instances), as n
+    dependent low-level jobs; same results."""
+    lib = load_library(_lib_path)
+    if not hasattr(lib, "mrp_hl_solve_ecbs_ta_batch"):
+        raise RuntimeError("this build of the drivers has no mrp_hl_solve_ecbs_ta_batch")
+    opt = mrp_hl_ta_options(max_task_assignments, 1 if use_root_kernel else 0, max_hl_expansions, max_ll_expansions)
+
+    def call(device, *rest):
+        return lib.mrp_hl_solve_ecbs_ta_batch(device, ctypes.c_float(w), *rest)
+    return _solve_ta_batch(call, "mrp_hl_solve_ecbs_ta_batch", instances, opt, device, path_cap)

@@ -107,7 +107,7 @@ EXPORTS = ["mrp_ll_create", "mrp_ll_destroy", "mrp_ll_last_error", "mrp_ll_uploa
            "mrp_ll_compute_heuristics", "mrp_ll_read_heuristic", "mrp_ll_heuristic_lookup", "mrp_ll_submit_scan",
            "mrp_ll_constraint_store_reserve", "mrp_ll_submit_sets", "mrp_ll_session_front_tables",
            "mrp_ll_submit_node", "mrp_ll_assign_batch", "mrp_ll_assign_series_create", "mrp_ll_assign_series_next",
-           "mrp_ll_assign_series_destroy", "mrp_ll_ta_root_batch"]
+           "mrp_ll_assign_series_destroy", "mrp_ll_ta_root_batch", "mrp_ll_ta_eps_root_batch"]
 
 _lib = None
 
@@ -207,6 +207,9 @@ def load_library(path: Optional[str] = None):
     lib.mrp_ll_assign_series_next.restype = ctypes.c_int
     lib.mrp_ll_assign_series_next.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p),
                                               ctypes.POINTER(mrp_ll_assign_result)]
+    lib.mrp_ll_ta_eps_root_batch.restype = ctypes.c_int
+    lib.mrp_ll_ta_eps_root_batch.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_int32, ctypes.POINTER(mrp_ll_ta_root),
+                                             ctypes.POINTER(mrp_ll_conflict), I32P]
     lib.mrp_ll_ta_root_batch.restype = ctypes.c_int
     lib.mrp_ll_ta_root_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(mrp_ll_ta_root), I32P,
                                          ctypes.POINTER(mrp_ll_conflict)]
@@ -549,6 +552,22 @@ class LowLevelEngine:
         if raw_rc and rc != 0:
             return rc
         self._check(rc, "mrp_ll_ta_root_batch")
+        names = [k for k, _ in mrp_ll_conflict._fields_]
+        return [TaRootResult(planned=int(planned[i]), results=self._results(na, cap, cres, states, actions, costs),
+                             conflict={k: getattr(conf[i], k) for k in names})
+                for i, (na, cres, states, actions, costs) in enumerate(per_root)]
+
+    def ta_eps_root_batch(self, roots: Sequence[TaRoot], w: float, states_cap: Optional[int] = None, raw_rc: bool = False):
+        """mrp_ll_ta_eps_root_batch: the roots of ECBS-TA conflict trees under weight w, one workgroup each, in one launch:
+        agent a's MRP_LL_ASTAR_EPS_TA search sees the paths of the agents before it.  Returns one TaRootResult per root
+        (conflict["count"] is the node's focalHeuristic); with raw_rc the call's return code instead of raising."""
+        n = len(roots)
+        cap = states_cap or self.max_horizon
+        croots, planned, conf, per_root, keep = self._marshal_ta_roots(roots, cap)
+        rc = self._lib.mrp_ll_ta_eps_root_batch(self._h, w, n, croots, conf, planned.ctypes.data_as(I32P))
+        if raw_rc and rc != 0:
+            return rc
+        self._check(rc, "mrp_ll_ta_eps_root_batch")
         names = [k for k, _ in mrp_ll_conflict._fields_]
         return [TaRootResult(planned=int(planned[i]), results=self._results(na, cap, cres, states, actions, costs),
                              conflict={k: getattr(conf[i], k) for k in names})

@@ -1,0 +1,88 @@
+"""ECBS-TA on the device: instances per second of the batched driver (mrp_hl_solve_ecbs_ta_batch, the time of its rounds:
+tables and the series' optima are set up before) with roots through mrp_ll_ta_eps_root_batch (use_root_kernel 1) and as
+dependent MRP_LL_ASTAR_EPS_TA jobs (0), the answers compared.  Workload: generated 32 x 32 instances with 204 obstacles, ten
+agents, twenty potential goals shared by all agents of an instance, w = 1.3.  The two forms alternate, --repeats runs each
+after one warm-up run each; reported: the median, every run, and the spread (max - min) / median.
+usage: python scripts/ecbs_ta_tree_throughput.py [--instances 2048] [--w 1.3]  (prints one JSON line)"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from libmultirobotplanning_amd import hl  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--instances", type=int, default=2048)
+ap.add_argument("--agents", type=int, default=10)
+ap.add_argument("--goals", type=int, default=20)
+ap.add_argument("--maps", type=int, default=16)
+ap.add_argument("--repeats", type=int, default=5)
+ap.add_argument("--w", type=float, default=1.3)
+args = ap.parse_args()
+CAP = 128  # states per result buffer
+
+
+def component(dim, obst):
+    """The largest connected set of free cells."""
+    free = {(x, y) for y in range(dim) for x in range(dim)} - obst
+    best = []
+    while free:
+        todo = [free.pop()]
+        comp = list(todo)
+        while todo:
+            x, y = todo.pop()
+            for c in ((x + 1, y), (x - 1, y), (x, y + 1), (x, y - 1)):
+                if c in free:
+                    free.remove(c)
+                    todo.append(c)
+                    comp.append(c)
+        best = comp if len(comp) > len(best) else best
+    return sorted(best)
+
+
+def median(v):
+    return sorted(v)[len(v) // 2]
+
+
+rng = np.random.default_rng(3)
+worlds = []
+for _ in range(args.maps):
+    cells = rng.permutation(32 * 32)[:204]
+    obst = {(int(c) % 32, int(c) // 32) for c in cells}
+    worlds.append((component(32, obst), [list(o) for o in sorted(obst)]))
+insts = []
+for k in range(args.instances):
+    comp, obst = worlds[k % args.maps]
+    pick = rng.permutation(len(comp))[:args.agents + args.goals]
+    goals = [list(comp[i]) for i in pick[args.agents:]]
+    insts.append(dict(dimx=32, dimy=32, obstacles=obst, starts=[list(comp[i]) for i in pick[:args.agents]],
+                      potential_goals=[goals] * args.agents))
+n = len(insts)
+
+walls, answers, last = {0: [], 1: []}, {}, {}
+for rep in range(args.repeats + 1):  # the first run of each form is the warm-up
+    for use in (1, 0):
+        got, st = hl.solve_ecbs_ta_batch(insts, args.w, use_root_kernel=bool(use), path_cap=CAP)
+        walls[use].append(st["wall_seconds"])
+        last[use] = (got, st)
+        answers[use] = [(g["status"], g["cost"], g["hl_expanded"], g["ll_expanded"], g["num_task_assignments"], g["digest"]) for g in got]
+assert answers[0] == answers[1]
+result = dict(instances=n, agents=args.agents, potential_goals=args.goals, w=args.w, repeats=args.repeats)
+for use, name in ((1, "root_kernel"), (0, "root_jobs")):
+    v = walls[use][1:]
+    m = median(v)
+    result[name] = dict(rounds_wall_s=round(m, 5), instances_per_s=round(n / m), walls=[round(x, 5) for x in v],
+                        spread=round((max(v) - min(v)) / m, 4), rounds=last[use][1]["rounds"])
+got, st = last[1]
+searches = sum(g["n_ll_searches"] for g in got)
+result["breakdown"] = dict(solved=sum(1 for g in got if g["status"] == hl.SOLVED), searches=searches,
+                           root_search_share=round(sum(g["n_root_searches"] for g in got) / max(searches, 1), 4),
+                           solved_at_first_root_share=round(st["root_solved"] / n, 4), hl_expanded=sum(g["hl_expanded"] for g in got),
+                           task_assignments=sum(g["num_task_assignments"] for g in got))
+result["speedup_root_kernel_over_jobs"] = round(result["root_jobs"]["rounds_wall_s"] / result["root_kernel"]["rounds_wall_s"], 3)
+print(json.dumps(result))
