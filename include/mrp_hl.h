@@ -273,6 +273,11 @@ int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options* opt, int3
  * itself; the results are the same.  One expansion can take several rounds either way (children, then assignment and root).
  * A NULL options pointer means use_root_kernel = 0, as do the Python and CLI front-ends: roots as jobs measured faster at
  * the reference shape with thousands of instances, the root call at a few hundred.
+ * Environment, read once per call: MRP_HL_TA_DEVICE_PATHS=1 (off by default; same results, same stats but the times) keeps
+ * every path in the engine's device-resident path store — the root call becomes mrp_ll_ta_eps_root_batch_stored, every job
+ * carries MRP_LL_JOB_STORE_RESULT while a slot is free — and a job whose node has every other agent's path there names its
+ * context by slot (mrp_ll_job.path_ids) instead of shipping it.  MRP_HL_TA_PATH_SLOTS=N: slots of that store (unset: four per
+ * agent of the batch, between 256 and 65536; not tuned).
  * w >= 1 (else MRP_LL_E_INVALID).  root_conflicts counts the expanded nodes with a conflict that carry the root flag (a
  * child is a copy of its parent, flag included). */
 int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_ta_options* opt, int32_t n_instances,

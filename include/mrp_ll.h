@@ -104,8 +104,15 @@ extern "C" {
                            /* look the other agents up at the successor's TIME (g != time here).  A state found again with a  */
                            /* smaller g is re-keyed in the open list and, if it already sits in the focal list, keeps its      */
                            /* place there with the new key (a_star_epsilon.hpp:249-269), exactly as the reference's heaps do.   */
-                           /* Rejected (MRP_LL_BAD_JOB): initial_cost != 0, path_ids, MRP_LL_JOB_ROOT_CHAIN, _HEAVY,           */
-                           /* _STORE_RESULT.  Runs in batches and in mixed sessions (mrp_ll_session_begin); the one-algorithm  */
+                           /* The device-resident path store serves it as it serves MRP_LL_ASTAR_EPS: with                     */
+                           /* MRP_LL_JOB_STORE_RESULT the result path also stays in slot result_path_id, and path_ids names    */
+                           /* the context's paths by their slots instead of shipping them (path_xy may be NULL) — under the    */
+                           /* same rules: a store is reserved, the id of every other agent with path_len > 0 lies inside it,  */
+                           /* the longest path_len is at most max_horizon, and the table [longest path_len][n_agents rounded   */
+                           /* up to 16] of 2-byte cells fits the arena slot's path area (the workgroup builds it there).       */
+                           /* Rejected (MRP_LL_BAD_JOB): initial_cost != 0, MRP_LL_JOB_ROOT_CHAIN, _HEAVY, _SCAN_CONFLICTS,    */
+                           /* _CONSTRAINT_SET; path_ids or _STORE_RESULT with no store reserved.                              */
+                           /* Runs in batches and in mixed sessions (mrp_ll_session_begin); the one-algorithm                  */
                            /* sessions and mrp_ll_session_occupancy answer MRP_LL_E_INVALID for it.                          */
                            /* One tier, the arena (result.tier == 1): any map the context accepts, any number of              */
                            /* constraints, any number of context agents.  Limits, with B = 40 * arena_nodes + 48 bytes:       */
@@ -188,10 +195,14 @@ typedef struct mrp_ll_job {
   const struct mrp_ll_sipp_table* sipp_table;
   /* Device-resident path store (mrp_ll_path_store_reserve).  A conflict-tree child differs from its
    * parent in ONE path (ecbs.hpp:253-263 copies all N), and every path was produced by a search of this engine: with
-   * result_path_id >= 0 the kernel ALSO leaves the result path in that store slot, and a later MRP_LL_ASTAR_EPS job names
-   * the CT node's paths by their slots — path_ids[n_agents], -1 = no path / the searching agent itself — instead of
-   * shipping them (path_xy may then be NULL; path_len is still required).  Slot ids are managed by the caller: a slot
-   * may be reused once no unfinished job names it.
+   * result_path_id >= 0 the kernel ALSO leaves the result path in that store slot, and a later MRP_LL_ASTAR_EPS or
+   * MRP_LL_ASTAR_EPS_TA job names the CT node's paths by their slots — path_ids[n_agents], -1 = no path / the searching
+   * agent itself — instead of shipping them (path_xy may then be NULL; path_len is still required).  Slot ids are managed
+   * by the caller: a slot may be reused once no unfinished job names it.
+   * A slot is a length word and max_horizon states (rounded up to 8 halfwords), and the packer cannot know a result's
+   * length beforehand: the device stores NOTHING when a path does not fit its slot, and the slot keeps its previous
+   * content, which a by-id reader would then take for the path.  A caller that stores results keeps its paths below
+   * max_horizon and treats a returned n_states >= max_horizon as "not stored".
    * result_path_id is honoured only when `flags` has MRP_LL_JOB_STORE_RESULT: a zero-initialised job (`mrp_ll_job j{}`,
    * memset) stores nothing and touches no slot. */
   const int32_t* path_ids;
@@ -696,6 +707,18 @@ int mrp_ll_ta_root_batch(mrp_ll_ctx* ctx, int32_t n_roots, const mrp_ll_ta_root*
  * MRP_LL_E_INVALID also for w < 1 or NaN. */
 int mrp_ll_ta_eps_root_batch(mrp_ll_ctx* ctx, float w, int32_t n_roots, const mrp_ll_ta_root* roots,
                              mrp_ll_conflict* conflicts /* [n_roots] */, int32_t* planned /* [n_roots] */);
+
+/* The same call for a caller that keeps its paths in the device-resident path store (mrp_ll_path_store_reserve):
+ * result_path_ids[r][a] >= 0 is the slot that ALSO receives the path of agent a of root r, exactly as
+ * MRP_LL_JOB_STORE_RESULT does for an ordinary job, so that the children of the root can name it (mrp_ll_job.path_ids); -1 =
+ * not stored.  result_path_ids == NULL, or result_path_ids[r] == NULL, stores nothing: mrp_ll_ta_eps_root_batch is this call
+ * with NULL.  Results, planned and conflicts are bit for bit what the call without ids returns.  Only the slots of agents that
+ * come back MRP_LL_OK are written; the slot of any other agent (not planned, no path) keeps its content.  The agents the call
+ * completes on the host (above) store their paths too.  A root with an id below -1 or outside the reserved store is refused
+ * like any other invalid root: MRP_LL_BAD_JOB in each of its results, nothing run, no slot touched. */
+int mrp_ll_ta_eps_root_batch_stored(mrp_ll_ctx* ctx, float w, int32_t n_roots, const mrp_ll_ta_root* roots,
+                                    mrp_ll_conflict* conflicts /* [n_roots] */, int32_t* planned /* [n_roots] */,
+                                    const int32_t* const* result_path_ids /* [n_roots] -> [n_agents]; NULL = none */);
 
 int mrp_ll_get_stats(const mrp_ll_ctx* ctx, mrp_ll_stats* out);
 int mrp_ll_reset_stats(mrp_ll_ctx* ctx);

@@ -22,6 +22,7 @@ struct Path {
   std::vector<int32_t> xy;  // x, y at time 0, 1, ...
   std::vector<int32_t> g;   // the path's cost up to that state (what the reference writes as t, cbs_ta.cpp:606-610)
   int32_t cost = 0;
+  int32_t slot = -1;        // the engine's path-store slot that holds these cells too (ta_batch_setup.hpp PathSlots); -1: none
   int len() const { return static_cast<int>(g.size()); }
 };
 typedef std::shared_ptr<const Path> PathP;

@@ -7,6 +7,9 @@
 //   3. mrp_ll_search_batch         MRP_LL_ASTAR_EPS_TA jobs: for every tree with an expanded node, its two child searches with
 //                                  the node's paths as the context
 // and then lets every tree run up to its next request.  The trees scan and count their children's conflicts themselves.
+// MRP_HL_TA_DEVICE_PATHS=1 (ta_batch_setup.hpp TaKnobs; off by default, same results): the engine's path store is reserved,
+// every search is told to leave its path in a slot of it (a root through mrp_ll_ta_eps_root_batch_stored), and a job whose
+// node has every other agent's path there goes out with path_ids instead of a shipped table.
 // A translation unit of its own, like csrc/hl/mrp_hl_ta.cpp.
 #include <chrono>
 #include <cstring>
@@ -17,6 +20,11 @@
 #include "ecbs_ta_tree.hpp"
 #include "ta_batch_setup.hpp"
 
+// The engine's entry point for roots that leave their paths in the store.  A weak reference: an engine library without it
+// still loads, and MRP_HL_TA_DEVICE_PATHS then sends its roots through the plain call, their paths unstored.
+extern "C" int mrp_ll_ta_eps_root_batch_stored(mrp_ll_ctx*, float, int32_t, const mrp_ll_ta_root*, mrp_ll_conflict*, int32_t*,
+                                               const int32_t* const*) __attribute__((weak));
+
 namespace {
 
 using mrp_hl::ecbs_ta::Tree;
@@ -25,6 +33,8 @@ using mrp_hl::ta::Engine;
 using mrp_hl::ta::kPathCap;
 using mrp_hl::ta::PathP;
 using mrp_hl::ta::pathOf;
+using mrp_hl::ta::PathSlots;
+using mrp_hl::ta::PathSlotsP;
 using mrp_hl::ta::ResultPool;
 
 // What a search's status means to its tree: 0 a path, 1 no path (the reference's `success == false`), else the tree ends.
@@ -37,21 +47,37 @@ int verdict(Tree& t, const mrp_ll_result& r) {
 
 // The focal context of one job: the solution vector the search sees (its own entry is ignored, an empty path is skipped).
 struct Context {
-  std::vector<int32_t> len;
+  std::vector<int32_t> len, ids;  // ids: the paths' slots in the path store, -1: not there (or no path)
   std::vector<const int32_t*> xy;
   void of(const std::vector<PathP>& sol) {
     static const int32_t none[2] = {0, 0};
     len.assign(sol.size(), 0);
+    ids.assign(sol.size(), -1);
     xy.assign(sol.size(), none);
     for (size_t a = 0; a < sol.size(); ++a)
       if (sol[a]) {
         len[a] = sol[a]->len();
+        ids[a] = sol[a]->slot;
         xy[a] = sol[a]->xy.data();
       }
   }
+  // The context of `agent`'s search can go by slot: some other agent has a path, and each of those paths is in the store.
+  // (The table the workgroup then builds always fits: 64 agents x kPathCap 512 states x 2 bytes = 64 KiB of the default
+  // engine's 128 KiB path area.)
+  bool byId(int agent) const {
+    bool any = false;
+    for (size_t a = 0; a < len.size(); ++a) {
+      if (static_cast<int>(a) == agent || len[a] <= 0) continue;
+      if (ids[a] < 0) return false;
+      any = true;
+    }
+    return any;
+  }
 };
 
-void epsJob(mrp_ll_job& j, const Tree& t, int agent, int32_t task, const Cons* cons, const Context& ctx, int64_t budget) {
+// slot >= 0: the search also leaves its path there; byId: the context goes by slot, nothing is shipped.
+void epsJob(mrp_ll_job& j, const Tree& t, int agent, int32_t task, const Cons* cons, const Context& ctx, int64_t budget,
+            int32_t slot = -1, bool byId = false) {
   std::memset(&j, 0, sizeof(j));
   j.map_id = t.mapId;
   j.algo = MRP_LL_ASTAR_EPS_TA;
@@ -64,12 +90,20 @@ void epsJob(mrp_ll_job& j, const Tree& t, int agent, int32_t task, const Cons* c
   j.n_agents = static_cast<int32_t>(ctx.len.size());
   j.path_len = ctx.len.data();
   j.path_xy = ctx.xy.data();
+  if (byId) {
+    j.path_ids = ctx.ids.data();
+    j.path_xy = nullptr;
+  }
+  if (slot >= 0) {
+    j.result_path_id = slot;
+    j.flags |= MRP_LL_JOB_STORE_RESULT;
+  }
   if (task >= 0) {
     j.goal_x = t.taskXY[2 * task];
     j.goal_y = t.taskXY[2 * task + 1];
     j.heuristic_id = t.taskHeur[task];
   } else {
-    j.flags = MRP_LL_JOB_NO_GOAL;
+    j.flags |= MRP_LL_JOB_NO_GOAL;
     j.heuristic_id = -1;
   }
   if (cons) {
@@ -107,6 +141,18 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
   rc = mrp_hl::ta::setUpBatch(eng, n, inst, trees);
   if (rc != MRP_LL_SUCCESS) return rc;
   for (int32_t k = 0; k < n; ++k) trees[k]->w = w;
+  // ---- MRP_HL_TA_DEVICE_PATHS: the store and its free list (null: the knob is off, and nothing below differs from before)
+  const mrp_hl::ta::TaKnobs knobs = mrp_hl::ta::TaKnobs::read();
+  PathSlotsP slots;
+  if (knobs.devicePaths) {
+    int64_t agents = 0;
+    for (int32_t k = 0; k < n; ++k) agents += trees[k]->running() ? trees[k]->nAgents : 0;
+    const int32_t nSlots = knobs.slotsFor(agents);
+    rc = mrp_ll_path_store_reserve(eng.ctx, nSlots);
+    if (rc != MRP_LL_SUCCESS) return rc;
+    slots = std::make_shared<PathSlots>();
+    slots->reset(nSlots);
+  }
 
   // ---- the rounds
   const auto t0 = std::chrono::steady_clock::now();
@@ -166,6 +212,21 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
     pool.reserve(nResults);
     std::vector<mrp_ll_result> res(nResults + 1);
     for (size_t q = 0; q < nResults; ++q) pool.attach(res[q], q);
+    // the slot result q's search was told to leave its path in (-1: none); whoever turns the result into a path takes it
+    std::vector<int32_t> outSlot(nResults + 1, -1);
+    auto takeSlot = [&](size_t q) {
+      if (slots) outSlot[q] = slots->take();
+      return outSlot[q];
+    };
+    auto pathFrom = [&](size_t q) {
+      int32_t s = outSlot[q];
+      outSlot[q] = -1;
+      if (s >= 0 && res[q].n_states >= kPathCap) {  // as long as a slot: the device did not store it (mrp_ll.h)
+        slots->give(s);
+        s = -1;
+      }
+      return pathOf(res[q], s, slots);
+    };
     std::vector<Context> ctx(rootOf.size() + childOf.size());
     std::vector<mrp_ll_job> jobs(nJobs);
     std::vector<int32_t> planned(rootOf.size() + 1, 0);
@@ -193,7 +254,17 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
         r.max_expansions = budgetOf(t);
         r.results = res.data() + rootFirst[q];
       }
-      if (!rootOf.empty()) {
+      if (!rootOf.empty() && slots && &mrp_ll_ta_eps_root_batch_stored != nullptr) {
+        std::vector<std::vector<int32_t>> ids(rootOf.size());
+        std::vector<const int32_t*> idsOf(rootOf.size());
+        for (size_t q = 0; q < rootOf.size(); ++q) {
+          for (size_t a = 0; a < rootFirst[q + 1] - rootFirst[q]; ++a) ids[q].push_back(takeSlot(rootFirst[q] + a));
+          idsOf[q] = ids[q].data();
+        }
+        rc = mrp_ll_ta_eps_root_batch_stored(eng.ctx, w, static_cast<int32_t>(rootOf.size()), roots.data(), rootScan.data(),
+                                             planned.data(), idsOf.data());
+        if (rc != MRP_LL_SUCCESS) return rc;
+      } else if (!rootOf.empty()) {
         rc = mrp_ll_ta_eps_root_batch(eng.ctx, w, static_cast<int32_t>(rootOf.size()), roots.data(), rootScan.data(), planned.data());
         if (rc != MRP_LL_SUCCESS) return rc;
       }
@@ -201,7 +272,8 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
       for (size_t q = 0; q < rootOf.size(); ++q) {
         const Tree& t = *trees[rootOf[q]];
         ctx[q].of(t.rootPaths);
-        epsJob(jobs[q], t, t.rootAgent, t.rootTasks[t.rootAgent], nullptr, ctx[q], budgetOf(t));
+        epsJob(jobs[q], t, t.rootAgent, t.rootTasks[t.rootAgent], nullptr, ctx[q], budgetOf(t), takeSlot(rootFirst[q]),
+               slots && ctx[q].byId(t.rootAgent));
       }
     }
     // 3. the child searches (and, without the root call, the roots' next searches in front of them)
@@ -211,7 +283,7 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
       c.of(t.nodes[t.popped].sol);
       for (int s = 0; s < 2; ++s)
         epsJob(jobs[nRootJobs + 2 * q + s], t, t.childAgent[s], t.nodes[t.popped].taskOf[t.childAgent[s]], t.childCons[s].get(), c,
-               budgetOf(t));
+               budgetOf(t), takeSlot(nRootResults + 2 * q + s), slots && c.byId(t.childAgent[s]));
     }
     if (!jobs.empty()) {
       rc = mrp_ll_search_batch(eng.ctx, static_cast<int32_t>(jobs.size()), jobs.data(), res.data() + (nRootResults - nRootJobs));
@@ -225,7 +297,7 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
         t.nRootSearches += 1;
         t.llExpanded += r.expanded;  // (the expansions of a failed root count)
         const int v = verdict(t, r);
-        if (v != 2) t.gotRootSearch(v == 0 ? pathOf(r) : nullptr, r.fmin);
+        if (v != 2) t.gotRootSearch(v == 0 ? pathFrom(rootFirst[q]) : nullptr, r.fmin);
         continue;
       }
       std::vector<PathP> paths(static_cast<size_t>(t.nAgents));
@@ -240,7 +312,7 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
         t.llExpanded += r.expanded;
         const int v = verdict(t, r);
         if (v == 0) {
-          paths[a] = pathOf(r);
+          paths[a] = pathFrom(rootFirst[q] + a);
           fmin[a] = r.fmin;
         } else {
           all = false;  // the root ends behind this agent (ecbs_ta.hpp:323-326)
@@ -261,12 +333,14 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
         t.nSearches += 1;
         t.llExpanded += r.expanded;
         if (verdict(t, r) == 0) {
-          path[s] = pathOf(r);
+          path[s] = pathFrom(nRootResults + 2 * q + s);
           fmin[s] = r.fmin;
         }
       }
       if (t.running()) t.gotChildren(path, fmin);
     }
+    for (int32_t s : outSlot)  // a search that left no path, or whose tree had ended: its slot is free again
+      if (s >= 0) slots->give(s);
     for (int32_t k : live) {
       Tree& t = *trees[k];
       if (t.running() && opt.max_ll_expansions >= 0 && t.llExpanded > opt.max_ll_expansions) t.end(MRP_HL_CAP);

@@ -2,6 +2,8 @@
 // trees: the engine context with its assignment series, the caller-side result buffers of a round, a result turned into a
 // tree's path, and the set-up of a batch — maps, tasks, one launch for all shortest-path tables, one for all optima.
 #pragma once
+#include <algorithm>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -29,8 +31,68 @@ struct ResultPool {
   }
 };
 
-inline PathP pathOf(const mrp_ll_result& r) {
-  auto p = std::make_shared<Path>();
+// The MRP_HL_TA_* environment knobs of mrp_hl_solve_ecbs_ta_batch, read once per call (as solve_knobs.hpp's for the CBS / ECBS
+// solver).
+struct TaKnobs {
+  // MRP_HL_TA_DEVICE_PATHS=1: every path stays in the engine's device-resident path store, in the slot its search was told
+  // to leave it in, and a search whose conflict-tree node has every other agent's path there names them by slot instead of
+  // shipping the focal table.  Same results; off by default.
+  bool devicePaths = false;
+  // MRP_HL_TA_PATH_SLOTS=N: slots of that store.  Unset (-1): four per agent over the batch's instances, between 256 and
+  // 65536 (about 1 KB of device memory a slot) — room for every root and a few levels of children; not tuned.  (The trees
+  // keep every node they made, so a tree's slots come back when a search leaves no path or the tree is destroyed.)  A tree
+  // that finds the free list empty ships its contexts as without the knob.
+  int32_t pathSlots = -1;
+  static TaKnobs read() {
+    TaKnobs k;
+    if (const char* e = std::getenv("MRP_HL_TA_DEVICE_PATHS")) k.devicePaths = std::atoi(e) != 0;
+    if (const char* e = std::getenv("MRP_HL_TA_PATH_SLOTS")) k.pathSlots = std::max(1, std::atoi(e));
+    return k;
+  }
+  int32_t slotsFor(int64_t agentsOfTheBatch) const {
+    if (pathSlots > 0) return pathSlots;
+    return static_cast<int32_t>(std::min<int64_t>(65536, std::max<int64_t>(256, 4 * agentsOfTheBatch)));
+  }
+};
+
+// The free list of the path store's slots.  A slot lives and dies with its path: it is taken when the search that will
+// produce the path is issued, belongs to the Path made of that search's result (pathOf below: the deleter gives it back
+// when the last PathP drops), and comes straight back when the search leaves no path.
+// Why a freed slot can be handed out at once: the driver's engine calls are synchronous — a call returns when every search
+// of the round has ended — and paths are dropped only between calls, while the trees consume a round's results.  So no
+// job in flight names a slot on this list; a slot freed in round r is at the earliest written by a search of round r + 1.
+// Inside one batch a slot is written by the one search it was handed to and read only by jobs whose node holds its Path:
+// never both, since a slot on the list belongs to no Path.
+struct PathSlots {
+  std::vector<int32_t> free;
+  void reset(int32_t n) {
+    free.resize(static_cast<size_t>(n));
+    for (int32_t i = 0; i < n; ++i) free[i] = n - 1 - i;
+  }
+  int32_t take() {
+    if (free.empty()) return -1;
+    const int32_t s = free.back();
+    free.pop_back();
+    return s;
+  }
+  void give(int32_t s) {
+    if (s >= 0) free.push_back(s);
+  }
+};
+typedef std::shared_ptr<PathSlots> PathSlotsP;
+
+// slot >= 0: the search also left the path in that slot of `slots`' store.
+inline PathP pathOf(const mrp_ll_result& r, int32_t slot = -1, const PathSlotsP& slots = PathSlotsP()) {
+  std::shared_ptr<Path> p;
+  if (slot >= 0 && slots) {
+    p = std::shared_ptr<Path>(new Path(), [slots](Path* q) {
+      slots->give(q->slot);
+      delete q;
+    });
+    p->slot = slot;
+  } else {
+    p = std::make_shared<Path>();
+  }
   p->cost = r.cost;
   int32_t g = 0;
   for (int k = 0; k < r.n_states; ++k) {

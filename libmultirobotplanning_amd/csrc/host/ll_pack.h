@@ -424,9 +424,9 @@ static inline bool packJob(const PackEnv& env, const mrp_ll_job& j, const PackAr
     return false;
   if (j.algo == MRP_LL_ASTAR_EPS && j.initial_cost != 0) return false;  // AStarEpsilon::search has no initialCost
   const bool epsTa = j.algo == MRP_LL_ASTAR_EPS_TA;
-  // MRP_LL_ASTAR_EPS_TA serves ecbs_ta.hpp's calls only: no initial cost, no root chain, no tier hint, no path store
-  if (epsTa && (j.initial_cost != 0 || (j.flags & (MRP_LL_JOB_ROOT_CHAIN | MRP_LL_JOB_HEAVY | MRP_LL_JOB_STORE_RESULT)) || j.path_ids))
-    return false;
+  // MRP_LL_ASTAR_EPS_TA serves ecbs_ta.hpp's calls only: no initial cost, no root chain, no tier hint (and, below, no
+  // constraint set and no conflict scan: both ask for MRP_LL_ASTAR / MRP_LL_ASTAR_EPS); the path store as MRP_LL_ASTAR_EPS has it
+  if (epsTa && (j.initial_cost != 0 || (j.flags & (MRP_LL_JOB_ROOT_CHAIN | MRP_LL_JOB_HEAVY)))) return false;
   if (j.initial_cost < 0 || j.initial_cost >= 0x40000000) return false;  // (bit 30 of the per-job word marks MRP_LL_ASTAR_TA, jobInitOf)
   // The agent's set by its slot in the constraint store (mrp_ll.h mrp_ll_submit_sets): the arrays are the additions.
   const bool bySet = (j.flags & MRP_LL_JOB_CONSTRAINT_SET) != 0;
@@ -586,8 +586,9 @@ static inline bool packJob(const PackEnv& env, const mrp_ll_job& j, const PackAr
                        ? static_cast<uint32_t>(j.result_path_id)
                        : kNoStoreSlot;
   if (storeResult && d.store_out_id == kNoStoreSlot) return false;  // no such slot (or no store reserved)
-  if (j.algo == MRP_LL_ASTAR_EPS && j.n_agents > 0 && j.path_ids) {
-    // f2: the CT node's paths by their path-store slots; the workgroup builds the table (ll_jobs.h runJob)
+  if ((j.algo == MRP_LL_ASTAR_EPS || epsTa) && j.n_agents > 0 && j.path_ids) {
+    // f2: the CT node's paths by their path-store slots; the workgroup builds the table (ll_jobs.h runJob, ll_ta.h
+    // runJobTaEps: path_off names the ids, heur_off the heuristic table)
     if (!j.path_len || !env.pathStoreSlots) return false;
     int tpad = 0;
     for (int a = 0; a < j.n_agents; ++a)
@@ -595,7 +596,7 @@ static inline bool packJob(const PackEnv& env, const mrp_ll_job& j, const PackAr
         if (j.path_ids[a] < 0 || static_cast<uint32_t>(j.path_ids[a]) >= env.pathStoreSlots) return false;
         tpad = std::max(tpad, j.path_len[a]);
       }
-    // The workgroup builds the table in LDS or in its arena slot's path area; a table that fits neither (a caller's
+    // The workgroup builds the table in LDS or in its arena slot's path area (MRP_LL_ASTAR_EPS_TA: there only); a table that fits neither (a caller's
     // path_len beyond max_horizon, a very wide solution) is refused here rather than written past the slot.
     if (tpad > horizon ||
         static_cast<uint64_t>(tpad) * ((static_cast<uint32_t>(j.n_agents) + 15u) & ~15u) * 2u > env.arenaPathsBytes)

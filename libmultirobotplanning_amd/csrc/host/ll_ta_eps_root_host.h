@@ -3,6 +3,8 @@
 // ticket's staging buffers and stream, the launch parameters of an ordinary batch, unpackResult on the way back.  A root
 // whose table outgrew its arena slot's path area is finished here before the call returns: the agents the kernel did not
 // reach as ordinary MRP_LL_ASTAR_EPS_TA jobs with shipped contexts, one after the other, and the scan by mrp_ll_conflict_scan.
+// mrp_ll_ta_eps_root_batch_stored: the agents' paths also go to the path-store slots the caller names, from the kernel
+// (a run of slot words behind the agent words) and from the jobs run here (MRP_LL_JOB_STORE_RESULT) alike.
 #pragma once
 #include "ll_batch.h"
 #include "ll_ctx.h"
@@ -13,8 +15,10 @@
 namespace {
 
 // The agents planned[k] .. n - 1 of root R as ordinary jobs; paths: the planned agents' ([x, y] per state), extended here.
+// storeIds: nullptr, or the agents' path-store slots (-1: not stored): their jobs carry MRP_LL_JOB_STORE_RESULT.
 // Returns an engine error, or MRP_LL_SUCCESS with `all` = every agent has a path.
-int taEpsRootRest(mrp_ll_ctx* ctx, float w, const mrp_ll_ta_root& R, int32_t& planned, std::vector<std::vector<int32_t>>& paths, bool& all) {
+int taEpsRootRest(mrp_ll_ctx* ctx, float w, const mrp_ll_ta_root& R, const int32_t* storeIds, int32_t& planned,
+                  std::vector<std::vector<int32_t>>& paths, bool& all) {
   const int32_t cap = ctx->env.maxHorizon;
   std::vector<int32_t> st(static_cast<size_t>(cap) * 3), ac(cap), co(cap), len(R.n_agents, 0);
   std::vector<const int32_t*> xy(R.n_agents, nullptr);
@@ -40,12 +44,16 @@ int taEpsRootRest(mrp_ll_ctx* ctx, float w, const mrp_ll_ta_root& R, int32_t& pl
     j.path_xy = xy.data();
     j.max_expansions = budget;
     j.result_path_id = -1;
+    if (storeIds && storeIds[a] >= 0) {
+      j.result_path_id = storeIds[a];
+      j.flags |= MRP_LL_JOB_STORE_RESULT;
+    }
     j.heuristic_id = R.heuristic_ids[a];
     if (R.heuristic_ids[a] >= 0) {
       j.goal_x = R.goals_xy[2 * a];
       j.goal_y = R.goals_xy[2 * a + 1];
     } else {
-      j.flags = MRP_LL_JOB_NO_GOAL;
+      j.flags |= MRP_LL_JOB_NO_GOAL;
     }
     mrp_ll_result full;
     std::memset(&full, 0, sizeof(full));
@@ -78,7 +86,8 @@ int taEpsRootRest(mrp_ll_ctx* ctx, float w, const mrp_ll_ta_root& R, int32_t& pl
   return MRP_LL_SUCCESS;
 }
 
-int taEpsRootLaunch(mrp_ll_ctx* ctx, float w, int32_t n, const mrp_ll_ta_root* roots, int32_t* planned, mrp_ll_conflict* conflicts) {
+int taEpsRootLaunch(mrp_ll_ctx* ctx, float w, int32_t n, const mrp_ll_ta_root* roots, int32_t* planned, mrp_ll_conflict* conflicts,
+                    const int32_t* const* storeIds) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int rc = syncMaps(ctx);
   if (rc != MRP_LL_SUCCESS) return rc;
@@ -87,7 +96,7 @@ int taEpsRootLaunch(mrp_ll_ctx* ctx, float w, int32_t n, const mrp_ll_ta_root* r
   Ticket& t = ctx->tickets[0];  // idle: no session, no batch in flight
   auto packT0 = std::chrono::steady_clock::now();
   mrp::host::TaRootStaging st;
-  mrp::host::packTaEpsRoots(ctx->env, w, n, roots, 0, st);
+  mrp::host::packTaEpsRoots(ctx->env, w, n, roots, 0, st, storeIds);
   const uint32_t outStride = static_cast<uint32_t>(ctx->env.maxHorizon) + mrp::kScanOutHalfs;
   const uint32_t nDev = static_cast<uint32_t>(st.recs.size());
   std::vector<int32_t> needScan, needRest;
@@ -99,15 +108,16 @@ int taEpsRootLaunch(mrp_ll_ctx* ctx, float w, int32_t n, const mrp_ll_ta_root* r
   t.cons.clear();
   t.paths.clear();
   HIPCHK(ctx, t.jobs.resize(nDev));
-  HIPCHK(ctx, t.cons.resize(std::max<size_t>(st.words.size(), 16)));
+  HIPCHK(ctx, t.cons.resize(std::max<size_t>(st.words.size() + st.slotWords.size(), 16)));
   HIPCHK(ctx, t.paths.reserve(16));
   HIPCHK(ctx, t.results.resize(st.nResults));
   HIPCHK(ctx, t.outPaths.resize(static_cast<size_t>(st.nResults) * outStride));
   std::memcpy(t.jobs.host, st.recs.data(), nDev * sizeof(DevJob));
   std::memcpy(t.cons.host, st.words.data(), st.words.size() * 4);
+  if (!st.slotWords.empty()) std::memcpy(t.cons.host + st.words.size(), st.slotWords.data(), st.slotWords.size() * 4);
   mrp::host::blankTaRootAnswers(st, t.outPaths.host, outStride);
   ctx->stats.pack_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - packT0).count();
-  ctx->stats.staged_bytes += static_cast<int64_t>(nDev * sizeof(DevJob) + st.words.size() * 4);
+  ctx->stats.staged_bytes += static_cast<int64_t>(nDev * sizeof(DevJob) + (st.words.size() + st.slotWords.size()) * 4);
 
   mrp::LaunchParams P;
   std::memset(&P, 0, sizeof(P));
@@ -154,7 +164,7 @@ int taEpsRootLaunch(mrp_ll_ctx* ctx, float w, int32_t n, const mrp_ll_ta_root* r
     const int32_t k = todo[q];
     bool all = true;
     if (q >= needScan.size()) {
-      rc = taEpsRootRest(ctx, w, roots[k], planned[k], paths[q], all);
+      rc = taEpsRootRest(ctx, w, roots[k], storeIds ? storeIds[k] : nullptr, planned[k], paths[q], all);
       if (rc != MRP_LL_SUCCESS) return rc;
     }
     if (!all) continue;  // no node: found stays -1
@@ -177,8 +187,8 @@ int taEpsRootLaunch(mrp_ll_ctx* ctx, float w, int32_t n, const mrp_ll_ta_root* r
 
 extern "C" {
 
-int mrp_ll_ta_eps_root_batch(mrp_ll_ctx* ctx, float w, int32_t nRoots, const mrp_ll_ta_root* roots, mrp_ll_conflict* conflicts,
-                             int32_t* planned) {
+int mrp_ll_ta_eps_root_batch_stored(mrp_ll_ctx* ctx, float w, int32_t nRoots, const mrp_ll_ta_root* roots, mrp_ll_conflict* conflicts,
+                                    int32_t* planned, const int32_t* const* resultPathIds) {
   if (!ctx) return MRP_LL_E_INVALID;
   if (nRoots < 0 || !(w >= 1.0f) || (nRoots > 0 && (!roots || !planned || !conflicts))) {
     ctx->err = "mrp_ll_ta_eps_root_batch: invalid argument";
@@ -189,10 +199,15 @@ int mrp_ll_ta_eps_root_batch(mrp_ll_ctx* ctx, float w, int32_t nRoots, const mrp
     return MRP_LL_E_BUSY;
   }
   if (nRoots == 0) return MRP_LL_SUCCESS;
-  mrp::host::blankTaRootOutputs(ctx->env, nRoots, roots, planned, conflicts);
-  const int rc = taEpsRootLaunch(ctx, w, nRoots, roots, planned, conflicts);
-  if (rc != MRP_LL_SUCCESS) mrp::host::blankTaRootOutputs(ctx->env, nRoots, roots, planned, conflicts);  // nothing half-told
+  mrp::host::blankTaRootOutputs(ctx->env, nRoots, roots, planned, conflicts, resultPathIds);
+  const int rc = taEpsRootLaunch(ctx, w, nRoots, roots, planned, conflicts, resultPathIds);
+  if (rc != MRP_LL_SUCCESS) mrp::host::blankTaRootOutputs(ctx->env, nRoots, roots, planned, conflicts, resultPathIds);  // nothing half-told
   return rc;
+}
+
+int mrp_ll_ta_eps_root_batch(mrp_ll_ctx* ctx, float w, int32_t nRoots, const mrp_ll_ta_root* roots, mrp_ll_conflict* conflicts,
+                             int32_t* planned) {
+  return mrp_ll_ta_eps_root_batch_stored(ctx, w, nRoots, roots, conflicts, planned, nullptr);
 }
 
 }  // extern "C"

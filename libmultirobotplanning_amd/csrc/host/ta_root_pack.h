@@ -18,6 +18,8 @@ namespace host {
 struct TaRootStaging {
   std::vector<DevJob> recs;            // one per ACCEPTED root, in the caller's order
   std::vector<uint32_t> words;         // their agent words; DevJob::vc_off counts from wordBase
+  std::vector<uint32_t> slotWords;     // mrp_ll_ta_eps_root_batch_stored: one path-store slot per agent of the roots that store,
+                                       // behind `words` in the launch's buffer (DevJob::ec_off; ll_device.h)
   std::vector<int32_t> devRootOf;      // [n_roots] the root's record in recs, -1: refused
   std::vector<uint32_t> firstResult;   // [n_roots] its first result (refused: unused)
   uint32_t nResults = 0;               // results (DevResult + output area) of the launch
@@ -25,10 +27,14 @@ struct TaRootStaging {
 
 // What the call refuses (mrp_ll.h): a null array, n_agents outside 1 .. 64, an unknown map, a start outside the grid, a task
 // whose table is unknown or belongs to another map or whose goal lies outside the grid — every case in which packJob would
-// refuse the ordinary job of one of the agents.
-static inline bool taRootValid(const PackEnv& env, const mrp_ll_ta_root& r) {
+// refuse the ordinary job of one of the agents.  storeIds (mrp_ll_ta_eps_root_batch_stored; nullptr: none): the path-store
+// slot of each agent's path, -1 = not stored; any other value outside the reserved store refuses the root.
+static inline bool taRootValid(const PackEnv& env, const mrp_ll_ta_root& r, const int32_t* storeIds = nullptr) {
   if (r.n_agents < 1 || r.n_agents > static_cast<int32_t>(kTaRootMaxAgents)) return false;
   if (!r.starts_xy || !r.goals_xy || !r.heuristic_ids || !r.results) return false;
+  if (storeIds)
+    for (int a = 0; a < r.n_agents; ++a)
+      if (storeIds[a] < -1 || (storeIds[a] >= 0 && static_cast<uint32_t>(storeIds[a]) >= env.pathStoreSlots)) return false;
   if (r.map_id < 0 || r.map_id >= static_cast<int32_t>(env.maps.size())) return false;
   const MapRec& mp = env.maps[r.map_id];
   auto inGrid = [&](int x, int y) { return x >= 0 && x < mp.dimx && y >= 0 && y < mp.dimy; };
@@ -44,16 +50,21 @@ static inline bool taRootValid(const PackEnv& env, const mrp_ll_ta_root& r) {
 
 // wordBase: where st.words will stand in the launch's constraint-word buffer.  algo / w: MRP_LL_ASTAR_TA (w unused) for
 // mrp_ll_ta_root_batch, MRP_LL_ASTAR_EPS_TA and its weight for mrp_ll_ta_eps_root_batch (ll_device.h taEpsRootAgentJob).
+// storeIds: nullptr, or per root nullptr or its agents' path-store slots (taRootValid): st.slotWords, which the caller
+// copies behind st.words; a root without ids has no run there and keeps ec_off == vc_off.
 static inline void packTaRootsAs(const PackEnv& env, uint32_t algo, float w, int32_t n, const mrp_ll_ta_root* roots, uint32_t wordBase,
-                                 TaRootStaging& st) {
+                                 TaRootStaging& st, const int32_t* const* storeIds = nullptr) {
   st.recs.clear();
   st.words.clear();
+  st.slotWords.clear();
+  std::vector<int64_t> slotRun;  // per record: where its run starts in slotWords, -1: none
   st.devRootOf.assign(n, -1);
   st.firstResult.assign(n, 0);
   st.nResults = 0;
   for (int32_t k = 0; k < n; ++k) {
     const mrp_ll_ta_root& r = roots[k];
-    if (!taRootValid(env, r)) continue;
+    const int32_t* ids = storeIds ? storeIds[k] : nullptr;
+    if (!taRootValid(env, r, ids)) continue;
     const MapRec& mp = env.maps[r.map_id];
     DevJob d;
     std::memset(&d, 0, sizeof(d));
@@ -70,6 +81,7 @@ static inline void packTaRootsAs(const PackEnv& env, uint32_t algo, float w, int
     d.store_out_id = kNoStoreSlot;
     d.n_ctx = static_cast<uint32_t>(r.n_agents);
     d.reserved = st.nResults;
+    slotRun.push_back(ids ? static_cast<int64_t>(st.slotWords.size()) : -1);
     for (int a = 0; a < r.n_agents; ++a) {
       const bool noGoal = r.heuristic_ids[a] < 0;
       const uint32_t gx = noGoal ? 0u : static_cast<uint32_t>(r.goals_xy[2 * a]), gy = noGoal ? 0u : static_cast<uint32_t>(r.goals_xy[2 * a + 1]);
@@ -77,12 +89,15 @@ static inline void packTaRootsAs(const PackEnv& env, uint32_t algo, float w, int
                          (gy << 24));
       st.words.push_back(noGoal ? 0u : env.heurs[r.heuristic_ids[a]].wordOff);
       st.words.push_back(noGoal ? kTaNoGoal : 0u);
+      if (ids) st.slotWords.push_back(ids[a] >= 0 ? static_cast<uint32_t>(ids[a]) : kNoStoreSlot);
     }
     st.devRootOf[k] = static_cast<int32_t>(st.recs.size());
     st.firstResult[k] = st.nResults;
     st.nResults += static_cast<uint32_t>(r.n_agents);
     st.recs.push_back(d);
   }
+  for (size_t q = 0; q < st.recs.size(); ++q)
+    if (slotRun[q] >= 0) st.recs[q].ec_off = wordBase + static_cast<uint32_t>(st.words.size()) + static_cast<uint32_t>(slotRun[q]);
 }
 
 static inline void packTaRoots(const PackEnv& env, int32_t n, const mrp_ll_ta_root* roots, uint32_t wordBase, TaRootStaging& st) {
@@ -114,14 +129,14 @@ static inline void notRunResult(mrp_ll_result& r, int32_t status) {
 // MRP_LL_BAD_JOB and of any other root MRP_LL_NOT_RUN, their other fields 0.  Written before the first step that can fail and
 // again when one did, so that a non-zero return never leaves an output as the caller passed it in.
 static inline void blankTaRootOutputs(const PackEnv& env, int32_t n, const mrp_ll_ta_root* roots, int32_t* planned,
-                                      mrp_ll_conflict* conflicts) {
+                                      mrp_ll_conflict* conflicts, const int32_t* const* storeIds = nullptr) {
   for (int32_t k = 0; k < n; ++k) {
     std::memset(&conflicts[k], 0, sizeof(mrp_ll_conflict));
     conflicts[k].found = -1;
     planned[k] = 0;
     const mrp_ll_ta_root& r = roots[k];
     if (!r.results || r.n_agents <= 0) continue;
-    const int32_t status = taRootValid(env, r) ? MRP_LL_NOT_RUN : MRP_LL_BAD_JOB;
+    const int32_t status = taRootValid(env, r, storeIds ? storeIds[k] : nullptr) ? MRP_LL_NOT_RUN : MRP_LL_BAD_JOB;
     for (int a = 0; a < r.n_agents; ++a) notRunResult(r.results[a], status);
   }
 }

@@ -140,6 +140,9 @@ MRP_DEV_FN void taRootAgentJob(DevJob& d, uint32_t startGoal, uint32_t heurOff, 
 // the CBS-TA root's above, with algo MRP_LL_ASTAR_EPS_TA and w.  Agent a's descriptor: what packJob makes for the ordinary
 // unconstrained MRP_LL_ASTAR_EPS_TA job whose shipped context is the paths of agents 0 .. a - 1 — the table's width and rows
 // (0, 0 for agent 0, whose context is empty) —, except path_off: the workgroup's table lies in its slot already.
+// mrp_ll_ta_eps_root_batch_stored: a root whose paths also go to the path store has ec_off != vc_off, and cons[ec_off + a] =
+// agent a's slot, or kNoStoreSlot (a run of its own behind all roots' agent words; ec_off == vc_off: nothing is stored, and
+// the record is word for word what it was before the store served this call).
 MRP_DEV_FN void taEpsRootAgentJob(DevJob& d, uint32_t startGoal, uint32_t heurOff, uint32_t flags, int64_t budget, uint32_t nAgentsPad,
                                   uint32_t tPad) {
   d.sx = startGoal & 0xFFu; d.sy = (startGoal >> 8) & 0xFFu; d.gx = (startGoal >> 16) & 0xFFu; d.gy = startGoal >> 24;

@@ -1,7 +1,7 @@
 // From a job descriptor to a search: the LDS window's size, the host / path-store access helpers (hostLoad32, hostStore32,
 // storeLoad), job staging shared by all searches (stageConstraints, fillCtx, baseCJob, putCJob / getCRes), the arena slot's
-// cut (cutHeaps, cutArena, compactFits), and the two CBS / ECBS job runners: runJob (stageFocalTable, compactAttempt, then
-// arenaAttempt) and runChain (the root chain of an ECBS conflict tree), with what they share with the other job loops
+// cut (cutHeaps, cutArena, compactFits), the by-id focal table build (buildIdTableInArena), and the two CBS / ECBS job runners:
+// runJob (stageFocalTable, compactAttempt, then arenaAttempt) and runChain (the root chain of an ECBS conflict tree), with what they share with the other job loops
 // (publishPath, beginJob / endJob).
 // Needs ll_slot.h (slot::), ll_compact.h (ct::), ll_arena_heap.h and ll_arena_search.h.
 #ifndef MRP_LL_JOBS_H
@@ -200,6 +200,64 @@ DEVI bool frontHandsOver(const LaunchParams& P, const DevJob& J) {
   return (J.ctx_flags & kCtxHeavy) != 0 || P.lds_nodes == 0 || J.dimx > 32u || J.dimy > 32u || J.n_agents_pad > 128u || J.n_ec > 64u;
 }
 
+// ---- a focal table built from the path store (kCtxById): what stageFocalTable and runJobTaEps (ll_ta.h) share -----------
+// The table starts as kEmptyCell everywhere; the barrier stands between the fill and the columns' stores.
+// The slots named by a job were written by OTHER workgroups of this same resident launch (possibly on another XCD,
+// whose L2 is not coherent with ours), each before its job's completion was published (processJob writes them in
+// front of residentLoop's system-scope release), and slots are recycled.  Every read of the store is therefore a storeLoad:
+// an agent-scope load that goes past this CU's L1 to the coherent level.  (MRP_LL_STORE_ACQUIRE_FENCE, the A/B build: one
+// agent-scope acquire drops whatever stale copies this CU's L1 / this XCD's L2 may hold from an earlier use of a recycled
+// slot; after it plain, cached, coalesced loads are correct — MI355X_MICROARCH.md "Valid forms": poll -> ONE acquire ->
+// s_waitcnt -> barrier -> plain loads.)
+DEVI void clearIdTable(uint16_t* dst, uint32_t pathBytes) {
+  uint32_t* d32 = (uint32_t*)dst;
+  for (uint32_t i = threadIdx.x; i < pathBytes / 4; i += 64) d32[i] = 0xFFFFFFFFu;  // kEmptyCell everywhere
+#ifdef MRP_LL_STORE_ACQUIRE_FENCE  // A/B: one fence + plain loads instead of agent-scope loads
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+  __syncthreads();
+}
+// Agents a0 .. a0 + 63 of the id list, one per lane: the slot and its length word (one gather for all lengths).  An id
+// outside the store — kNoStoreSlot: an empty path, the searching agent itself — has length 0.
+DEVI void loadIdChunk(const uint32_t* ids, uint32_t a0, uint32_t nCtx, const uint16_t* store, uint32_t stride, uint32_t slots,
+                      uint32_t& idL, uint32_t& lenL) {
+  const uint32_t lane = threadIdx.x;
+  idL = kNoStoreSlot; lenL = 0;
+  if (a0 + lane < nCtx) idL = hostLoad32(ids + a0 + lane);
+  if (idL < slots) lenL = storeLoad(store + (size_t)idL * stride);
+  if (lenL > stride - 1) lenL = stride - 1;
+}
+// The table [tPad][nAgentsPad] in the arena (global memory) at dst: one lane per AGENT, agents in chunks of 64, so that a
+// row of the table is one coalesced store (a lane per time step would scatter 2-byte stores 2 * n_agents_pad bytes apart
+// — measured on agents100: the longest conflict-tree chain of a batch a third slower).  The reads gather one cell per slot
+// and stay in L2 from row to row; eight rows are in flight at a time.  A path shorter than tPad is held at its last cell; an
+// id outside the store or a zero length word leaves the column empty.  The caller has made sure that the table fits at dst
+// and that nCtx <= nAgentsPad, and puts a barrier between this and the first read of the table.
+DEVI void buildIdTableInArena(uint16_t* dst, const uint32_t* ids, uint32_t nCtx, uint32_t tPad, uint32_t nAgentsPad,
+                              const uint16_t* store, uint32_t stride, uint32_t slots) {
+  const uint32_t lane = threadIdx.x;
+  clearIdTable(dst, tPad * nAgentsPad * 2);
+  for (uint32_t a0 = 0; a0 < nCtx; a0 += 64) {
+    uint32_t idL, lenA;
+    loadIdChunk(ids, a0, nCtx, store, stride, slots, idL, lenA);
+    const uint16_t* slotA = store + (size_t)(idL < slots ? idL : 0) * stride + 1;
+    const bool hasA = idL < slots && lenA != 0;
+    for (uint32_t t0 = 0; t0 < tPad; t0 += 8) {
+      uint32_t v[8];
+#pragma unroll
+      for (uint32_t u = 0; u < 8; ++u) {
+        const uint32_t t = t0 + u;
+        v[u] = kEmptyCell;
+        if (hasA && t < tPad) v[u] = storeLoad(slotA + (t < lenA ? t : lenA - 1));
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < 8; ++u)
+        if (hasA && t0 + u < tPad) dst[(t0 + u) * nAgentsPad + a0 + lane] = (uint16_t)v[u];
+    }
+  }
+}
+
 // runJob's first phase: the job's focal path table leaves host memory, or is built from the path store, in one coalesced
 // pass — into `ldsPaths` (behind the LDS window) when it fits there, else into `pathsArena` (the slot's path-table copy).
 // Leaves where the table is in c.paths / c.pathsLds; false: a table named by ids fits nowhere (nothing was written).
@@ -213,76 +271,42 @@ DEVI bool stageFocalTable(const LaunchParams& P, const DevJob& J, uint8_t* ldsPa
   if (pathBytes != 0 && (J.ctx_flags & kCtxById)) {
     // f2: the CT node's paths are named by their slots in the device-resident path store (each was written there by
     // the search that produced it); the time-major table [t][agent] is built here, on the device, instead of being
-    // packed by the host and read over PCIe.  One coalesced read per agent (lane = time step).
+    // packed by the host and read over PCIe.
     const bool inLds = idTableInLds<TIERS>(P, pathBytes);
     if (!inLds && pathBytes > P.arena_paths_bytes) return false;  // (the host packer refuses such a job; never write past the slot)
     uint16_t* dst = inLds ? (uint16_t*)ldsPaths : (uint16_t*)pathsArena;
-    {
-      uint32_t* d32 = (uint32_t*)dst;
-      for (uint32_t i = lane; i < pathBytes / 4; i += 64) d32[i] = 0xFFFFFFFFu;  // kEmptyCell everywhere
-    }
-    // The slots named here were written by OTHER workgroups of this same resident launch (possibly on another XCD,
-    // whose L2 is not coherent with ours), each before its job's completion was published (processJob writes them in
-    // front of residentLoop's system-scope release).  One agent-scope acquire drops whatever stale copies this CU's L1 /
-    // this XCD's L2 may hold from an earlier use of a recycled slot; after it plain, cached, coalesced loads are
-    // correct (MI355X_MICROARCH.md "Valid forms": poll -> ONE acquire -> s_waitcnt -> barrier -> plain loads).
-#ifdef MRP_LL_STORE_ACQUIRE_FENCE  // A/B: one fence + plain loads instead of agent-scope loads
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-    __syncthreads();
     const uint32_t* ids = P.cons + J.path_off;
     const uint32_t nCtx = J.n_ctx;
-    for (uint32_t a0 = 0; a0 < nCtx; a0 += 64) {
-      // this chunk's ids and lengths, one agent per lane (one gather for all lengths)
-      uint32_t idL = kNoStoreSlot, lenL = 0;
-      if (a0 + lane < nCtx) idL = hostLoad32(ids + a0 + lane);
-      if (idL < P.path_store_slots) lenL = storeLoad(P.path_store + (size_t)idL * P.path_store_stride);
-      if (lenL > P.path_store_stride - 1) lenL = P.path_store_stride - 1;
-      const uint32_t nHere = nCtx - a0 < 64 ? nCtx - a0 : 64;
-      if (!inLds) {
-        // Table in the arena (global memory): one lane per AGENT, so that a row of the table is one coalesced store
-        // (a lane per time step would scatter 2-byte stores 2 * n_agents_pad bytes apart — measured on agents100: the
-        // longest conflict-tree chain of a batch a third slower).  The reads gather one cell per slot and stay in L2
-        // from row to row; eight rows are in flight at a time.
-        const uint32_t lenA = lenL;
-        const uint16_t* slotA = P.path_store + (size_t)(idL < P.path_store_slots ? idL : 0) * P.path_store_stride + 1;
-        const bool hasA = idL < P.path_store_slots && lenA != 0;
-        for (uint32_t t0 = 0; t0 < c.tPad; t0 += 8) {
-          uint32_t v[8];
-#pragma unroll
-          for (uint32_t u = 0; u < 8; ++u) {
-            const uint32_t t = t0 + u;
-            v[u] = kEmptyCell;
-            if (hasA && t < c.tPad) v[u] = storeLoad(slotA + (t < lenA ? t : lenA - 1));
-          }
-#pragma unroll
-          for (uint32_t u = 0; u < 8; ++u)
-            if (hasA && t0 + u < c.tPad) dst[(t0 + u) * c.nAgentsPad + a0 + lane] = (uint16_t)v[u];
-        }
-        continue;
-      }
+    if (!inLds) {
+      buildIdTableInArena(dst, ids, nCtx, c.tPad, c.nAgentsPad, P.path_store, P.path_store_stride, P.path_store_slots);
+    } else {
       // table in LDS: a lane per time step (one coalesced read per agent); eight agents' loads are in flight before
       // the first store
-      for (uint32_t t0 = 0; t0 < c.tPad; t0 += 64) {
-        const uint32_t t = t0 + lane;
-        for (uint32_t q0 = 0; q0 < nHere; q0 += 8) {
-          uint32_t v[8];
-          bool has[8];
+      clearIdTable(dst, pathBytes);
+      for (uint32_t a0 = 0; a0 < nCtx; a0 += 64) {
+        uint32_t idL, lenL;
+        loadIdChunk(ids, a0, nCtx, P.path_store, P.path_store_stride, P.path_store_slots, idL, lenL);
+        const uint32_t nHere = nCtx - a0 < 64 ? nCtx - a0 : 64;
+        for (uint32_t t0 = 0; t0 < c.tPad; t0 += 64) {
+          const uint32_t t = t0 + lane;
+          for (uint32_t q0 = 0; q0 < nHere; q0 += 8) {
+            uint32_t v[8];
+            bool has[8];
 #pragma unroll
-          for (uint32_t u = 0; u < 8; ++u) {
-            uint32_t id = kNoStoreSlot, len = 0;
-            if (q0 + u < nHere) {
-              id = __builtin_amdgcn_readlane(idL, q0 + u);
-              len = __builtin_amdgcn_readlane(lenL, q0 + u);
+            for (uint32_t u = 0; u < 8; ++u) {
+              uint32_t id = kNoStoreSlot, len = 0;
+              if (q0 + u < nHere) {
+                id = __builtin_amdgcn_readlane(idL, q0 + u);
+                len = __builtin_amdgcn_readlane(lenL, q0 + u);
+              }
+              has[u] = id < P.path_store_slots && len != 0 && t < c.tPad;  // not: empty path / the searching agent itself
+              v[u] = kEmptyCell;
+              if (has[u]) v[u] = storeLoad(P.path_store + (size_t)id * P.path_store_stride + 1 + (t < len ? t : len - 1));
             }
-            has[u] = id < P.path_store_slots && len != 0 && t < c.tPad;  // not: empty path / the searching agent itself
-            v[u] = kEmptyCell;
-            if (has[u]) v[u] = storeLoad(P.path_store + (size_t)id * P.path_store_stride + 1 + (t < len ? t : len - 1));
-          }
 #pragma unroll
-          for (uint32_t u = 0; u < 8; ++u)
-            if (has[u]) dst[t * c.nAgentsPad + a0 + q0 + u] = (uint16_t)v[u];
+            for (uint32_t u = 0; u < 8; ++u)
+              if (has[u]) dst[t * c.nAgentsPad + a0 + q0 + u] = (uint16_t)v[u];
+          }
         }
       }
     }
@@ -478,6 +502,9 @@ DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t*
 // store, where the jobs of the conflict-tree nodes that contain it will read it; visible to them because they are published
 // after this job's completion was seen.  sidOf() names the slot and is asked between the two.  Agent-scope stores: through
 // this XCD's L2 to memory, where the readers' agent-scope loads find them — no write-back of the whole L2 (residentLoop).
+// A path that does not fit its slot (len >= path_store_stride; the packer cannot know the length beforehand) is NOT stored:
+// the slot keeps its previous content, which a by-id reader would take for the path — callers keep their paths below
+// max_horizon and treat a returned n_states >= max_horizon as not stored (mrp_ll.h).
 template <class SidFn>
 DEVI void publishPath(const LaunchParams& P, const uint16_t* outPath, uint32_t len, uint32_t* hostDst, SidFn sidOf) {
   const uint32_t lane = threadIdx.x;

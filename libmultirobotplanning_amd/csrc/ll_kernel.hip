@@ -167,7 +167,7 @@ DEVI bool processJob(const LaunchParams& P, const DevJob* jobSrc, DevResult* res
     else if (algo == 4) {  // MRP_LL_ASTAR_EPS_TA: arena tier only; the result comes back through the staging record
       const uint64_t th0 = __builtin_amdgcn_s_memrealtime();
       runJobTaEps<false>(&jobS, &resS, arenaSlot, P.maps, P.cons, P.paths, P.arena_scratch_off, P.out_stride, P.arena_nodes,
-                  P.arena_rows, P.arena_row_words, P.arena_paths_bytes);
+                  P.arena_rows, P.arena_row_words, P.arena_paths_bytes, P.path_store, P.path_store_stride, P.path_store_slots);
       __syncthreads();
       res.status = rfli(resS.status); res.cost = rfli(resS.cost); res.fmin = rfli(resS.fmin);
       res.n_states = rfli(resS.n_states);

@@ -366,12 +366,17 @@ DEVI bool orderedWalkTaEps(Mem<TierHbm>& m, Mem<TierFocalPos>& mf, SState& s, fl
 // staged it, the result goes to `out` (status, cost, fmin, n_states, expanded, nodes_created, tier).
 // IN_PLACE (ll_ta_eps_root.h): the focal table [t_pad][n_agents_pad] already lies in the slot's path area — where the
 // ordinary job copies its shipped one — and is taken as it is; nothing is copied, path_off is not looked at.  The ordinary
-// job is the IN_PLACE = false instance, unchanged.
+// job is the IN_PLACE = false instance, which knows two more sources: a table shipped by the host (paths[path_off]), or —
+// kCtxById — the conflict-tree node's paths named by their path-store slots (n_ctx ids at cons[path_off]): the workgroup
+// builds the table in the slot's path area with ll_jobs.h buildIdTableInArena, the build runJob uses for a table in the
+// arena.  A by-id table that does not fit the path area, or names more agents than its rows are wide, is ST_BAD with nothing
+// written (the host packer refuses such a job).  pathStore / storeStride / storeSlots: LaunchParams' path store.
 template <bool IN_PLACE>
 __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResult* out, uint8_t* arenaSlot, const uint32_t* maps,
                                                       const uint32_t* consHost, const uint16_t* pathsHost,
                                                       uint32_t scratchOff, uint32_t outStride, uint32_t arenaNodes,
-                                                      uint32_t arenaRows, uint32_t arenaRowWords, uint32_t arenaPathsBytes) {
+                                                      uint32_t arenaRows, uint32_t arenaRowWords, uint32_t arenaPathsBytes,
+                                                      const uint16_t* pathStore, uint32_t storeStride, uint32_t storeSlots) {
   typedef TierHbm T;
   typedef TierFocalPos TF;
   typedef T::E E;
@@ -395,6 +400,7 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
   uint32_t* consLocal = slot::consCopy(arenaSlot, scratchOff, outStride);
   uint8_t* pathsArena = slot::pathsCopy(arenaSlot, scratchOff, outStride);
   stageConstraints(consHost, rfl(Jp->vc_off), c.nVc, c.nEc, consLocal, c.vc, c.ec);
+  bool tableOk = true;
   {
     const uint32_t pathOff = rfl(Jp->path_off);
     const uint32_t pathBytes = tPad * c.nAgentsPad * 2;  // multiple of 32
@@ -403,6 +409,18 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
       c.nAgentsPad = 0;
     } else if constexpr (IN_PLACE) {
       c.paths = (const uint16_t*)pathsArena;  // (its writer made sure that it fits)
+    } else if (rfl(Jp->ctx_flags) & kCtxById) {
+      // (the store's arguments arrive in vector registers too: wave-uniform, so are the build's loop bounds and slot bases)
+      const uint32_t nCtx = rfl(Jp->n_ctx);
+      if (pathBytes > rfl(arenaPathsBytes) || nCtx > c.nAgentsPad) {  // never write past the path area
+        tableOk = false;
+        c.paths = nullptr;
+        c.nAgentsPad = 0;
+      } else {
+        buildIdTableInArena((uint16_t*)pathsArena, consHost + pathOff, nCtx, tPad, c.nAgentsPad,
+                            (const uint16_t*)rfl64((uint64_t)pathStore), rfl(storeStride), rfl(storeSlots));
+        c.paths = (const uint16_t*)pathsArena;
+      }
     } else if (pathBytes <= arenaPathsBytes) {
       const uint32_t* psrc = (const uint32_t*)(pathsHost + pathOff);
       uint32_t* dst = (uint32_t*)pathsArena;
@@ -440,7 +458,10 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
 
   bool run = true;
   uint32_t h0 = 0;
-  if (rows < 2u || !env.startH(c.sx, c.sy, h0)) {  // no room for a second time step / the task is out of reach
+  if (!tableOk) {
+    status = ST_BAD;
+    run = false;
+  } else if (rows < 2u || !env.startH(c.sx, c.sy, h0)) {  // no room for a second time step / the task is out of reach
     status = ST_CAP_HORIZON;
     run = false;
   } else if (capN < 16u) {

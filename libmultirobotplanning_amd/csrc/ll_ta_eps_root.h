@@ -21,6 +21,8 @@
 // __syncthreads() stands between a column's stores and the next search's loads.
 // A table that would outgrow the path area (only under MRP_LL_ARENA_PATHS_BYTES) ends the kernel's part behind the agent
 // whose path did not fit: the answer says kTaRootScanSkipped and how many agents are planned, the host runs the rest.
+// mrp_ll_ta_eps_root_batch_stored: cons[ec_off + a] names the path-store slot that also receives agent a's path
+// (publishPath, as an ordinary job with MRP_LL_JOB_STORE_RESULT); the slot of an agent the root did not plan is not touched.
 #ifndef MRP_LL_TA_EPS_ROOT_H
 #define MRP_LL_TA_EPS_ROOT_H
 
@@ -35,6 +37,7 @@ DEVI void runTaEpsRoot(const LaunchParams& P, const DevJob* rootSrc, uint8_t* sm
   const uint32_t n = rfl(jobS.n_ctx), base = rfl(jobS.reserved);
   if (n < 1u || n > kTaRootMaxAgents) return;  // (the host refuses such a root: nothing is run, nothing written)
   const uint32_t* who = P.cons + rfl(jobS.vc_off);
+  const uint32_t* storeIds = rfl(jobS.ec_off) != rfl(jobS.vc_off) ? P.cons + rfl(jobS.ec_off) : nullptr;  // (ll_device.h)
   int64_t budget = (int64_t)rfl64((uint64_t)jobS.max_expansions);  // < 0: unlimited
   const uint32_t npad = (n + 15u) & ~15u;  // <= 64: one lane per column
   uint16_t* outPath = slot::outPath(arenaSlot, P.arena_scratch_off, P.out_stride);
@@ -46,11 +49,12 @@ DEVI void runTaEpsRoot(const LaunchParams& P, const DevJob* rootSrc, uint8_t* sm
   for (uint32_t a = 0; allOk && tableOk && a < n; ++a) {
     const uint32_t sg = rfl(hostLoad32(who + a * kTaRootAgentWords)), heurOff = rfl(hostLoad32(who + a * kTaRootAgentWords + 1u)),
                    flags = rfl(hostLoad32(who + a * kTaRootAgentWords + 2u));
+    const uint32_t storeId = storeIds ? rfl(hostLoad32(storeIds + a)) : kNoStoreSlot;  // kNoStoreSlot: the path goes to the host only
     __syncthreads();
     taEpsRootAgentJob(jobS, sg, heurOff, flags, budget, a ? npad : 0u, a ? maxLen : 0u);  // (every lane stores the same words)
     __syncthreads();
     runJobTaEps<true>(&jobS, &resS, arenaSlot, P.maps, P.cons, P.paths, P.arena_scratch_off, P.out_stride, P.arena_nodes,
-                      P.arena_rows, P.arena_row_words, P.arena_paths_bytes);
+                      P.arena_rows, P.arena_row_words, P.arena_paths_bytes, P.path_store, P.path_store_stride, P.path_store_slots);
     __syncthreads();
     res.status = rfli(resS.status); res.cost = rfli(resS.cost); res.fmin = rfli(resS.fmin);
     res.n_states = rfli(resS.n_states);
@@ -65,7 +69,7 @@ DEVI void runTaEpsRoot(const LaunchParams& P, const DevJob* rootSrc, uint8_t* sm
       break;
     }
     const uint32_t len = rfl((uint32_t)res.n_states);
-    publishPath(P, outPath, len, (uint32_t*)(P.out_paths + (size_t)(base + a) * P.out_host_stride), [] { return kNoStoreSlot; });
+    publishPath(P, outPath, len, (uint32_t*)(P.out_paths + (size_t)(base + a) * P.out_host_stride), [&] { return storeId; });
     const uint32_t newMax = len > maxLen ? len : maxLen;
     if (len >= 1u && (uint64_t)newMax * npad * 2u <= (uint64_t)P.arena_paths_bytes) {
       // the rows this path adds: the planned columns at their last cell, every other column empty (its own comes below)

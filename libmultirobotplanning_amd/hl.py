@@ -630,7 +630,11 @@ def solve_ecbs_ta_batch(instances: Sequence[Dict], w: float, max_task_assignment
     """mrp_hl_solve_ecbs_ta_batch: ECBS with task assignment (ecbs_ta.hpp:94-352, low level AStarEpsilon under the same
     weight w >= 1) for a batch of instances; instances and results as solve_cbs_ta_batch.  use_root_kernel: roots through
     mrp_ll_ta_eps_root_batch (one workgroup each) or, False (the default: measured faster for thousands of instances), as n
-    dependent low-level jobs; same results."""
+    dependent low-level jobs; same results.
+    Environment, read once per call: MRP_HL_TA_DEVICE_PATHS=1 keeps every path in the engine's device-resident path store and
+    names a search's focal context by slot instead of shipping its table (same results; off by default);
+    MRP_HL_TA_PATH_SLOTS=N sets the store's slot count (unset: four per agent of the batch, 256 .. 65536; not tuned) — a
+    search that finds no free slot, or whose context has a path outside the store, goes out as without the knob."""
     lib = load_library(_lib_path)
     if not hasattr(lib, "mrp_hl_solve_ecbs_ta_batch"):
         raise RuntimeError("this build of the drivers has no mrp_hl_solve_ecbs_ta_batch")

@@ -107,7 +107,8 @@ EXPORTS = ["mrp_ll_create", "mrp_ll_destroy", "mrp_ll_last_error", "mrp_ll_uploa
            "mrp_ll_compute_heuristics", "mrp_ll_read_heuristic", "mrp_ll_heuristic_lookup", "mrp_ll_submit_scan",
            "mrp_ll_constraint_store_reserve", "mrp_ll_submit_sets", "mrp_ll_session_front_tables",
            "mrp_ll_submit_node", "mrp_ll_assign_batch", "mrp_ll_assign_series_create", "mrp_ll_assign_series_next",
-           "mrp_ll_assign_series_destroy", "mrp_ll_ta_root_batch", "mrp_ll_ta_eps_root_batch"]
+           "mrp_ll_assign_series_destroy", "mrp_ll_ta_root_batch", "mrp_ll_ta_eps_root_batch",
+           "mrp_ll_ta_eps_root_batch_stored"]
 
 _lib = None
 
@@ -210,6 +211,9 @@ def load_library(path: Optional[str] = None):
     lib.mrp_ll_ta_eps_root_batch.restype = ctypes.c_int
     lib.mrp_ll_ta_eps_root_batch.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_int32, ctypes.POINTER(mrp_ll_ta_root),
                                              ctypes.POINTER(mrp_ll_conflict), I32P]
+    lib.mrp_ll_ta_eps_root_batch_stored.restype = ctypes.c_int
+    lib.mrp_ll_ta_eps_root_batch_stored.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_int32, ctypes.POINTER(mrp_ll_ta_root),
+                                                    ctypes.POINTER(mrp_ll_conflict), I32P, ctypes.POINTER(I32P)]
     lib.mrp_ll_ta_root_batch.restype = ctypes.c_int
     lib.mrp_ll_ta_root_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(mrp_ll_ta_root), I32P,
                                          ctypes.POINTER(mrp_ll_conflict)]
@@ -557,14 +561,28 @@ class LowLevelEngine:
                              conflict={k: getattr(conf[i], k) for k in names})
                 for i, (na, cres, states, actions, costs) in enumerate(per_root)]
 
-    def ta_eps_root_batch(self, roots: Sequence[TaRoot], w: float, states_cap: Optional[int] = None, raw_rc: bool = False):
+    def ta_eps_root_batch(self, roots: Sequence[TaRoot], w: float, states_cap: Optional[int] = None, raw_rc: bool = False,
+                          result_path_ids: Optional[Sequence[Optional[Sequence[int]]]] = None):
         """mrp_ll_ta_eps_root_batch: the roots of ECBS-TA conflict trees under weight w, one workgroup each, in one launch:
         agent a's MRP_LL_ASTAR_EPS_TA search sees the paths of the agents before it.  Returns one TaRootResult per root
-        (conflict["count"] is the node's focalHeuristic); with raw_rc the call's return code instead of raising."""
+        (conflict["count"] is the node's focalHeuristic); with raw_rc the call's return code instead of raising.
+        result_path_ids (mrp_ll_ta_eps_root_batch_stored): per root None or one path-store slot per agent (-1: not stored)
+        that also receives the agent's path, for later jobs that name it in path_ids; the answer is the same."""
         n = len(roots)
         cap = states_cap or self.max_horizon
         croots, planned, conf, per_root, keep = self._marshal_ta_roots(roots, cap)
-        rc = self._lib.mrp_ll_ta_eps_root_batch(self._h, w, n, croots, conf, planned.ctypes.data_as(I32P))
+        if result_path_ids is not None:
+            if len(result_path_ids) != n:
+                raise ValueError("result_path_ids: one entry per root")
+            arrs = [None if ids is None else np.ascontiguousarray(np.asarray(ids, dtype=np.int32).reshape(-1)) for ids in result_path_ids]
+            for r, a in zip(roots, arrs):
+                if a is not None and len(a) != len(r.starts):
+                    raise ValueError("result_path_ids: one slot per agent")
+            ptrs = (I32P * max(n, 1))(*[a.ctypes.data_as(I32P) if a is not None else I32P() for a in arrs])
+            keep.append((arrs, ptrs))
+            rc = self._lib.mrp_ll_ta_eps_root_batch_stored(self._h, w, n, croots, conf, planned.ctypes.data_as(I32P), ptrs)
+        else:
+            rc = self._lib.mrp_ll_ta_eps_root_batch(self._h, w, n, croots, conf, planned.ctypes.data_as(I32P))
         if raw_rc and rc != 0:
             return rc
         self._check(rc, "mrp_ll_ta_eps_root_batch")

@@ -1,9 +1,11 @@
 """ECBS-TA on the device: instances per second of the batched driver (mrp_hl_solve_ecbs_ta_batch, the time of its rounds:
 tables and the series' optima are set up before) with roots through mrp_ll_ta_eps_root_batch (use_root_kernel 1) and as
 dependent MRP_LL_ASTAR_EPS_TA jobs (0), the answers compared.  Workload: generated 32 x 32 instances with 204 obstacles, ten
-agents, twenty potential goals shared by all agents of an instance, w = 1.3.  The two forms alternate, --repeats runs each
+agents, twenty potential goals shared by all agents of an instance, w = 1.3.  The forms alternate, --repeats runs each
 after one warm-up run each; reported: the median, every run, and the spread (max - min) / median.
-usage: python scripts/ecbs_ta_tree_throughput.py [--instances 2048] [--w 1.3]  (prints one JSON line)"""
+--device-paths adds both forms once more under MRP_HL_TA_DEVICE_PATHS=1 (paths in the engine's path store, contexts by slot;
+--path-slots sets MRP_HL_TA_PATH_SLOTS), interleaved with the other two, answers compared with theirs.
+usage: python scripts/ecbs_ta_tree_throughput.py [--instances 2048] [--w 1.3] [--device-paths]  (prints one JSON line)"""
 import argparse
 import json
 import os
@@ -23,6 +25,8 @@ ap.add_argument("--goals", type=int, default=20)
 ap.add_argument("--maps", type=int, default=16)
 ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--w", type=float, default=1.3)
+ap.add_argument("--device-paths", action="store_true")
+ap.add_argument("--path-slots", type=int, default=0)
 args = ap.parse_args()
 CAP = 128  # states per result buffer
 
@@ -64,21 +68,32 @@ for k in range(args.instances):
                       potential_goals=[goals] * args.agents))
 n = len(insts)
 
-walls, answers, last = {0: [], 1: []}, {}, {}
+legs = [(1, False, "root_kernel"), (0, False, "root_jobs")]
+if args.device_paths:
+    legs += [(1, True, "root_kernel_device_paths"), (0, True, "root_jobs_device_paths")]
+for knob in ("MRP_HL_TA_DEVICE_PATHS", "MRP_HL_TA_PATH_SLOTS"):
+    os.environ.pop(knob, None)
+walls, answers, last = {name: [] for _, _, name in legs}, {}, {}
 for rep in range(args.repeats + 1):  # the first run of each form is the warm-up
-    for use in (1, 0):
+    for use, paths, name in legs:
+        if paths:  # (the driver reads its knobs once per call)
+            os.environ["MRP_HL_TA_DEVICE_PATHS"] = "1"
+            if args.path_slots:
+                os.environ["MRP_HL_TA_PATH_SLOTS"] = str(args.path_slots)
         got, st = hl.solve_ecbs_ta_batch(insts, args.w, use_root_kernel=bool(use), path_cap=CAP)
-        walls[use].append(st["wall_seconds"])
-        last[use] = (got, st)
-        answers[use] = [(g["status"], g["cost"], g["hl_expanded"], g["ll_expanded"], g["num_task_assignments"], g["digest"]) for g in got]
-assert answers[0] == answers[1]
+        for knob in ("MRP_HL_TA_DEVICE_PATHS", "MRP_HL_TA_PATH_SLOTS"):
+            os.environ.pop(knob, None)
+        walls[name].append(st["wall_seconds"])
+        last[name] = (got, st)
+        answers[name] = [(g["status"], g["cost"], g["hl_expanded"], g["ll_expanded"], g["num_task_assignments"], g["digest"]) for g in got]
+assert all(a == answers["root_kernel"] for a in answers.values())
 result = dict(instances=n, agents=args.agents, potential_goals=args.goals, w=args.w, repeats=args.repeats)
-for use, name in ((1, "root_kernel"), (0, "root_jobs")):
-    v = walls[use][1:]
+for _, _, name in legs:
+    v = walls[name][1:]
     m = median(v)
     result[name] = dict(rounds_wall_s=round(m, 5), instances_per_s=round(n / m), walls=[round(x, 5) for x in v],
-                        spread=round((max(v) - min(v)) / m, 4), rounds=last[use][1]["rounds"])
-got, st = last[1]
+                        spread=round((max(v) - min(v)) / m, 4), rounds=last[name][1]["rounds"])
+got, st = last["root_kernel"]
 searches = sum(g["n_ll_searches"] for g in got)
 result["breakdown"] = dict(solved=sum(1 for g in got if g["status"] == hl.SOLVED), searches=searches,
                            root_search_share=round(sum(g["n_root_searches"] for g in got) / max(searches, 1), 4),
