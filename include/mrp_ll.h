@@ -401,6 +401,40 @@ int mrp_ll_assign_series_next(mrp_ll_ctx* ctx, int32_t n, mrp_ll_assign_series* 
                               mrp_ll_assign_result* results /* [n] */);
 void mrp_ll_assign_series_destroy(mrp_ll_assign_series* series);
 
+/* ---- the wide form: up to 256 agents x 256 tasks ---------------------------------------------------------------
+ * The calls above give one lane to each agent and each task, hence 64 x 64.  The _w calls solve the same problem with
+ * the same method, contract, statuses and tie rules for dimensions 0 .. 256: lane l owns the columns and agents
+ * l + 64k.  They are separate calls; nothing above changes.  On a problem that fits 64 x 64 a _w call returns exactly
+ * what the narrow call returns, task_of entry for entry (among equally near tasks the lowest task INDEX wins).
+ * mrp_ll_assign_problem_w is mrp_ll_assign_problem plus mask_words: allowed and forbidden are [n_agents][mask_words]
+ * words, bit t of an agent's mask is bit t % 64 of its word t / 64.  mask_words is 1 .. 4 and, when a mask is given, at
+ * least ceil(n_tasks / 64).  Mask bits at or above n_tasks are ignored.  min_matching is 0 .. 256, a forced task
+ * < n_tasks, a cost 0 .. 2^24 - 1; beyond those limits the problem is MRP_LL_BAD_JOB (MRP_LL_E_INVALID from
+ * mrp_ll_assign_series_create_w).  Everything else is as the narrow calls: ONE launch per call, none for n == 0, a
+ * result that depends on the problem alone, MRP_LL_E_BUSY under the same rules.
+ * Where the cost rows live is a pure function of (n_agents, n_tasks, budget): in LDS when n_agents rows of
+ * 256 * ceil(max(n_agents, n_tasks) / 64) bytes fit the budget (128 x 128 at the default 64 KiB), otherwise in device
+ * memory (256 x 256) — the staged matrix, or for the gather form a matrix the wave writes first.  The answer is the
+ * same either way.  MRP_LL_ASSIGN_LDS_BYTES (0 .. 65536, read once by mrp_ll_create) lowers the budget: a tuning and
+ * test knob, 0 sends every problem with agents to memory rows.
+ * A series made by mrp_ll_assign_series_create_w is advanced and destroyed by the calls above, also together with
+ * narrow series in one mrp_ll_assign_series_next: the children of the narrow series go in one launch and those of the
+ * wide series in another (one launch when all series are of one kind). */
+typedef struct mrp_ll_assign_problem_w {
+  int32_t n_agents, n_tasks;      /* 0 .. 256 */
+  const int32_t* cost;
+  const int32_t* heuristic_ids;
+  const int32_t* starts_xy;
+  const uint64_t* allowed;        /* [n_agents][mask_words] or NULL = all;  gather form */
+  const uint64_t* forbidden;      /* [n_agents][mask_words] or NULL */
+  const int32_t* mode;
+  int32_t min_matching;
+  int32_t mask_words;             /* 1 .. 4 */
+} mrp_ll_assign_problem_w;
+int mrp_ll_assign_batch_w(mrp_ll_ctx* ctx, int32_t n, const mrp_ll_assign_problem_w* problems, mrp_ll_assign_result* results);
+int mrp_ll_assign_series_create_w(mrp_ll_ctx* ctx, int32_t n, const mrp_ll_assign_problem_w* problems,
+                                  mrp_ll_assign_series** out /* [n] */);
+
 /* Copies every map uploaded so far to the device now (otherwise done lazily by the next submit / session_begin). */
 int mrp_ll_sync_maps(mrp_ll_ctx* ctx);
 

@@ -12,8 +12,8 @@
     python -m libmultirobotplanning_amd.cli a_star --startX 0 --startY 0 --goalX 2 --goalY 1 -m map.txt -o out.yaml
                                                                                    (example/a_star.cpp:128-213)
     python -m libmultirobotplanning_amd.cli shortest_path_heuristic -i in.yaml     (example/shortest_path_heuristic.cpp:40-156)
-    python -m libmultirobotplanning_amd.cli assignment -i costs.txt -o out.yaml    (example/assignment.cpp:11-86)
-    python -m libmultirobotplanning_amd.cli next_best_assignment -i costs.txt -o out.yaml
+    python -m libmultirobotplanning_amd.cli assignment -i costs.txt -o out.yaml [--wide]    (example/assignment.cpp:11-86)
+    python -m libmultirobotplanning_amd.cli next_best_assignment -i costs.txt -o out.yaml [--wide]
                                                                                    (example/next_best_assignment.cpp:11-92)
 
 ecbs / cbs   input  (ecbs.cpp:554-574): map.dimensions [x, y], map.obstacles [[x, y]..], agents[].{name,start,goal}
@@ -36,7 +36,8 @@ assignment / next_best_assignment  input: text, one "agent -> task : cost" per l
              with one "  - cost: / assignment:" block per matching of the optimum's cardinality in non-decreasing order
              of cost, "  []" when there is none (next_best_assignment.cpp:73-89); agents in sorted name order, as
              std::map prints them.  Solved on the device (mrp_ll_assign_batch, mrp_ll_assign_series_*): at most 64
-             agents, 64 tasks and costs up to 16 777 215; beyond that the tool says so and exits non-zero.  The order among
+             agents, 64 tasks and costs up to 16 777 215; beyond that the tool says so and exits non-zero.  --wide takes
+             the wide solver (mrp_ll_assign_batch_w, mrp_ll_assign_series_create_w): at most 256 of each.  The order among
              solutions of equal cost is the engine's (include/mrp_ll.h), not Boost's.
 On failure the reference prints "Planning NOT successful!" (and, for ecbs / cbs, writes nothing); so does this tool.
 Several input files may be given to ecbs / cbs / mapf_prioritized_sipp (-i a.yaml -i b.yaml ... with matching -o): they
@@ -270,8 +271,9 @@ def main_shortest_path_heuristic(args, ap) -> int:
 _PAIR = re.compile(r"(\w+)\s*->\s*(\w+)\s*:\s*(\d+)")  # assignment.cpp:41
 
 
-def read_assignment(path: str):
-    """agent names, task names (order of first appearance) and the cost matrix with None where no line set a cost."""
+def read_assignment(path: str, limit: int = 64):
+    """agent names, task names (order of first appearance) and the cost matrix with None where no line set a cost.
+    limit: how many agents and tasks the solver takes (64; 256 with --wide)."""
     agents, tasks, cost = [], [], {}
     with open(path) as f:
         for line in f.read().splitlines():
@@ -286,8 +288,9 @@ def read_assignment(path: str):
                 tasks.append(t)
             key = (agents.index(a), tasks.index(t))
             cost[key] = min(c, cost.get(key, c))  # a pair given twice: two parallel edges, the cheaper one is used
-    if len(agents) > 64 or len(tasks) > 64:
-        raise ValueError("%d agents and %d tasks: the device solver takes at most 64 of each" % (len(agents), len(tasks)))
+    if len(agents) > limit or len(tasks) > limit:
+        raise ValueError("%d agents and %d tasks: the device solver takes at most %d of each%s"
+                         % (len(agents), len(tasks), limit, "" if limit > 64 else " (--wide: 256)"))
     if any(c > 16777215 for c in cost.values()):
         raise ValueError("a cost above 16777215 (2^24 - 1): the device solver does not take it")
     matrix = [[cost.get((a, t)) for t in range(len(tasks))] for a in range(len(agents))]
@@ -303,7 +306,7 @@ def main_assignment(args, ap) -> int:
     if len(args.input) != 1 or len(args.output) != 1:
         ap.error("%s takes one -i and one -o" % args.algo)
     try:
-        agents, tasks, matrix = read_assignment(args.input[0])
+        agents, tasks, matrix = read_assignment(args.input[0], 256 if args.wide else 64)
     except ValueError as e:
         sys.stderr.write("%s: %s\n" % (args.algo, e))
         return 1
@@ -312,14 +315,14 @@ def main_assignment(args, ap) -> int:
     try:
         with open(args.output[0], "w") as out:
             if args.algo == "assignment":
-                r = eng.assign_batch([prob])[0]
+                r = eng.assign_batch([prob], wide=args.wide)[0]
                 print("solution with cost: %d" % r.cost)
                 out.write("cost: %d\nassignment:\n" % r.cost)
                 for a, t in _pairs(agents, tasks, r.task_of):
                     print("%s: %s" % (a, t))
                     out.write("  %s: %s\n" % (a, t))
             else:
-                series = eng.assign_series([prob])[0]
+                series = eng.assign_series([prob], wide=args.wide)[0]
                 out.write("solutions:\n")
                 try:
                     count = 0
@@ -351,6 +354,8 @@ def main(argv: List[str] = None) -> int:
     for k in ("startX", "startY", "goalX", "goalY"):
         ap.add_argument("--" + k, type=int, help="a_star: %s" % k)
     ap.add_argument("--maxTaskAssignments", type=int, default=10 ** 9, help="cbs_ta, ecbs_ta: maximum number of task assignments to try")
+    ap.add_argument("--wide", action="store_true",
+                    help="assignment, next_best_assignment: the wide solver, at most 256 agents and 256 tasks (default: 64)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--max-ll-expansions", type=int, default=-1, help="harness cap per instance (reference: none)")
     args = ap.parse_args(argv)

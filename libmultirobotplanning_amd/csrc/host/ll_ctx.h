@@ -236,6 +236,8 @@ struct mrp_ll_ctx {
   std::vector<uint16_t> scanStates;
   mrp::host::AssignStaging assignStaging;  // mrp_ll_assign_batch / _series_*: the packed batch (kept for its capacity)
   std::vector<uint32_t> assignOut;         // ... and its result records
+  mrp::host::AssignStagingWide assignStagingWide;         // the same of mrp_ll_assign_batch_w
+  uint32_t assignLdsBudget = mrp::as::kLdsBudgetWide;     // LDS rows up to here, memory rows beyond (MRP_LL_ASSIGN_LDS_BYTES)
 };
 
 namespace {

@@ -44,6 +44,13 @@ struct AssignParams {
   uint32_t* out;              // the result records
   uint32_t n;
 };
+struct AssignWideParams {
+  const uint32_t* maps;
+  const as::AssignJobWide* jobs;  // [n]
+  const uint32_t* data;
+  uint32_t* out;                  // the result records, then the scratch regions of the gather problems with memory rows
+  uint32_t n;
+};
 
 }  // namespace mrp
 
@@ -68,4 +75,5 @@ hipError_t mrp_ll_launch_heur_bfs(const mrp::HeurParams* P, uint32_t ldsBytes, h
 hipError_t mrp_ll_launch_heur_lookup(const mrp::LookupParams* P, hipStream_t stream);
 // assign_kernel.hip
 hipError_t mrp_ll_launch_assign(const mrp::AssignParams* P, uint32_t ldsBytes, hipStream_t stream);
+hipError_t mrp_ll_launch_assign_wide(const mrp::AssignWideParams* P, uint32_t ldsBytes, hipStream_t stream);
 }

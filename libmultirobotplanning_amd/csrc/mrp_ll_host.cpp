@@ -82,6 +82,8 @@ int mrp_ll_create(const mrp_ll_options* optIn, mrp_ll_ctx** out) {
   ctx->env.arenaPathsBytes = 128 * 1024;
   if (const char* e = std::getenv("MRP_LL_ARENA_PATHS_BYTES"))  // tuning knob (tests: a path area too small for a root's table)
     ctx->env.arenaPathsBytes = static_cast<uint32_t>(std::min(std::max(std::atoi(e), 4096), 128 * 1024)) & ~255u;
+  if (const char* e = std::getenv("MRP_LL_ASSIGN_LDS_BYTES"))  // tuning knob (tests: a small wide problem on memory rows)
+    ctx->assignLdsBudget = static_cast<uint32_t>(std::min(std::max(std::atoi(e), 0), static_cast<int>(mrp::as::kLdsBudgetWide)));
   ctx->arenaScratchOff = static_cast<uint32_t>(mrp::slot::scratchOff(o.arena_nodes, o.max_horizon, ctx->arenaRowWords));
   const uint64_t stride = mrp::slot::stride(o.arena_nodes, o.max_horizon, ctx->arenaRowWords, ctx->env.arenaPathsBytes);
   ctx->arenaStride = stride;

@@ -78,6 +78,10 @@ class mrp_ll_assign_problem(ctypes.Structure):
                 ("starts_xy", I32P), ("allowed", U64P), ("forbidden", U64P), ("mode", I32P), ("min_matching", ctypes.c_int32)]
 
 
+class mrp_ll_assign_problem_w(ctypes.Structure):  # the wide form: allowed / forbidden are [n_agents][mask_words]
+    _fields_ = mrp_ll_assign_problem._fields_ + [("mask_words", ctypes.c_int32)]
+
+
 class mrp_ll_assign_result(ctypes.Structure):
     _fields_ = [("status", ctypes.c_int32), ("matched", ctypes.c_int32), ("cost", ctypes.c_int64), ("task_of", I32P)]
 
@@ -107,7 +111,7 @@ EXPORTS = ["mrp_ll_create", "mrp_ll_destroy", "mrp_ll_last_error", "mrp_ll_uploa
            "mrp_ll_compute_heuristics", "mrp_ll_read_heuristic", "mrp_ll_heuristic_lookup", "mrp_ll_submit_scan",
            "mrp_ll_constraint_store_reserve", "mrp_ll_submit_sets", "mrp_ll_session_front_tables",
            "mrp_ll_submit_node", "mrp_ll_assign_batch", "mrp_ll_assign_series_create", "mrp_ll_assign_series_next",
-           "mrp_ll_assign_series_destroy", "mrp_ll_ta_root_batch", "mrp_ll_ta_eps_root_batch",
+           "mrp_ll_assign_series_destroy", "mrp_ll_assign_batch_w", "mrp_ll_assign_series_create_w", "mrp_ll_ta_root_batch", "mrp_ll_ta_eps_root_batch",
            "mrp_ll_ta_eps_root_batch_stored"]
 
 _lib = None
@@ -205,6 +209,12 @@ def load_library(path: Optional[str] = None):
     lib.mrp_ll_assign_series_create.restype = ctypes.c_int
     lib.mrp_ll_assign_series_create.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(mrp_ll_assign_problem),
                                                 ctypes.POINTER(ctypes.c_void_p)]
+    lib.mrp_ll_assign_batch_w.restype = ctypes.c_int
+    lib.mrp_ll_assign_batch_w.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(mrp_ll_assign_problem_w),
+                                          ctypes.POINTER(mrp_ll_assign_result)]
+    lib.mrp_ll_assign_series_create_w.restype = ctypes.c_int
+    lib.mrp_ll_assign_series_create_w.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(mrp_ll_assign_problem_w),
+                                                  ctypes.POINTER(ctypes.c_void_p)]
     lib.mrp_ll_assign_series_next.restype = ctypes.c_int
     lib.mrp_ll_assign_series_next.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_void_p),
                                               ctypes.POINTER(mrp_ll_assign_result)]
@@ -638,11 +648,13 @@ class LowLevelEngine:
                                                       out.ctypes.data_as(I32P)), "mrp_ll_heuristic_lookup")
         return out[:len(ids)]
 
-    def _marshal_assign(self, problems):
+    def _marshal_assign(self, problems, wide=False):
         """dicts -> mrp_ll_assign_problem[].  Matrix form: cost ([nA][nT]; None or ASSIGN_NO_EDGE = no edge); gather form:
-        heuristic_ids [nT], starts [nA][2], allowed [nA] (optional).  Both: forbidden [nA], mode [nA], min_matching."""
+        heuristic_ids [nT], starts [nA][2], allowed [nA] (optional).  Both: forbidden [nA], mode [nA], min_matching.
+        wide: -> mrp_ll_assign_problem_w[]; a mask is a Python int of any width, marshalled to mask_words =
+        ceil(n_tasks / 64) words (at least one; its bits at or above 64 * mask_words are dropped)."""
         n = len(problems)
-        carr = (mrp_ll_assign_problem * max(n, 1))()
+        carr = ((mrp_ll_assign_problem_w if wide else mrp_ll_assign_problem) * max(n, 1))()
         keep, dims = [], []
 
         def arr(v, dtype, ptr, shape=-1):
@@ -651,6 +663,11 @@ class LowLevelEngine:
                 a = np.zeros(1, dtype=dtype)
             keep.append(a)
             return a.ctypes.data_as(ptr)
+
+        def masks(v, words):
+            if not wide:
+                return arr(v, np.uint64, U64P)
+            return arr([[(int(m) >> (64 * k)) & (2 ** 64 - 1) for k in range(words)] for m in v], np.uint64, U64P)
 
         for c, p in zip(carr, problems):
             cost = p.get("cost")
@@ -668,10 +685,13 @@ class LowLevelEngine:
                 c.n_agents, c.n_tasks = len(p["starts"]), len(p["heuristic_ids"])
                 c.heuristic_ids = arr(p["heuristic_ids"], np.int32, I32P)
                 c.starts_xy = arr(p["starts"], np.int32, I32P)
-                if p.get("allowed") is not None:
-                    c.allowed = arr(p["allowed"], np.uint64, U64P)
+            words = min(max((c.n_tasks + 63) // 64, 1), 4)
+            if wide:
+                c.mask_words = int(p.get("mask_words", words))  # (tests hand in a wrong one)
+            if cost is None and p.get("allowed") is not None:
+                c.allowed = masks(p["allowed"], words)
             if p.get("forbidden") is not None:
-                c.forbidden = arr(p["forbidden"], np.uint64, U64P)
+                c.forbidden = masks(p["forbidden"], words)
             if p.get("mode") is not None:
                 c.mode = arr(p["mode"], np.int32, I32P)
             c.min_matching = int(p.get("min_matching") or 0)
@@ -690,23 +710,32 @@ class LowLevelEngine:
     def _assign_unpack(cres, task_of, dims):
         return [AssignResult(r.status, r.matched, r.cost, t[:max(min(d, len(t)), 0)].tolist()) for r, t, d in zip(cres, task_of, dims)]
 
-    def assign_batch(self, problems: Sequence[dict]) -> List[AssignResult]:
+    def assign_batch(self, problems: Sequence[dict], wide: bool = False) -> List[AssignResult]:
         """mrp_ll_assign_batch: every problem's maximum-cardinality, minimum-cost matching, the whole batch in ONE launch.
-        A rejected problem comes back with status BAD_JOB; the others are unaffected."""
-        carr, keep, dims = self._marshal_assign(problems)
+        A rejected problem comes back with status BAD_JOB; the others are unaffected.  wide: mrp_ll_assign_batch_w, up to
+        256 agents x 256 tasks per problem (narrow: 64 x 64), masks as Python ints of any width."""
+        carr, keep, dims = self._marshal_assign(problems, wide)
         cres, task_of = self._assign_results(dims)
-        self._check(self._lib.mrp_ll_assign_batch(self._h, len(problems), carr, cres), "mrp_ll_assign_batch")
+        if wide:
+            self._check(self._lib.mrp_ll_assign_batch_w(self._h, len(problems), carr, cres), "mrp_ll_assign_batch_w")
+        else:
+            self._check(self._lib.mrp_ll_assign_batch(self._h, len(problems), carr, cres), "mrp_ll_assign_batch")
         return self._assign_unpack(cres, task_of, dims)
 
-    def assign_series(self, problems: Sequence[dict]) -> List[AssignmentSeries]:
-        """mrp_ll_assign_series_create: one next-best series per (unconstrained) problem; the optima in ONE launch."""
-        carr, keep, dims = self._marshal_assign(problems)
+    def assign_series(self, problems: Sequence[dict], wide: bool = False) -> List[AssignmentSeries]:
+        """mrp_ll_assign_series_create: one next-best series per (unconstrained) problem; the optima in ONE launch.
+        wide: mrp_ll_assign_series_create_w (up to 256 x 256)."""
+        carr, keep, dims = self._marshal_assign(problems, wide)
         hs = (ctypes.c_void_p * max(len(problems), 1))()
-        self._check(self._lib.mrp_ll_assign_series_create(self._h, len(problems), carr, hs), "mrp_ll_assign_series_create")
+        if wide:
+            self._check(self._lib.mrp_ll_assign_series_create_w(self._h, len(problems), carr, hs), "mrp_ll_assign_series_create_w")
+        else:
+            self._check(self._lib.mrp_ll_assign_series_create(self._h, len(problems), carr, hs), "mrp_ll_assign_series_create")
         return [AssignmentSeries(self, hs[k], dims[k]) for k in range(len(problems))]
 
     def assign_series_next(self, series: Sequence[AssignmentSeries]) -> List[AssignResult]:
-        """mrp_ll_assign_series_next: the next matching of each series; all children of all pops in ONE launch."""
+        """mrp_ll_assign_series_next: the next matching of each series; all children of all pops in ONE launch — narrow and
+        wide series may be mixed, then the narrow children take one launch and the wide children another."""
         dims = [s.n_agents for s in series]
         hs = (ctypes.c_void_p * max(len(series), 1))(*[s._h for s in series])
         cres, task_of = self._assign_results(dims)
