@@ -196,10 +196,13 @@ int mrp_hl_ct_deliver_rows(mrp_hl_ct* ct, const int32_t* gathered, int32_t world
  * first gets its new root — which takes `id`, advanced only when every agent got a path, and is pushed BEFORE the two
  * children; the expansions of a failed root count.  Conflicts are Environment::getFirstConflict's of cbs_ta.cpp:369-420, which
  * also looks at the time step at which the longest path ends (mrp_ll_conflict_scan does not: the driver adds that step).
+ * Instances within 64 agents x 64 tasks share ONE mrp_ll_assign_series_create, the others ONE mrp_ll_assign_series_create_w;
+ * all series advance in the round's one mrp_ll_assign_series_next.  With use_root_kernel = 1 the roots of at most 64 agents go
+ * through mrp_ll_ta_root_batch and the others through mrp_ll_ta_root_batch_w: at most two root calls per round.
  * The cost is the reference's; among assignments of equal cost the series' documented order (cost, then creation number)
  * stands in for Boost's accidental one, so WHICH of several optimal solutions comes back is this project's own choice.
- * Limits: at most 64 agents and 64 tasks per instance, assignment costs below 2^24 (the assignment calls'); beyond them the
- * instance ends MRP_HL_LL_ERROR, as it does when a search comes back with a capacity status other than the expansion cap. */
+ * Limits: at most 256 agents and 256 tasks (distinct potential goals) per instance, assignment costs below 2^24 (the wide
+ * assignment calls'); beyond them the instance ends MRP_HL_LL_ERROR, the other instances of the batch unaffected, as it does when a search comes back with a capacity status other than the expansion cap. */
 typedef struct mrp_hl_ta_instance {
   int32_t dimx, dimy;
   int32_t n_obstacles;
@@ -267,7 +270,8 @@ int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options* opt, int3
  *   - an empty focal list at an expansion (:238; the truncation can leave the top's cost above nextRootNodeCost) ends the
  *     instance MRP_HL_LL_ERROR.
  * Round-based over all instances; a round makes at most one mrp_ll_assign_series_next, one mrp_ll_ta_eps_root_batch for the
- * new roots and one mrp_ll_search_batch of MRP_LL_ASTAR_EPS_TA jobs: for every expanded node its two child searches with the
+ * new roots of at most 64 agents plus one mrp_ll_ta_eps_root_batch_w for the others (at most two root calls), and one
+ * mrp_ll_search_batch of MRP_LL_ASTAR_EPS_TA jobs: for every expanded node its two child searches with the
  * node's paths as the shipped focal context.  With options.use_root_kernel = 0 a root is n_agents dependent jobs of that
  * batch instead, one agent per round, each with the paths before it as its context, and the driver scans and counts
  * itself; the results are the same.  One expansion can take several rounds either way (children, then assignment and root).
@@ -277,7 +281,8 @@ int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options* opt, int3
  * every path in the engine's device-resident path store — the root call becomes mrp_ll_ta_eps_root_batch_stored, every job
  * carries MRP_LL_JOB_STORE_RESULT while a slot is free — and a job whose node has every other agent's path there names its
  * context by slot (mrp_ll_job.path_ids) instead of shipping it.  MRP_HL_TA_PATH_SLOTS=N: slots of that store (unset: four per
- * agent of the batch, between 256 and 65536; not tuned).
+ * agent of the batch, between 256 and 65536; not tuned).  Instances of more than 64 agents ignore the knob — their contexts
+ * ship and their roots go through the unstored call: a by-slot table of 256 agents does not fit a workgroup's path area.
  * w >= 1 (else MRP_LL_E_INVALID).  root_conflicts counts the expanded nodes with a conflict that carry the root flag (a
  * child is a copy of its parent, flag included). */
 int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_ta_options* opt, int32_t n_instances,

@@ -713,7 +713,7 @@ int mrp_ll_submit_node(mrp_ll_ctx* ctx, int32_t tag, int32_t n_jobs, const mrp_l
  * with larger tables come back MRP_LL_BAD_JOB (path_ids tables, root chains) or are read from host memory (shipped tables)
  * that a default context serves from the slot.  Results never depend on it; it exists for tests and measurements. */
 typedef struct mrp_ll_ta_root {
-  int32_t map_id, n_agents;        /* 1 .. 64 (the assignment's limit) */
+  int32_t map_id, n_agents;        /* 1 .. 64 (the narrow assignment's limit); the _w calls: 1 .. 256 */
   const int32_t* starts_xy;        /* [n_agents][2] */
   const int32_t* goals_xy;         /* [n_agents][2]; ignored where heuristic_ids[a] < 0 */
   const int32_t* heuristic_ids;    /* [n_agents]; < 0: the agent has no task (MRP_LL_JOB_NO_GOAL) */
@@ -753,6 +753,22 @@ int mrp_ll_ta_eps_root_batch(mrp_ll_ctx* ctx, float w, int32_t n_roots, const mr
 int mrp_ll_ta_eps_root_batch_stored(mrp_ll_ctx* ctx, float w, int32_t n_roots, const mrp_ll_ta_root* roots,
                                     mrp_ll_conflict* conflicts /* [n_roots] */, int32_t* planned /* [n_roots] */,
                                     const int32_t* const* result_path_ids /* [n_roots] -> [n_agents]; NULL = none */);
+
+/* ---- the same roots with up to 256 agents -------------------------------------------------------------------------
+ * mrp_ll_ta_root_batch_w and mrp_ll_ta_eps_root_batch_w are mrp_ll_ta_root_batch and mrp_ll_ta_eps_root_batch for roots of
+ * 1 .. 256 agents (what mrp_ll_assign_series_create_w assigns): the same records, refusals (with 256 in place of 64), one
+ * budget per root, MRP_LL_NOT_RUN, planned, ten conflict words, return codes and MRP_LL_E_BUSY, word for word.  Still ONE
+ * workgroup per root and ONE launch per call, of kernels of their own (mrp_ll_ta_root_wide_kernel,
+ * mrp_ll_ta_eps_root_wide_kernel: each lane keeps four agents); the narrow calls and their kernels are unchanged and go on
+ * refusing 65 agents.  A root of at most 64 agents gets from a _w call exactly what the narrow call returns.
+ * The table of a root is  longest path x (n_agents rounded up to 16) x 2  bytes: 256 agents fill the default path area of
+ * 128 KiB at 256 time steps.  Beyond it the narrow calls' fall-backs apply unchanged: the CBS-TA call completes the scan with
+ * mrp_ll_conflict_scan, the ECBS-TA call plans the remaining agents as ordinary jobs with shipped contexts and scans.
+ * There is no path-store variant of the wide ECBS-TA call. */
+int mrp_ll_ta_root_batch_w(mrp_ll_ctx* ctx, int32_t n_roots, const mrp_ll_ta_root* roots, int32_t* planned /* [n_roots] */,
+                           mrp_ll_conflict* conflicts /* [n_roots] */);
+int mrp_ll_ta_eps_root_batch_w(mrp_ll_ctx* ctx, float w, int32_t n_roots, const mrp_ll_ta_root* roots,
+                               mrp_ll_conflict* conflicts /* [n_roots] */, int32_t* planned /* [n_roots] */);
 
 int mrp_ll_get_stats(const mrp_ll_ctx* ctx, mrp_ll_stats* out);
 int mrp_ll_reset_stats(mrp_ll_ctx* ctx);

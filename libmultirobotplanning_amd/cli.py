@@ -6,6 +6,7 @@
         agents[].{name,start,potentialGoals}; statistics also has numTaskAssignments, and a state's t is its cost so far)
     python -m libmultirobotplanning_amd.cli ecbs_ta -i in.yaml -o out.yaml -w 1.3 [--maxTaskAssignments N]
                                                                                    (example/ecbs_ta.cpp:587-695, as cbs_ta)
+        cbs_ta / ecbs_ta: at most 256 agents and 256 distinct potential goals; beyond that "Planning NOT successful!"
     python -m libmultirobotplanning_amd.cli sipp -i in.yaml -o out.yaml            (example/sipp.cpp:149-236)
     python -m libmultirobotplanning_amd.cli mapf_prioritized_sipp -i in.yaml -o out.yaml
                                                                                    (example/mapf_prioritized_sipp.cpp:157-295)
@@ -112,7 +113,7 @@ def read_ta_instance(path: str) -> Dict:
 def main_cbs_ta(args, ap) -> int:
     """cbs_ta -i in.yaml -o out.yaml [--maxTaskAssignments N]: the output of example/cbs_ta.cpp:589-614.
     ecbs_ta -i in.yaml -o out.yaml -w W [--maxTaskAssignments N]: the output of example/ecbs_ta.cpp:655-689, which has the
-    same form."""
+    same form.  Both take at most 256 agents and 256 distinct potential goals."""
     from . import hl
     if len(args.input) != len(args.output):
         ap.error("give one -o per -i")

@@ -112,7 +112,8 @@ struct Tree {
   int32_t nAgents = 0, mapId = -1;
   std::vector<int32_t> starts;           // [n][2]
   std::vector<int32_t> taskXY, taskHeur; // the distinct potential goals in order of first appearance; their tables
-  std::vector<uint64_t> allowed;         // per agent: the tasks it may take
+  int32_t maskWords = 1;                 // max(1, ceil(tasks / 64))
+  std::vector<uint64_t> allowed;         // [nAgents][maskWords] the tasks an agent may take, as mrp_ll_assign_problem_w's masks
   // the search
   int32_t status = kRunning;
   std::vector<Node> nodes;

@@ -1,15 +1,18 @@
 // mrp_hl_solve_ecbs_ta_batch (include/mrp_hl.h): ECBS with task assignment for a batch of instances, round-based.  The trees
 // are hl/ecbs_ta_tree.hpp's state machines; a round makes at most three engine calls over ALL instances:
 //   1. mrp_ll_assign_series_next   for the trees whose new-root test (or start) asks for an assignment
-//   2. mrp_ll_ta_eps_root_batch    for the new roots, one workgroup each (use_root_kernel = 0: a root is n dependent jobs of
-//                                  call 3, one agent per round, each with the paths of the agents before it as its shipped
-//                                  focal context, and the tree scans and counts itself)
+//   2. mrp_ll_ta_eps_root_batch    for the new roots of at most 64 agents, one workgroup each, and mrp_ll_ta_eps_root_batch_w
+//                                  for the others: at most two root calls (use_root_kernel = 0, or a wide root with an engine
+//                                  that has no wide root call: a root is n dependent jobs of call 3, one agent per round, each
+//                                  with the paths of the agents before it as its shipped focal context, and the tree scans
+//                                  and counts itself)
 //   3. mrp_ll_search_batch         MRP_LL_ASTAR_EPS_TA jobs: for every tree with an expanded node, its two child searches with
 //                                  the node's paths as the context
 // and then lets every tree run up to its next request.  The trees scan and count their children's conflicts themselves.
 // MRP_HL_TA_DEVICE_PATHS=1 (ta_batch_setup.hpp TaKnobs; off by default, same results): the engine's path store is reserved,
 // every search is told to leave its path in a slot of it (a root through mrp_ll_ta_eps_root_batch_stored), and a job whose
-// node has every other agent's path there goes out with path_ids instead of a shipped table.
+// node has every other agent's path there goes out with path_ids instead of a shipped table.  Instances of more than 64
+// agents ignore the knob: their contexts ship, their searches store nothing and their roots go through the unstored call.
 // A translation unit of its own, like csrc/hl/mrp_hl_ta.cpp.
 #include <chrono>
 #include <cstring>
@@ -62,8 +65,8 @@ struct Context {
       }
   }
   // The context of `agent`'s search can go by slot: some other agent has a path, and each of those paths is in the store.
-  // (The table the workgroup then builds always fits: 64 agents x kPathCap 512 states x 2 bytes = 64 KiB of the default
-  // engine's 128 KiB path area.)
+  // (Asked for trees of at most 64 agents only — the table the workgroup then builds fits: 64 agents x kPathCap 512 states
+  // x 2 bytes = 64 KiB of the default engine's 128 KiB path area.  256 agents x 512 states do not, so wider trees ship.)
   bool byId(int agent) const {
     bool any = false;
     for (size_t a = 0; a < len.size(); ++a) {
@@ -146,7 +149,7 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
   PathSlotsP slots;
   if (knobs.devicePaths) {
     int64_t agents = 0;
-    for (int32_t k = 0; k < n; ++k) agents += trees[k]->running() ? trees[k]->nAgents : 0;
+    for (int32_t k = 0; k < n; ++k) agents += trees[k]->running() && trees[k]->nAgents <= mrp_hl::ta::kNarrowLimit ? trees[k]->nAgents : 0;
     const int32_t nSlots = knobs.slotsFor(agents);
     rc = mrp_ll_path_store_reserve(eng.ctx, nSlots);
     if (rc != MRP_LL_SUCCESS) return rc;
@@ -179,12 +182,8 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
         who.push_back(k);
       }
       if (!ask.empty()) {
-        std::vector<mrp_ll_assign_result> res(ask.size());
-        std::vector<int32_t> taskOf(ask.size() * 64, -1);
-        for (size_t q = 0; q < ask.size(); ++q) {
-          std::memset(&res[q], 0, sizeof(res[q]));
-          res[q].task_of = taskOf.data() + q * 64;
-        }
+        std::vector<mrp_ll_assign_result> res;
+        const std::vector<int32_t> taskOf = mrp_hl::ta::taskOfBuffers(ask.size(), res);
         rc = mrp_ll_assign_series_next(eng.ctx, static_cast<int32_t>(ask.size()), ask.data(), res.data());
         if (rc != MRP_LL_SUCCESS) return rc;
         for (size_t q = 0; q < ask.size(); ++q)
@@ -196,26 +195,35 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
       if (opt.max_ll_expansions < 0) return -1;
       return opt.max_ll_expansions > t.llExpanded ? opt.max_ll_expansions - t.llExpanded : 0;
     };
-    std::vector<int32_t> rootOf, childOf;  // trees with a pending root / pending children
+    // trees with a pending root — first those whose root goes through a root call, then those planned as jobs, so that the
+    // jobs' results stand in one run with the children's — and trees with pending children
+    std::vector<int32_t> rootOf, rootAsJobs, childOf;
     for (int32_t k : live) {
       const Tree& t = *trees[k];
       if (!t.running()) continue;
-      if (t.wantRoot) rootOf.push_back(k);
+      if (t.wantRoot) {
+        const bool call = opt.use_root_kernel && (t.nAgents <= mrp_hl::ta::kNarrowLimit || &mrp_ll_ta_eps_root_batch_w != nullptr);
+        (call ? rootOf : rootAsJobs).push_back(k);
+      }
       if (t.wantChildren) childOf.push_back(k);
     }
-    // the results of the round: the roots' (n each through the root call, one each as jobs), then two per pair of children
+    const size_t nKernelRoots = rootOf.size();
+    rootOf.insert(rootOf.end(), rootAsJobs.begin(), rootAsJobs.end());
+    // the results of the round: the roots' (n each through a root call, one each as jobs), then two per pair of children
     std::vector<size_t> rootFirst(rootOf.size() + 1, 0);
     for (size_t q = 0; q < rootOf.size(); ++q)
-      rootFirst[q + 1] = rootFirst[q] + (opt.use_root_kernel ? static_cast<size_t>(trees[rootOf[q]]->nAgents) : 1u);
-    const size_t nRootResults = rootFirst[rootOf.size()], nRootJobs = opt.use_root_kernel ? 0u : rootOf.size();
+      rootFirst[q + 1] = rootFirst[q] + (q < nKernelRoots ? static_cast<size_t>(trees[rootOf[q]]->nAgents) : 1u);
+    const size_t nRootResults = rootFirst[rootOf.size()], nRootJobs = rootOf.size() - nKernelRoots;
     const size_t nResults = nRootResults + 2 * childOf.size(), nJobs = nRootJobs + 2 * childOf.size();
     pool.reserve(nResults);
     std::vector<mrp_ll_result> res(nResults + 1);
     for (size_t q = 0; q < nResults; ++q) pool.attach(res[q], q);
-    // the slot result q's search was told to leave its path in (-1: none); whoever turns the result into a path takes it
+    // the slot result q's search was told to leave its path in (-1: none); whoever turns the result into a path takes it.
+    // Only trees of at most 64 agents keep paths in the store (Context::byId).
     std::vector<int32_t> outSlot(nResults + 1, -1);
-    auto takeSlot = [&](size_t q) {
-      if (slots) outSlot[q] = slots->take();
+    auto stores = [&](const Tree& t) { return slots && t.nAgents <= mrp_hl::ta::kNarrowLimit; };
+    auto takeSlot = [&](const Tree& t, size_t q) {
+      if (stores(t)) outSlot[q] = slots->take();
       return outSlot[q];
     };
     auto pathFrom = [&](size_t q) {
@@ -232,10 +240,11 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
     std::vector<int32_t> planned(rootOf.size() + 1, 0);
     std::vector<mrp_ll_conflict> rootScan(rootOf.size() + 1);
     std::vector<std::vector<int32_t>> rootGoals(rootOf.size()), rootHeur(rootOf.size());
-    if (opt.use_root_kernel) {
-      // 2. the new roots, one workgroup each
-      std::vector<mrp_ll_ta_root> roots(rootOf.size() + 1);
-      for (size_t q = 0; q < rootOf.size(); ++q) {
+    if (nKernelRoots > 0) {
+      // 2. the new roots, one workgroup each: the narrow ones in one call, the wide ones in another
+      std::vector<mrp_ll_ta_root> roots[2];
+      std::vector<size_t> rootIs[2];
+      for (size_t q = 0; q < nKernelRoots; ++q) {
         const Tree& t = *trees[rootOf[q]];
         rootGoals[q].assign(static_cast<size_t>(2 * t.nAgents), 0);
         rootHeur[q].assign(static_cast<size_t>(t.nAgents), -1);
@@ -245,7 +254,8 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
             rootGoals[q][2 * a + 1] = t.taskXY[2 * t.rootTasks[a] + 1];
             rootHeur[q][a] = t.taskHeur[t.rootTasks[a]];
           }
-        mrp_ll_ta_root& r = roots[q];
+        mrp_ll_ta_root r;
+        std::memset(&r, 0, sizeof(r));
         r.map_id = t.mapId;
         r.n_agents = t.nAgents;
         r.starts_xy = t.starts.data();
@@ -253,28 +263,41 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
         r.heuristic_ids = rootHeur[q].data();
         r.max_expansions = budgetOf(t);
         r.results = res.data() + rootFirst[q];
+        const int wide = t.nAgents > mrp_hl::ta::kNarrowLimit ? 1 : 0;
+        roots[wide].push_back(r);
+        rootIs[wide].push_back(q);
       }
-      if (!rootOf.empty() && slots && &mrp_ll_ta_eps_root_batch_stored != nullptr) {
-        std::vector<std::vector<int32_t>> ids(rootOf.size());
-        std::vector<const int32_t*> idsOf(rootOf.size());
-        for (size_t q = 0; q < rootOf.size(); ++q) {
-          for (size_t a = 0; a < rootFirst[q + 1] - rootFirst[q]; ++a) ids[q].push_back(takeSlot(rootFirst[q] + a));
-          idsOf[q] = ids[q].data();
+      for (int wide = 0; wide < 2; ++wide) {
+        if (roots[wide].empty()) continue;
+        const int32_t m = static_cast<int32_t>(roots[wide].size());
+        std::vector<int32_t> plannedOf(roots[wide].size(), 0);
+        std::vector<mrp_ll_conflict> scanOf(roots[wide].size());
+        if (wide) {
+          rc = mrp_ll_ta_eps_root_batch_w(eng.ctx, w, m, roots[wide].data(), scanOf.data(), plannedOf.data());
+        } else if (slots && &mrp_ll_ta_eps_root_batch_stored != nullptr) {
+          std::vector<std::vector<int32_t>> ids(roots[wide].size());
+          std::vector<const int32_t*> idsOf(roots[wide].size());
+          for (size_t i = 0; i < rootIs[wide].size(); ++i) {
+            const size_t q = rootIs[wide][i];
+            for (size_t a = 0; a < rootFirst[q + 1] - rootFirst[q]; ++a) ids[i].push_back(takeSlot(*trees[rootOf[q]], rootFirst[q] + a));
+            idsOf[i] = ids[i].data();
+          }
+          rc = mrp_ll_ta_eps_root_batch_stored(eng.ctx, w, m, roots[wide].data(), scanOf.data(), plannedOf.data(), idsOf.data());
+        } else {
+          rc = mrp_ll_ta_eps_root_batch(eng.ctx, w, m, roots[wide].data(), scanOf.data(), plannedOf.data());
         }
-        rc = mrp_ll_ta_eps_root_batch_stored(eng.ctx, w, static_cast<int32_t>(rootOf.size()), roots.data(), rootScan.data(),
-                                             planned.data(), idsOf.data());
         if (rc != MRP_LL_SUCCESS) return rc;
-      } else if (!rootOf.empty()) {
-        rc = mrp_ll_ta_eps_root_batch(eng.ctx, w, static_cast<int32_t>(rootOf.size()), roots.data(), rootScan.data(), planned.data());
-        if (rc != MRP_LL_SUCCESS) return rc;
+        for (size_t i = 0; i < rootIs[wide].size(); ++i) {
+          planned[rootIs[wide][i]] = plannedOf[i];
+          rootScan[rootIs[wide][i]] = scanOf[i];
+        }
       }
-    } else {
-      for (size_t q = 0; q < rootOf.size(); ++q) {
-        const Tree& t = *trees[rootOf[q]];
-        ctx[q].of(t.rootPaths);
-        epsJob(jobs[q], t, t.rootAgent, t.rootTasks[t.rootAgent], nullptr, ctx[q], budgetOf(t), takeSlot(rootFirst[q]),
-               slots && ctx[q].byId(t.rootAgent));
-      }
+    }
+    for (size_t q = nKernelRoots; q < rootOf.size(); ++q) {
+      const Tree& t = *trees[rootOf[q]];
+      ctx[q].of(t.rootPaths);
+      epsJob(jobs[q - nKernelRoots], t, t.rootAgent, t.rootTasks[t.rootAgent], nullptr, ctx[q], budgetOf(t), takeSlot(t, rootFirst[q]),
+             stores(t) && ctx[q].byId(t.rootAgent));
     }
     // 3. the child searches (and, without the root call, the roots' next searches in front of them)
     for (size_t q = 0; q < childOf.size(); ++q) {
@@ -283,7 +306,7 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
       c.of(t.nodes[t.popped].sol);
       for (int s = 0; s < 2; ++s)
         epsJob(jobs[nRootJobs + 2 * q + s], t, t.childAgent[s], t.nodes[t.popped].taskOf[t.childAgent[s]], t.childCons[s].get(), c,
-               budgetOf(t), takeSlot(nRootResults + 2 * q + s), slots && c.byId(t.childAgent[s]));
+               budgetOf(t), takeSlot(t, nRootResults + 2 * q + s), stores(t) && c.byId(t.childAgent[s]));
     }
     if (!jobs.empty()) {
       rc = mrp_ll_search_batch(eng.ctx, static_cast<int32_t>(jobs.size()), jobs.data(), res.data() + (nRootResults - nRootJobs));
@@ -291,7 +314,7 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
     }
     for (size_t q = 0; q < rootOf.size(); ++q) {
       Tree& t = *trees[rootOf[q]];
-      if (!opt.use_root_kernel) {
+      if (q >= nKernelRoots) {
         const mrp_ll_result& r = res[rootFirst[q]];
         t.nSearches += 1;
         t.nRootSearches += 1;

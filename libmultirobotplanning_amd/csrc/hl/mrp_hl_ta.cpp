@@ -1,7 +1,9 @@
 // mrp_hl_solve_cbs_ta_batch (include/mrp_hl.h): CBS with task assignment for a batch of instances, round-based.  The trees are
 // hl/cbs_ta_tree.hpp's state machines (speculation width 1); a round makes three engine calls over ALL instances:
 //   1. mrp_ll_assign_series_next  for the trees that need a root (one launch for all their series' children)
-//   2. mrp_ll_ta_root_batch       for the new roots (use_root_kernel = 0: their n searches join call 3, the tree scans itself)
+//   2. mrp_ll_ta_root_batch       for the new roots of at most 64 agents and mrp_ll_ta_root_batch_w for the others: at most
+//                                 two root calls (use_root_kernel = 0, or a wide root with an engine that has no wide root
+//                                 call: their n searches join call 3, the tree scans itself)
 //   3. mrp_ll_search_batch        for the child searches
 // and then lets every tree run up to its next request.  A translation unit of its own: csrc/hl/mrp_hl.cpp neither includes nor
 // calls it, so the drivers there still link against engines that have no table, assignment or root calls.
@@ -110,12 +112,8 @@ extern "C" int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options
         who.push_back(k);
       }
       if (!ask.empty()) {
-        std::vector<mrp_ll_assign_result> res(ask.size());
-        std::vector<int32_t> taskOf(ask.size() * 64, -1);
-        for (size_t q = 0; q < ask.size(); ++q) {
-          std::memset(&res[q], 0, sizeof(res[q]));
-          res[q].task_of = taskOf.data() + q * 64;
-        }
+        std::vector<mrp_ll_assign_result> res;
+        const std::vector<int32_t> taskOf = mrp_hl::ta::taskOfBuffers(ask.size(), res);
         rc = mrp_ll_assign_series_next(eng.ctx, static_cast<int32_t>(ask.size()), ask.data(), res.data());
         if (rc != MRP_LL_SUCCESS) return rc;
         for (size_t q = 0; q < ask.size(); ++q)
@@ -127,17 +125,23 @@ extern "C" int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options
       if (opt.max_ll_expansions < 0) return -1;
       return opt.max_ll_expansions > t.llExpanded ? opt.max_ll_expansions - t.llExpanded : 0;
     };
-    std::vector<int32_t> rootOf, childOf;  // trees with a pending root / pending children
-    size_t nRootSearches = 0;
+    // trees with a pending root — first those whose root goes through a root call, then those planned as ordinary jobs, so
+    // that the jobs' results stand in one run with the children's — and trees with pending children
+    std::vector<int32_t> rootOf, rootAsJobs, childOf;
+    size_t nRootSearches = 0, nKernelSearches = 0;
     for (int32_t k : live) {
       Tree& t = *trees[k];
       if (!t.running()) continue;
       if (t.wantRoot) {
-        rootOf.push_back(k);
+        const bool call = opt.use_root_kernel && (t.nAgents <= mrp_hl::ta::kNarrowLimit || &mrp_ll_ta_root_batch_w != nullptr);
+        (call ? rootOf : rootAsJobs).push_back(k);
         nRootSearches += static_cast<size_t>(t.nAgents);
+        if (call) nKernelSearches += static_cast<size_t>(t.nAgents);
       }
       if (t.wantChildren) childOf.push_back(k);
     }
+    const size_t nKernelRoots = rootOf.size();
+    rootOf.insert(rootOf.end(), rootAsJobs.begin(), rootAsJobs.end());
     const size_t nResults = nRootSearches + 2 * childOf.size();
     pool.reserve(nResults);
     std::vector<mrp_ll_result> res(nResults + 1);
@@ -154,10 +158,11 @@ extern "C" int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options
     std::vector<mrp_ll_conflict> rootConf(rootOf.size() + 1);
     std::vector<mrp_ll_job> jobs;
     std::vector<std::vector<int32_t>> rootGoals(rootOf.size()), rootHeur(rootOf.size());
-    if (opt.use_root_kernel) {
-      // 2. the new roots, one workgroup each
-      std::vector<mrp_ll_ta_root> roots(rootOf.size() + 1);
-      for (size_t q = 0; q < rootOf.size(); ++q) {
+    if (nKernelRoots > 0) {
+      // 2. the new roots, one workgroup each: the narrow ones in one call, the wide ones in another
+      std::vector<mrp_ll_ta_root> roots[2];
+      std::vector<size_t> rootIs[2];
+      for (size_t q = 0; q < nKernelRoots; ++q) {
         const Tree& t = *trees[rootOf[q]];
         rootGoals[q].assign(static_cast<size_t>(2 * t.nAgents), 0);
         rootHeur[q].assign(static_cast<size_t>(t.nAgents), -1);
@@ -167,7 +172,8 @@ extern "C" int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options
             rootGoals[q][2 * a + 1] = t.taskXY[2 * t.rootTasks[a] + 1];
             rootHeur[q][a] = t.taskHeur[t.rootTasks[a]];
           }
-        mrp_ll_ta_root& r = roots[q];
+        mrp_ll_ta_root r;
+        std::memset(&r, 0, sizeof(r));
         r.map_id = t.mapId;
         r.n_agents = t.nAgents;
         r.starts_xy = t.starts.data();
@@ -175,18 +181,29 @@ extern "C" int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options
         r.heuristic_ids = rootHeur[q].data();
         r.max_expansions = budgetOf(t);
         r.results = res.data() + rootFirst[q];
+        const int wide = t.nAgents > mrp_hl::ta::kNarrowLimit ? 1 : 0;
+        roots[wide].push_back(r);
+        rootIs[wide].push_back(q);
       }
-      if (!rootOf.empty()) {
-        rc = mrp_ll_ta_root_batch(eng.ctx, static_cast<int32_t>(rootOf.size()), roots.data(), planned.data(), rootConf.data());
+      for (int wide = 0; wide < 2; ++wide) {
+        if (roots[wide].empty()) continue;
+        const int32_t m = static_cast<int32_t>(roots[wide].size());
+        std::vector<int32_t> plannedOf(roots[wide].size(), 0);
+        std::vector<mrp_ll_conflict> confOf(roots[wide].size());
+        rc = wide ? mrp_ll_ta_root_batch_w(eng.ctx, m, roots[wide].data(), plannedOf.data(), confOf.data())
+                  : mrp_ll_ta_root_batch(eng.ctx, m, roots[wide].data(), plannedOf.data(), confOf.data());
         if (rc != MRP_LL_SUCCESS) return rc;
-      }
-    } else {
-      for (size_t q = 0; q < rootOf.size(); ++q) {
-        const Tree& t = *trees[rootOf[q]];
-        for (int a = 0; a < t.nAgents; ++a) {
-          jobs.emplace_back();
-          taskJob(jobs.back(), t, a, t.rootTasks[a], nullptr, budgetOf(t));
+        for (size_t i = 0; i < rootIs[wide].size(); ++i) {
+          planned[rootIs[wide][i]] = plannedOf[i];
+          rootConf[rootIs[wide][i]] = confOf[i];
         }
+      }
+    }
+    for (size_t q = nKernelRoots; q < rootOf.size(); ++q) {
+      const Tree& t = *trees[rootOf[q]];
+      for (int a = 0; a < t.nAgents; ++a) {
+        jobs.emplace_back();
+        taskJob(jobs.back(), t, a, t.rootTasks[a], nullptr, budgetOf(t));
       }
     }
     // 3. the child searches (and, without the root kernel, the roots' searches in front of them)
@@ -198,19 +215,19 @@ extern "C" int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options
       }
     }
     if (!jobs.empty()) {
-      mrp_ll_result* out = opt.use_root_kernel ? res.data() + nRootSearches : res.data();
-      rc = mrp_ll_search_batch(eng.ctx, static_cast<int32_t>(jobs.size()), jobs.data(), out);
+      rc = mrp_ll_search_batch(eng.ctx, static_cast<int32_t>(jobs.size()), jobs.data(), res.data() + nKernelSearches);
       if (rc != MRP_LL_SUCCESS) return rc;
     }
     // the roots first: a new root is pushed BEFORE the two children (cbs_ta.hpp:165-168 in front of :179-210)
     for (size_t q = 0; q < rootOf.size(); ++q) {
       Tree& t = *trees[rootOf[q]];
       std::vector<PathP> paths(static_cast<size_t>(t.nAgents));
+      const bool viaCall = q < nKernelRoots;
       int done = 0;
       bool all = true;
       for (int a = 0; a < t.nAgents && t.running(); ++a) {
         const mrp_ll_result& r = res[rootFirst[q] + a];
-        if (opt.use_root_kernel && a >= planned[q]) break;
+        if (viaCall && a >= planned[q]) break;
         done += 1;
         t.nSearches += 1;
         t.nRootSearches += 1;
@@ -225,7 +242,7 @@ extern "C" int mrp_hl_solve_cbs_ta_batch(int32_t device, const mrp_hl_ta_options
       if (!t.running()) continue;
       Conflict c;
       if (all && done == t.nAgents)
-        c = opt.use_root_kernel ? mrp_hl::ta::conflictFromScan(rootConf[q], paths) : mrp_hl::ta::firstConflict(paths);
+        c = viaCall ? mrp_hl::ta::conflictFromScan(rootConf[q], paths) : mrp_hl::ta::firstConflict(paths);
       t.gotRoot(paths, done, c);
     }
     for (size_t q = 0; q < childOf.size(); ++q) {

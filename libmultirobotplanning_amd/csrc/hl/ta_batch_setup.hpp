@@ -11,6 +11,15 @@
 #include "../../../include/mrp_hl.h"
 #include "cbs_ta_tree.hpp"
 
+// The engine's wide entry points (up to 256 agents and tasks).  Weak references, as mrp_hl_ecbs_ta.cpp's to the stored root
+// call: an engine library without them still loads; an instance beyond 64 agents or tasks then ends MRP_HL_LL_ERROR, and a
+// wide root without a wide root call is planned as ordinary jobs.
+extern "C" int mrp_ll_assign_series_create_w(mrp_ll_ctx*, int32_t, const mrp_ll_assign_problem_w*, mrp_ll_assign_series**)
+    __attribute__((weak));
+extern "C" int mrp_ll_ta_root_batch_w(mrp_ll_ctx*, int32_t, const mrp_ll_ta_root*, int32_t*, mrp_ll_conflict*) __attribute__((weak));
+extern "C" int mrp_ll_ta_eps_root_batch_w(mrp_ll_ctx*, float, int32_t, const mrp_ll_ta_root*, mrp_ll_conflict*, int32_t*)
+    __attribute__((weak));
+
 namespace mrp_hl {
 namespace ta {
 
@@ -114,12 +123,18 @@ struct Engine {
   }
 };
 
-// Fills trees[k] (TreeT: ta::Tree or ecbs_ta::Tree) from inst[k]; an instance beyond the limits ends MRP_HL_LL_ERROR.
-// Returns MRP_LL_SUCCESS or the engine's error.
+constexpr int32_t kNarrowLimit = 64;   // agents and tasks of mrp_ll_assign_series_create and of the narrow root calls
+constexpr int32_t kWideLimit = 256;    // ... of mrp_ll_assign_series_create_w and of the _w root calls
+
+// Fills trees[k] (TreeT: ta::Tree or ecbs_ta::Tree) from inst[k]; an instance beyond the limits — 256 agents or 256 distinct
+// potential goals, 64 of each with an engine that has no mrp_ll_assign_series_create_w — ends MRP_HL_LL_ERROR.
+// The instances within 64 x 64 share ONE mrp_ll_assign_series_create, the others ONE mrp_ll_assign_series_create_w, which is
+// called only when there are such instances.  Returns MRP_LL_SUCCESS or the engine's error.
 template <typename TreeT>
 int setUpBatch(Engine& eng, int32_t n, const mrp_hl_ta_instance* inst, std::vector<std::unique_ptr<TreeT>>& trees) {
   typedef TreeT Tree;
   int rc = MRP_LL_SUCCESS;
+  const int32_t limit = &mrp_ll_assign_series_create_w != nullptr ? kWideLimit : kNarrowLimit;
   // ---- the instances: maps, tasks, one launch for all tables, one for all optima
   trees.clear();
   trees.resize(static_cast<size_t>(n));
@@ -129,16 +144,16 @@ int setUpBatch(Engine& eng, int32_t n, const mrp_hl_ta_instance* inst, std::vect
     trees[k].reset(new Tree());
     Tree& t = *trees[k];
     t.nAgents = I.n_agents;
-    if (I.n_agents < 1 || I.n_agents > 64 || !I.starts_xy || !I.goal_first || (I.goal_first[I.n_agents] > 0 && !I.goals_xy) ||
+    if (I.n_agents < 1 || I.n_agents > limit || !I.starts_xy || !I.goal_first || (I.goal_first[I.n_agents] > 0 && !I.goals_xy) ||
         mrp_ll_upload_map(eng.ctx, I.dimx, I.dimy, I.n_obstacles, I.obstacles_xy, &t.mapId) != MRP_LL_SUCCESS) {
-      t.nAgents = I.n_agents > 0 && I.n_agents <= 64 ? I.n_agents : 0;
+      t.nAgents = I.n_agents > 0 && I.n_agents <= limit ? I.n_agents : 0;
       t.end(MRP_HL_LL_ERROR);
       continue;
     }
     t.starts.assign(I.starts_xy, I.starts_xy + 2 * I.n_agents);
-    t.allowed.assign(static_cast<size_t>(I.n_agents), 0);
+    std::vector<std::vector<int32_t>> tasksOf(static_cast<size_t>(I.n_agents));  // per agent: the tasks it may take
     bool tooMany = false;
-    for (int a = 0; a < I.n_agents; ++a) {
+    for (int a = 0; a < I.n_agents && !tooMany; ++a) {
       if (t.starts[2 * a] < 0 || t.starts[2 * a] >= I.dimx || t.starts[2 * a + 1] < 0 || t.starts[2 * a + 1] >= I.dimy) tooMany = true;
       for (int q = I.goal_first[a]; q < I.goal_first[a + 1]; ++q) {
         const int32_t gx = I.goals_xy[2 * q], gy = I.goals_xy[2 * q + 1];
@@ -146,17 +161,22 @@ int setUpBatch(Engine& eng, int32_t n, const mrp_hl_ta_instance* inst, std::vect
         size_t task = 0;
         while (task < t.taskXY.size() / 2 && !(t.taskXY[2 * task] == gx && t.taskXY[2 * task + 1] == gy)) ++task;
         if (task == t.taskXY.size() / 2) t.taskXY.insert(t.taskXY.end(), {gx, gy});
-        if (task >= 64) {
+        if (task >= static_cast<size_t>(limit)) {
           tooMany = true;
           break;
         }
-        t.allowed[a] |= 1ull << task;
+        tasksOf[a].push_back(static_cast<int32_t>(task));
       }
     }
     if (tooMany) {
       t.end(MRP_HL_LL_ERROR);
       continue;
     }
+    // the masks as mrp_ll_assign_problem_w lays them out: bit task % 64 of the agent's word task / 64
+    t.maskWords = std::max<int32_t>(1, static_cast<int32_t>((t.taskXY.size() / 2 + 63) / 64));
+    t.allowed.assign(static_cast<size_t>(I.n_agents) * t.maskWords, 0);
+    for (int a = 0; a < I.n_agents; ++a)
+      for (int32_t task : tasksOf[a]) t.allowed[static_cast<size_t>(a) * t.maskWords + task / 64] |= 1ull << (task % 64);
     for (size_t task = 0; task < t.taskXY.size() / 2; ++task) {
       tabMap.push_back(t.mapId);
       tabGoal.insert(tabGoal.end(), {t.taskXY[2 * task], t.taskXY[2 * task + 1]});
@@ -167,30 +187,61 @@ int setUpBatch(Engine& eng, int32_t n, const mrp_hl_ta_instance* inst, std::vect
   if (rc != MRP_LL_SUCCESS) return rc;
   {
     std::vector<mrp_ll_assign_problem> probs;
-    std::vector<int32_t> treeOf;
+    std::vector<mrp_ll_assign_problem_w> probsWide;
+    std::vector<int32_t> treeOf, treeOfWide;
     size_t next = 0;
     for (int32_t k = 0; k < n; ++k) {
       Tree& t = *trees[k];
       if (!t.running()) continue;
       t.taskHeur.assign(tabIds.begin() + next, tabIds.begin() + next + t.taskXY.size() / 2);
       next += t.taskXY.size() / 2;
-      mrp_ll_assign_problem p;
-      std::memset(&p, 0, sizeof(p));
-      p.n_agents = t.nAgents;
-      p.n_tasks = static_cast<int32_t>(t.taskHeur.size());
-      p.heuristic_ids = t.taskHeur.data();
-      p.starts_xy = t.starts.data();
-      p.allowed = t.allowed.data();
-      probs.push_back(p);
-      treeOf.push_back(k);
+      if (t.nAgents <= kNarrowLimit && t.taskHeur.size() <= static_cast<size_t>(kNarrowLimit)) {  // (one mask word)
+        mrp_ll_assign_problem p;
+        std::memset(&p, 0, sizeof(p));
+        p.n_agents = t.nAgents;
+        p.n_tasks = static_cast<int32_t>(t.taskHeur.size());
+        p.heuristic_ids = t.taskHeur.data();
+        p.starts_xy = t.starts.data();
+        p.allowed = t.allowed.data();
+        probs.push_back(p);
+        treeOf.push_back(k);
+      } else {
+        mrp_ll_assign_problem_w p;
+        std::memset(&p, 0, sizeof(p));
+        p.n_agents = t.nAgents;
+        p.n_tasks = static_cast<int32_t>(t.taskHeur.size());
+        p.heuristic_ids = t.taskHeur.data();
+        p.starts_xy = t.starts.data();
+        p.allowed = t.allowed.data();
+        p.mask_words = t.maskWords;
+        probsWide.push_back(p);
+        treeOfWide.push_back(k);
+      }
     }
     eng.series.assign(static_cast<size_t>(n), nullptr);
     std::vector<mrp_ll_assign_series*> made(probs.size() + 1, nullptr);
     rc = mrp_ll_assign_series_create(eng.ctx, static_cast<int32_t>(probs.size()), probs.data(), made.data());
     if (rc != MRP_LL_SUCCESS) return rc;
     for (size_t q = 0; q < treeOf.size(); ++q) eng.series[treeOf[q]] = made[q];
+    if (!probsWide.empty()) {  // (only with an engine that has the call: `limit` above)
+      std::vector<mrp_ll_assign_series*> madeWide(probsWide.size() + 1, nullptr);
+      rc = mrp_ll_assign_series_create_w(eng.ctx, static_cast<int32_t>(probsWide.size()), probsWide.data(), madeWide.data());
+      for (size_t q = 0; q < treeOfWide.size(); ++q) eng.series[treeOfWide[q]] = madeWide[q];  // (the Engine destroys what was made)
+      if (rc != MRP_LL_SUCCESS) return rc;
+    }
   }
   return MRP_LL_SUCCESS;
+}
+
+// The caller-side task_of buffers of one mrp_ll_assign_series_next over `count` series: a stride that holds any instance.
+inline std::vector<int32_t> taskOfBuffers(size_t count, std::vector<mrp_ll_assign_result>& res) {
+  std::vector<int32_t> taskOf(count * static_cast<size_t>(kWideLimit), -1);
+  res.resize(count);
+  for (size_t q = 0; q < count; ++q) {
+    std::memset(&res[q], 0, sizeof(res[q]));
+    res[q].task_of = taskOf.data() + q * static_cast<size_t>(kWideLimit);
+  }
+  return taskOf;
 }
 
 }  // namespace ta

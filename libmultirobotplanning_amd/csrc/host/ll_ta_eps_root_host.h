@@ -5,6 +5,8 @@
 // reach as ordinary MRP_LL_ASTAR_EPS_TA jobs with shipped contexts, one after the other, and the scan by mrp_ll_conflict_scan.
 // mrp_ll_ta_eps_root_batch_stored: the agents' paths also go to the path-store slots the caller names, from the kernel
 // (a run of slot words behind the agent words) and from the jobs run here (MRP_LL_JOB_STORE_RESULT) alike.
+// mrp_ll_ta_eps_root_batch_w: roots of up to 256 agents through mrp_ll_ta_eps_root_wide_kernel (ll_ta_root_wide.h), nothing
+// stored; the jobs that finish an outgrown root ship contexts of any width (ll_pack.h), so that path is the narrow call's.
 #pragma once
 #include "ll_batch.h"
 #include "ll_ctx.h"
@@ -87,7 +89,7 @@ int taEpsRootRest(mrp_ll_ctx* ctx, float w, const mrp_ll_ta_root& R, const int32
 }
 
 int taEpsRootLaunch(mrp_ll_ctx* ctx, float w, int32_t n, const mrp_ll_ta_root* roots, int32_t* planned, mrp_ll_conflict* conflicts,
-                    const int32_t* const* storeIds) {
+                    const int32_t* const* storeIds, bool wide) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int rc = syncMaps(ctx);
   if (rc != MRP_LL_SUCCESS) return rc;
@@ -96,7 +98,7 @@ int taEpsRootLaunch(mrp_ll_ctx* ctx, float w, int32_t n, const mrp_ll_ta_root* r
   Ticket& t = ctx->tickets[0];  // idle: no session, no batch in flight
   auto packT0 = std::chrono::steady_clock::now();
   mrp::host::TaRootStaging st;
-  mrp::host::packTaEpsRoots(ctx->env, w, n, roots, 0, st, storeIds);
+  mrp::host::packTaEpsRoots(ctx->env, w, n, roots, 0, st, storeIds, wide ? mrp::kTaRootWideMaxAgents : mrp::kTaRootMaxAgents);
   const uint32_t outStride = static_cast<uint32_t>(ctx->env.maxHorizon) + mrp::kScanOutHalfs;
   const uint32_t nDev = static_cast<uint32_t>(st.recs.size());
   std::vector<int32_t> needScan, needRest;
@@ -133,7 +135,7 @@ int taEpsRootLaunch(mrp_ll_ctx* ctx, float w, int32_t n, const mrp_ll_ta_root* r
   if (rc != MRP_LL_SUCCESS) return rc;
   const uint32_t grid = std::min<uint32_t>(nDev, static_cast<uint32_t>(ctx->opt.slots));
   HIPCHK(ctx, hipEventRecord(t.evK0, t.stream));
-  HIPCHK(ctx, mrp_ll_launch_ta_eps_root(&P, grid, ldsBytes, t.stream));
+  HIPCHK(ctx, mrp_ll_launch_ta_eps_root(&P, grid, ldsBytes, wide ? 1 : 0, t.stream));
   HIPCHK(ctx, hipEventRecord(t.evK1, t.stream));
   HIPCHK(ctx, hipEventSynchronize(t.evK1));
   ctx->stats.launches += 1;
@@ -183,12 +185,9 @@ int taEpsRootLaunch(mrp_ll_ctx* ctx, float w, int32_t n, const mrp_ll_ta_root* r
   return MRP_LL_SUCCESS;
 }
 
-}  // namespace
-
-extern "C" {
-
-int mrp_ll_ta_eps_root_batch_stored(mrp_ll_ctx* ctx, float w, int32_t nRoots, const mrp_ll_ta_root* roots, mrp_ll_conflict* conflicts,
-                                    int32_t* planned, const int32_t* const* resultPathIds) {
+// wide: roots of up to 256 agents, resultPathIds == nullptr.
+int taEpsRootBatch(mrp_ll_ctx* ctx, float w, int32_t nRoots, const mrp_ll_ta_root* roots, mrp_ll_conflict* conflicts, int32_t* planned,
+                   const int32_t* const* resultPathIds, bool wide) {
   if (!ctx) return MRP_LL_E_INVALID;
   if (nRoots < 0 || !(w >= 1.0f) || (nRoots > 0 && (!roots || !planned || !conflicts))) {
     ctx->err = "mrp_ll_ta_eps_root_batch: invalid argument";
@@ -199,15 +198,31 @@ int mrp_ll_ta_eps_root_batch_stored(mrp_ll_ctx* ctx, float w, int32_t nRoots, co
     return MRP_LL_E_BUSY;
   }
   if (nRoots == 0) return MRP_LL_SUCCESS;
-  mrp::host::blankTaRootOutputs(ctx->env, nRoots, roots, planned, conflicts, resultPathIds);
-  const int rc = taEpsRootLaunch(ctx, w, nRoots, roots, planned, conflicts, resultPathIds);
-  if (rc != MRP_LL_SUCCESS) mrp::host::blankTaRootOutputs(ctx->env, nRoots, roots, planned, conflicts, resultPathIds);  // nothing half-told
+  const uint32_t maxAgents = wide ? mrp::kTaRootWideMaxAgents : mrp::kTaRootMaxAgents;
+  mrp::host::blankTaRootOutputs(ctx->env, nRoots, roots, planned, conflicts, resultPathIds, maxAgents);
+  const int rc = taEpsRootLaunch(ctx, w, nRoots, roots, planned, conflicts, resultPathIds, wide);
+  if (rc != MRP_LL_SUCCESS)
+    mrp::host::blankTaRootOutputs(ctx->env, nRoots, roots, planned, conflicts, resultPathIds, maxAgents);  // nothing half-told
   return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrp_ll_ta_eps_root_batch_stored(mrp_ll_ctx* ctx, float w, int32_t nRoots, const mrp_ll_ta_root* roots, mrp_ll_conflict* conflicts,
+                                    int32_t* planned, const int32_t* const* resultPathIds) {
+  return taEpsRootBatch(ctx, w, nRoots, roots, conflicts, planned, resultPathIds, false);
 }
 
 int mrp_ll_ta_eps_root_batch(mrp_ll_ctx* ctx, float w, int32_t nRoots, const mrp_ll_ta_root* roots, mrp_ll_conflict* conflicts,
                              int32_t* planned) {
-  return mrp_ll_ta_eps_root_batch_stored(ctx, w, nRoots, roots, conflicts, planned, nullptr);
+  return taEpsRootBatch(ctx, w, nRoots, roots, conflicts, planned, nullptr, false);
+}
+
+int mrp_ll_ta_eps_root_batch_w(mrp_ll_ctx* ctx, float w, int32_t nRoots, const mrp_ll_ta_root* roots, mrp_ll_conflict* conflicts,
+                               int32_t* planned) {
+  return taEpsRootBatch(ctx, w, nRoots, roots, conflicts, planned, nullptr, true);
 }
 
 }  // extern "C"

@@ -2,6 +2,7 @@
 // (ll_ta_root.h).  The packer of ta_root_pack.h, the first ticket's staging buffers and stream (the engine is idle), the
 // launch parameters of an ordinary MRP_LL_ASTAR_TA batch, unpackResult on the way back; the scan of a root whose table did
 // not fit its arena slot is completed with mrp_ll_conflict_scan.
+// mrp_ll_ta_root_batch_w: the same with roots of up to 256 agents and mrp_ll_ta_root_wide_kernel (ll_ta_root_wide.h).
 #pragma once
 #include "ll_batch.h"
 #include "ll_ctx.h"
@@ -11,7 +12,7 @@
 
 namespace {
 
-int taRootLaunch(mrp_ll_ctx* ctx, int32_t n, const mrp_ll_ta_root* roots, int32_t* planned, mrp_ll_conflict* conflicts) {
+int taRootLaunch(mrp_ll_ctx* ctx, int32_t n, const mrp_ll_ta_root* roots, int32_t* planned, mrp_ll_conflict* conflicts, bool wide) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   int rc = syncMaps(ctx);
   if (rc != MRP_LL_SUCCESS) return rc;
@@ -20,7 +21,7 @@ int taRootLaunch(mrp_ll_ctx* ctx, int32_t n, const mrp_ll_ta_root* roots, int32_
   Ticket& t = ctx->tickets[0];  // idle: no session, no batch in flight
   auto packT0 = std::chrono::steady_clock::now();
   mrp::host::TaRootStaging st;
-  mrp::host::packTaRoots(ctx->env, n, roots, 0, st);
+  mrp::host::packTaRoots(ctx->env, n, roots, 0, st, wide ? mrp::kTaRootWideMaxAgents : mrp::kTaRootMaxAgents);
   const uint32_t outStride = static_cast<uint32_t>(ctx->env.maxHorizon) + mrp::kScanOutHalfs;
   const uint32_t nDev = static_cast<uint32_t>(st.recs.size());
   std::vector<int32_t> needScan;
@@ -56,7 +57,7 @@ int taRootLaunch(mrp_ll_ctx* ctx, int32_t n, const mrp_ll_ta_root* roots, int32_
   if (rc != MRP_LL_SUCCESS) return rc;
   const uint32_t grid = std::min<uint32_t>(nDev, static_cast<uint32_t>(ctx->opt.slots));
   HIPCHK(ctx, hipEventRecord(t.evK0, t.stream));
-  HIPCHK(ctx, mrp_ll_launch_ta_root(&P, grid, ldsBytes, t.stream));
+  HIPCHK(ctx, mrp_ll_launch_ta_root(&P, grid, ldsBytes, wide ? 1 : 0, t.stream));
   HIPCHK(ctx, hipEventRecord(t.evK1, t.stream));
   HIPCHK(ctx, hipEventSynchronize(t.evK1));
   ctx->stats.launches += 1;
@@ -91,9 +92,9 @@ int taRootLaunch(mrp_ll_ctx* ctx, int32_t n, const mrp_ll_ta_root* roots, int32_
 
 }  // namespace
 
-extern "C" {
+namespace {
 
-int mrp_ll_ta_root_batch(mrp_ll_ctx* ctx, int32_t nRoots, const mrp_ll_ta_root* roots, int32_t* planned, mrp_ll_conflict* conflicts) {
+int taRootBatch(mrp_ll_ctx* ctx, int32_t nRoots, const mrp_ll_ta_root* roots, int32_t* planned, mrp_ll_conflict* conflicts, bool wide) {
   if (!ctx) return MRP_LL_E_INVALID;
   if (nRoots < 0 || (nRoots > 0 && (!roots || !planned || !conflicts))) {
     ctx->err = "mrp_ll_ta_root_batch: invalid argument";
@@ -104,10 +105,23 @@ int mrp_ll_ta_root_batch(mrp_ll_ctx* ctx, int32_t nRoots, const mrp_ll_ta_root* 
     return MRP_LL_E_BUSY;
   }
   if (nRoots == 0) return MRP_LL_SUCCESS;
-  mrp::host::blankTaRootOutputs(ctx->env, nRoots, roots, planned, conflicts);
-  const int rc = taRootLaunch(ctx, nRoots, roots, planned, conflicts);
-  if (rc != MRP_LL_SUCCESS) mrp::host::blankTaRootOutputs(ctx->env, nRoots, roots, planned, conflicts);  // nothing half-told
+  const uint32_t maxAgents = wide ? mrp::kTaRootWideMaxAgents : mrp::kTaRootMaxAgents;
+  mrp::host::blankTaRootOutputs(ctx->env, nRoots, roots, planned, conflicts, nullptr, maxAgents);
+  const int rc = taRootLaunch(ctx, nRoots, roots, planned, conflicts, wide);
+  if (rc != MRP_LL_SUCCESS) mrp::host::blankTaRootOutputs(ctx->env, nRoots, roots, planned, conflicts, nullptr, maxAgents);  // nothing half-told
   return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mrp_ll_ta_root_batch(mrp_ll_ctx* ctx, int32_t nRoots, const mrp_ll_ta_root* roots, int32_t* planned, mrp_ll_conflict* conflicts) {
+  return taRootBatch(ctx, nRoots, roots, planned, conflicts, false);
+}
+
+int mrp_ll_ta_root_batch_w(mrp_ll_ctx* ctx, int32_t nRoots, const mrp_ll_ta_root* roots, int32_t* planned, mrp_ll_conflict* conflicts) {
+  return taRootBatch(ctx, nRoots, roots, planned, conflicts, true);
 }
 
 }  // extern "C"

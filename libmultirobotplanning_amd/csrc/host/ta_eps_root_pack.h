@@ -10,8 +10,8 @@ namespace host {
 
 // storeIds (mrp_ll_ta_eps_root_batch_stored): where each agent's path also goes in the path store; nullptr: nowhere.
 static inline void packTaEpsRoots(const PackEnv& env, float w, int32_t n, const mrp_ll_ta_root* roots, uint32_t wordBase, TaRootStaging& st,
-                                  const int32_t* const* storeIds = nullptr) {
-  packTaRootsAs(env, MRP_LL_ASTAR_EPS_TA, w, n, roots, wordBase, st, storeIds);
+                                  const int32_t* const* storeIds = nullptr, uint32_t maxAgents = kTaRootMaxAgents) {
+  packTaRootsAs(env, MRP_LL_ASTAR_EPS_TA, w, n, roots, wordBase, st, storeIds, maxAgents);
 }
 
 // After the launch: unpackTaRoots, plus needRest: the roots the kernel left in front of agent planned[k] < n_agents with

@@ -25,12 +25,13 @@ struct TaRootStaging {
   uint32_t nResults = 0;               // results (DevResult + output area) of the launch
 };
 
-// What the call refuses (mrp_ll.h): a null array, n_agents outside 1 .. 64, an unknown map, a start outside the grid, a task
+// What the call refuses (mrp_ll.h): a null array, n_agents outside 1 .. maxAgents (64; kTaRootWideMaxAgents for the _w calls), an unknown map, a start outside the grid, a task
 // whose table is unknown or belongs to another map or whose goal lies outside the grid — every case in which packJob would
 // refuse the ordinary job of one of the agents.  storeIds (mrp_ll_ta_eps_root_batch_stored; nullptr: none): the path-store
 // slot of each agent's path, -1 = not stored; any other value outside the reserved store refuses the root.
-static inline bool taRootValid(const PackEnv& env, const mrp_ll_ta_root& r, const int32_t* storeIds = nullptr) {
-  if (r.n_agents < 1 || r.n_agents > static_cast<int32_t>(kTaRootMaxAgents)) return false;
+static inline bool taRootValid(const PackEnv& env, const mrp_ll_ta_root& r, const int32_t* storeIds = nullptr,
+                               uint32_t maxAgents = kTaRootMaxAgents) {
+  if (r.n_agents < 1 || r.n_agents > static_cast<int32_t>(maxAgents)) return false;
   if (!r.starts_xy || !r.goals_xy || !r.heuristic_ids || !r.results) return false;
   if (storeIds)
     for (int a = 0; a < r.n_agents; ++a)
@@ -51,9 +52,9 @@ static inline bool taRootValid(const PackEnv& env, const mrp_ll_ta_root& r, cons
 // wordBase: where st.words will stand in the launch's constraint-word buffer.  algo / w: MRP_LL_ASTAR_TA (w unused) for
 // mrp_ll_ta_root_batch, MRP_LL_ASTAR_EPS_TA and its weight for mrp_ll_ta_eps_root_batch (ll_device.h taEpsRootAgentJob).
 // storeIds: nullptr, or per root nullptr or its agents' path-store slots (taRootValid): st.slotWords, which the caller
-// copies behind st.words; a root without ids has no run there and keeps ec_off == vc_off.
+// copies behind st.words; a root without ids has no run there and keeps ec_off == vc_off.  maxAgents: taRootValid's.
 static inline void packTaRootsAs(const PackEnv& env, uint32_t algo, float w, int32_t n, const mrp_ll_ta_root* roots, uint32_t wordBase,
-                                 TaRootStaging& st, const int32_t* const* storeIds = nullptr) {
+                                 TaRootStaging& st, const int32_t* const* storeIds = nullptr, uint32_t maxAgents = kTaRootMaxAgents) {
   st.recs.clear();
   st.words.clear();
   st.slotWords.clear();
@@ -64,7 +65,7 @@ static inline void packTaRootsAs(const PackEnv& env, uint32_t algo, float w, int
   for (int32_t k = 0; k < n; ++k) {
     const mrp_ll_ta_root& r = roots[k];
     const int32_t* ids = storeIds ? storeIds[k] : nullptr;
-    if (!taRootValid(env, r, ids)) continue;
+    if (!taRootValid(env, r, ids, maxAgents)) continue;
     const MapRec& mp = env.maps[r.map_id];
     DevJob d;
     std::memset(&d, 0, sizeof(d));
@@ -100,8 +101,9 @@ static inline void packTaRootsAs(const PackEnv& env, uint32_t algo, float w, int
     if (slotRun[q] >= 0) st.recs[q].ec_off = wordBase + static_cast<uint32_t>(st.words.size()) + static_cast<uint32_t>(slotRun[q]);
 }
 
-static inline void packTaRoots(const PackEnv& env, int32_t n, const mrp_ll_ta_root* roots, uint32_t wordBase, TaRootStaging& st) {
-  packTaRootsAs(env, MRP_LL_ASTAR_TA, 0.0f, n, roots, wordBase, st);
+static inline void packTaRoots(const PackEnv& env, int32_t n, const mrp_ll_ta_root* roots, uint32_t wordBase, TaRootStaging& st,
+                               uint32_t maxAgents = kTaRootMaxAgents) {
+  packTaRootsAs(env, MRP_LL_ASTAR_TA, 0.0f, n, roots, wordBase, st, nullptr, maxAgents);
 }
 
 // The answer words of a root in its first result's output area.
@@ -129,14 +131,15 @@ static inline void notRunResult(mrp_ll_result& r, int32_t status) {
 // MRP_LL_BAD_JOB and of any other root MRP_LL_NOT_RUN, their other fields 0.  Written before the first step that can fail and
 // again when one did, so that a non-zero return never leaves an output as the caller passed it in.
 static inline void blankTaRootOutputs(const PackEnv& env, int32_t n, const mrp_ll_ta_root* roots, int32_t* planned,
-                                      mrp_ll_conflict* conflicts, const int32_t* const* storeIds = nullptr) {
+                                      mrp_ll_conflict* conflicts, const int32_t* const* storeIds = nullptr,
+                                      uint32_t maxAgents = kTaRootMaxAgents) {
   for (int32_t k = 0; k < n; ++k) {
     std::memset(&conflicts[k], 0, sizeof(mrp_ll_conflict));
     conflicts[k].found = -1;
     planned[k] = 0;
     const mrp_ll_ta_root& r = roots[k];
     if (!r.results || r.n_agents <= 0) continue;
-    const int32_t status = taRootValid(env, r, storeIds ? storeIds[k] : nullptr) ? MRP_LL_NOT_RUN : MRP_LL_BAD_JOB;
+    const int32_t status = taRootValid(env, r, storeIds ? storeIds[k] : nullptr, maxAgents) ? MRP_LL_NOT_RUN : MRP_LL_BAD_JOB;
     for (int a = 0; a < r.n_agents; ++a) notRunResult(r.results[a], status);
   }
 }

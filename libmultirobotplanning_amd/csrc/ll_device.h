@@ -118,7 +118,9 @@ constexpr uint32_t kHeurWords = 512;                               // a heuristi
 // kTaRootScanSkipped: all did, and the table did not fit the slot's path area) and, in word kTaRootPlannedWord, the number
 // of results filled in.
 constexpr uint32_t kTaRootAgentWords = 3;
-constexpr uint32_t kTaRootMaxAgents = 64;                          // (the assignment's limit)
+constexpr uint32_t kTaRootMaxAgents = 64;                          // (the narrow assignment's limit; one lane per agent)
+constexpr uint32_t kTaRootWideMaxAgents = 256;                     // mrp_ll_ta_root_batch_w / _eps_root_batch_w (ll_ta_root_wide.h):
+                                                                   // the wide assignment's limit; four agents per lane
 constexpr uint32_t kTaRootPlannedWord = 10;
 constexpr uint32_t kTaRootScanSkipped = 0xFFFFFFFEu;
 #ifdef __HIP__  // (the language mode of hipcc: a .hip source, device and host pass)

@@ -21,6 +21,7 @@
 //   ll_ta.h            TaEnv, runTaArena / runJobTA, runJobTaEps: the task-assignment low levels
 //   ll_ta_root.h       runTaRoot, taRootLoop: the root node of a CBS-TA conflict tree, searches and scan, by one workgroup
 //   ll_ta_eps_root.h   runTaEpsRoot, taEpsRootLoop: the root node of an ECBS-TA conflict tree, likewise, one table for both
+//   ll_ta_root_wide.h  runTaRootWide, runTaEpsRootWide: their siblings for roots of up to 256 agents, four agents per lane
 //   ll_sipp.h          SIPP: its tiers, sippLoop, runSipp, processSippJob
 //   ll_node_scan.h     nodeScan, nodeScanFromParent: the conflicts of the conflict-tree node a search has completed (also
 //                      compiled for the CPU)
@@ -49,6 +50,7 @@
 #include "ll_ta.h"
 #include "ll_ta_root.h"
 #include "ll_ta_eps_root.h"
+#include "ll_ta_root_wide.h"
 #include "ll_sipp.h"
 #include "ll_node_scan.h"
 
@@ -247,6 +249,8 @@ MRP_LL_WINDOW_KERNEL(mrp_ll_ecbs_search_kernel, batchLoop<1>)  // A*-epsilon job
 MRP_LL_WINDOW_KERNEL(mrp_ll_cbs_search_kernel, batchLoop<2>)  // A* jobs only
 MRP_LL_WINDOW_KERNEL(mrp_ll_ta_root_kernel, taRootLoop)  // roots of CBS-TA conflict trees (ll_ta_root.h), the A* kernels' window
 MRP_LL_WINDOW_KERNEL(mrp_ll_ta_eps_root_kernel, taEpsRootLoop)  // roots of ECBS-TA conflict trees (ll_ta_eps_root.h), the mixed kernel's window
+MRP_LL_WINDOW_KERNEL(mrp_ll_ta_root_wide_kernel, taRootWideLoop)  // the same for roots of up to 256 agents (ll_ta_root_wide.h)
+MRP_LL_WINDOW_KERNEL(mrp_ll_ta_eps_root_wide_kernel, taEpsRootWideLoop)
 
 // SIPP batches (MRP_LL_SIPP jobs only) run in their own kernels so that the CBS/ECBS kernels' register allocation is
 // not widened by a path they never take.  Same queue discipline as mrp_ll_search_kernel.
@@ -533,18 +537,19 @@ extern "C" __global__ void __launch_bounds__(64) mrp_ll_sipp_persistent_kernel(L
 // The CBS / ECBS kernels by role and kind (0 = mixed, 1 = A*-epsilon jobs only, 2 = A* jobs only, see processJob; the front /
 // heavy pair exists for kind 1 alone).  `slot` numbers the kernel for allowFullLds.
 typedef void (*Kern)(LaunchParams);
-enum Role : int { kBatch = 0, kResident = 1, kFront = 2, kHeavy = 3, kFront4 = 4, kTaRoot = 5, kTaEpsRoot = 6 };
+enum Role : int { kBatch = 0, kResident = 1, kFront = 2, kHeavy = 3, kFront4 = 4, kTaRoot = 5, kTaEpsRoot = 6, kTaRootWide = 7, kTaEpsRootWide = 8 };
 struct KernelRef {
   Kern fn;
   int slot;
 };
 static KernelRef kernelFor(Role role, int kind) {
-  static const Kern table[11] = {mrp_ll_search_kernel,     mrp_ll_ecbs_search_kernel,     mrp_ll_cbs_search_kernel,
+  static const Kern table[13] = {mrp_ll_search_kernel,     mrp_ll_ecbs_search_kernel,     mrp_ll_cbs_search_kernel,
                                  mrp_ll_persistent_kernel, mrp_ll_ecbs_persistent_kernel, mrp_ll_cbs_persistent_kernel,
                                  mrp_ll_ecbs_front_kernel, mrp_ll_ecbs_heavy_kernel,      mrp_ll_ecbs_front4_kernel,
-                                 mrp_ll_ta_root_kernel,    mrp_ll_ta_eps_root_kernel};
+                                 mrp_ll_ta_root_kernel,    mrp_ll_ta_eps_root_kernel,     mrp_ll_ta_root_wide_kernel,
+                                 mrp_ll_ta_eps_root_wide_kernel};
   const int slot = role == kFront ? 6 : role == kHeavy ? 7 : role == kFront4 ? 8 : role == kTaRoot ? 9 : role == kTaEpsRoot ? 10
-                   : 3 * role + (kind == 1 || kind == 2 ? kind : 0);
+                   : role == kTaRootWide ? 11 : role == kTaEpsRootWide ? 12 : 3 * role + (kind == 1 || kind == 2 ? kind : 0);
   return KernelRef{table[slot], slot};
 }
 
@@ -553,7 +558,7 @@ static KernelRef kernelFor(Role role, int kind) {
 // launches through here, and the attribute is per device.
 static hipError_t allowFullLds(const KernelRef& k) {
   static std::mutex mu;
-  static bool done[11][64] = {};
+  static bool done[13][64] = {};
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
@@ -619,14 +624,15 @@ extern "C" int mrp_ll_front_heavy_occupancy(int heavy, uint32_t ldsBytes) {
 
 // The roots of CBS-TA conflict trees (ll_ta_root.h): `grid` workgroups share P->n_jobs roots; the window of the A* kernels
 // (mrp_ll_lds_bytes(kind = 2)), so that every search meets the tiers an ordinary MRP_LL_ASTAR_TA batch gives it.
-extern "C" hipError_t mrp_ll_launch_ta_root(const mrp::LaunchParams* P, uint32_t grid, uint32_t ldsBytes, hipStream_t stream) {
-  return mrp::launchWithLds(mrp::kernelFor(mrp::kTaRoot, 0), P, grid, ldsBytes, stream);
+// wide: the kernel for roots of up to 256 agents (ll_ta_root_wide.h), same window.
+extern "C" hipError_t mrp_ll_launch_ta_root(const mrp::LaunchParams* P, uint32_t grid, uint32_t ldsBytes, int wide, hipStream_t stream) {
+  return mrp::launchWithLds(mrp::kernelFor(wide ? mrp::kTaRootWide : mrp::kTaRoot, 0), P, grid, ldsBytes, stream);
 }
 
 // The roots of ECBS-TA conflict trees (ll_ta_eps_root.h), likewise; the window of the mixed kernel (mrp_ll_lds_bytes(kind = 0)),
 // which is what an ordinary MRP_LL_ASTAR_EPS_TA batch is launched with.
-extern "C" hipError_t mrp_ll_launch_ta_eps_root(const mrp::LaunchParams* P, uint32_t grid, uint32_t ldsBytes, hipStream_t stream) {
-  return mrp::launchWithLds(mrp::kernelFor(mrp::kTaEpsRoot, 0), P, grid, ldsBytes, stream);
+extern "C" hipError_t mrp_ll_launch_ta_eps_root(const mrp::LaunchParams* P, uint32_t grid, uint32_t ldsBytes, int wide, hipStream_t stream) {
+  return mrp::launchWithLds(mrp::kernelFor(wide ? mrp::kTaEpsRootWide : mrp::kTaEpsRoot, 0), P, grid, ldsBytes, stream);
 }
 
 // The SIPP kernels' LDS is static: no attribute to set.

@@ -618,7 +618,10 @@ def solve_cbs_ta_batch(instances: Sequence[Dict], max_task_assignments: int = 2 
     dimx, dimy, obstacles [[x, y]], starts [[x, y]] and potential_goals (per agent a list of [x, y]).  Returns (results,
     stats): per instance status, cost, makespan, hl_expanded, ll_expanded, num_task_assignments, n_roots, root_conflicts,
     n_ll_searches, n_root_searches, digest, tasks (per agent [x, y] or None) and paths (per agent [[x, y, t]], t = the path's cost up to that
-    state, as the reference writes it)."""
+    state, as the reference writes it).
+    An instance has at most 256 agents and 256 distinct potential goals (beyond that: LL_ERROR, the other instances
+    unaffected); instances within 64 x 64 and wider ones may share a batch.  use_root_kernel: roots of at most 64 agents
+    through mrp_ll_ta_root_batch, wider ones through mrp_ll_ta_root_batch_w."""
     lib = load_library(_lib_path)
     opt = mrp_hl_ta_options(max_task_assignments, 1 if use_root_kernel else 0, max_hl_expansions, max_ll_expansions)
     return _solve_ta_batch(lib.mrp_hl_solve_cbs_ta_batch, "mrp_hl_solve_cbs_ta_batch", instances, opt, device, path_cap)
@@ -628,13 +631,15 @@ def solve_ecbs_ta_batch(instances: Sequence[Dict], w: float, max_task_assignment
                         max_hl_expansions: int = -1, max_ll_expansions: int = -1, device: int = 0, path_cap: int = 256,
                         _lib_path: Optional[str] = None):
     """mrp_hl_solve_ecbs_ta_batch: ECBS with task assignment (ecbs_ta.hpp:94-352, low level AStarEpsilon under the same
-    weight w >= 1) for a batch of instances; instances and results as solve_cbs_ta_batch.  use_root_kernel: roots through
-    mrp_ll_ta_eps_root_batch (one workgroup each) or, False (the default: measured faster for thousands of instances), as n
-    dependent low-level jobs; same results.
+    weight w >= 1) for a batch of instances; instances, limits (256 agents, 256 distinct potential goals) and results as
+    solve_cbs_ta_batch.  use_root_kernel: roots through mrp_ll_ta_eps_root_batch (one workgroup each; roots of more than 64
+    agents through mrp_ll_ta_eps_root_batch_w) or, False (the default: measured faster for thousands of instances of the
+    reference shape), as n dependent low-level jobs; same results.
     Environment, read once per call: MRP_HL_TA_DEVICE_PATHS=1 keeps every path in the engine's device-resident path store and
     names a search's focal context by slot instead of shipping its table (same results; off by default);
     MRP_HL_TA_PATH_SLOTS=N sets the store's slot count (unset: four per agent of the batch, 256 .. 65536; not tuned) — a
-    search that finds no free slot, or whose context has a path outside the store, goes out as without the knob."""
+    search that finds no free slot, or whose context has a path outside the store, goes out as without the knob.  Instances
+    of more than 64 agents ignore MRP_HL_TA_DEVICE_PATHS: a table of their paths by slot does not fit a workgroup's path area."""
     lib = load_library(_lib_path)
     if not hasattr(lib, "mrp_hl_solve_ecbs_ta_batch"):
         raise RuntimeError("this build of the drivers has no mrp_hl_solve_ecbs_ta_batch")

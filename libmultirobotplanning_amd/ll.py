@@ -112,7 +112,7 @@ EXPORTS = ["mrp_ll_create", "mrp_ll_destroy", "mrp_ll_last_error", "mrp_ll_uploa
            "mrp_ll_constraint_store_reserve", "mrp_ll_submit_sets", "mrp_ll_session_front_tables",
            "mrp_ll_submit_node", "mrp_ll_assign_batch", "mrp_ll_assign_series_create", "mrp_ll_assign_series_next",
            "mrp_ll_assign_series_destroy", "mrp_ll_assign_batch_w", "mrp_ll_assign_series_create_w", "mrp_ll_ta_root_batch", "mrp_ll_ta_eps_root_batch",
-           "mrp_ll_ta_eps_root_batch_stored"]
+           "mrp_ll_ta_eps_root_batch_stored", "mrp_ll_ta_root_batch_w", "mrp_ll_ta_eps_root_batch_w"]
 
 _lib = None
 
@@ -227,6 +227,10 @@ def load_library(path: Optional[str] = None):
     lib.mrp_ll_ta_root_batch.restype = ctypes.c_int
     lib.mrp_ll_ta_root_batch.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(mrp_ll_ta_root), I32P,
                                          ctypes.POINTER(mrp_ll_conflict)]
+    lib.mrp_ll_ta_root_batch_w.restype = ctypes.c_int
+    lib.mrp_ll_ta_root_batch_w.argtypes = lib.mrp_ll_ta_root_batch.argtypes
+    lib.mrp_ll_ta_eps_root_batch_w.restype = ctypes.c_int
+    lib.mrp_ll_ta_eps_root_batch_w.argtypes = lib.mrp_ll_ta_eps_root_batch.argtypes
     lib.mrp_ll_assign_series_destroy.restype = None
     lib.mrp_ll_assign_series_destroy.argtypes = [ctypes.c_void_p]
     if path is None:
@@ -556,28 +560,34 @@ class LowLevelEngine:
             per_root.append((na, cres, states, actions, costs))
         return croots, planned, conf, per_root, keep
 
-    def ta_root_batch(self, roots: Sequence[TaRoot], states_cap: Optional[int] = None, raw_rc: bool = False):
+    def ta_root_batch(self, roots: Sequence[TaRoot], states_cap: Optional[int] = None, raw_rc: bool = False, wide: bool = False):
         """mrp_ll_ta_root_batch: the roots of CBS-TA conflict trees, one workgroup each, in one launch.  Returns one
-        TaRootResult per root; with raw_rc the call's return code instead of raising (E_BUSY inside a session)."""
+        TaRootResult per root; with raw_rc the call's return code instead of raising (E_BUSY inside a session).
+        wide: mrp_ll_ta_root_batch_w (roots of up to 256 agents instead of 64; the same answers)."""
         n = len(roots)
         cap = states_cap or self.max_horizon
         croots, planned, conf, per_root, keep = self._marshal_ta_roots(roots, cap)
-        rc = self._lib.mrp_ll_ta_root_batch(self._h, n, croots, planned.ctypes.data_as(I32P), conf)
+        call = self._lib.mrp_ll_ta_root_batch_w if wide else self._lib.mrp_ll_ta_root_batch
+        rc = call(self._h, n, croots, planned.ctypes.data_as(I32P), conf)
         if raw_rc and rc != 0:
             return rc
-        self._check(rc, "mrp_ll_ta_root_batch")
+        self._check(rc, "mrp_ll_ta_root_batch_w" if wide else "mrp_ll_ta_root_batch")
         names = [k for k, _ in mrp_ll_conflict._fields_]
         return [TaRootResult(planned=int(planned[i]), results=self._results(na, cap, cres, states, actions, costs),
                              conflict={k: getattr(conf[i], k) for k in names})
                 for i, (na, cres, states, actions, costs) in enumerate(per_root)]
 
     def ta_eps_root_batch(self, roots: Sequence[TaRoot], w: float, states_cap: Optional[int] = None, raw_rc: bool = False,
-                          result_path_ids: Optional[Sequence[Optional[Sequence[int]]]] = None):
+                          result_path_ids: Optional[Sequence[Optional[Sequence[int]]]] = None, wide: bool = False):
         """mrp_ll_ta_eps_root_batch: the roots of ECBS-TA conflict trees under weight w, one workgroup each, in one launch:
         agent a's MRP_LL_ASTAR_EPS_TA search sees the paths of the agents before it.  Returns one TaRootResult per root
         (conflict["count"] is the node's focalHeuristic); with raw_rc the call's return code instead of raising.
         result_path_ids (mrp_ll_ta_eps_root_batch_stored): per root None or one path-store slot per agent (-1: not stored)
-        that also receives the agent's path, for later jobs that name it in path_ids; the answer is the same."""
+        that also receives the agent's path, for later jobs that name it in path_ids; the answer is the same.
+        wide: mrp_ll_ta_eps_root_batch_w (roots of up to 256 agents instead of 64; the same answers); it has no stored
+        variant, so wide together with result_path_ids raises ValueError."""
+        if wide and result_path_ids is not None:
+            raise ValueError("ta_eps_root_batch: the wide call stores no paths (wide=True with result_path_ids)")
         n = len(roots)
         cap = states_cap or self.max_horizon
         croots, planned, conf, per_root, keep = self._marshal_ta_roots(roots, cap)
@@ -591,6 +601,8 @@ class LowLevelEngine:
             ptrs = (I32P * max(n, 1))(*[a.ctypes.data_as(I32P) if a is not None else I32P() for a in arrs])
             keep.append((arrs, ptrs))
             rc = self._lib.mrp_ll_ta_eps_root_batch_stored(self._h, w, n, croots, conf, planned.ctypes.data_as(I32P), ptrs)
+        elif wide:
+            rc = self._lib.mrp_ll_ta_eps_root_batch_w(self._h, w, n, croots, conf, planned.ctypes.data_as(I32P))
         else:
             rc = self._lib.mrp_ll_ta_eps_root_batch(self._h, w, n, croots, conf, planned.ctypes.data_as(I32P))
         if raw_rc and rc != 0:

@@ -6,6 +6,10 @@ done once outside the timed region, median of --repeats after a warm-up; kernel 
 (2) Instances per second of the batched driver (mrp_hl_solve_cbs_ta_batch, the time of its rounds: tables and the series'
 optima are set up before) on the same instances with use_root_kernel 1 and 0, same median, the answers compared; with the
 share of searches that are root searches and the share of instances solved at their first root.
+--agents N above 64: comparison (2) alone, on instances of the wide corpus generator (tests/ta_wide_corpus.py
+instance(seed, N, pool): 32 x 32, 100 obstacles, 1 - 3 potential goals per agent among the six nearest of --pool cells, default
+min(256, 2 N)), seeds 0 .. instances - 1, every tree under --max-hl expansions (default 20); the root call is then
+mrp_ll_ta_root_batch_w.  E.g. --agents 96 --instances 16 and --agents 256 --instances 4.
 usage: python scripts/cbs_ta_throughput.py [--instances 4096]  (prints one JSON line)"""
 import argparse
 import json
@@ -27,7 +31,11 @@ ap.add_argument("--goals", type=int, default=20)
 ap.add_argument("--maps", type=int, default=16)
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--slots", type=int, default=1024)
+ap.add_argument("--pool", type=int, default=0)
+ap.add_argument("--max-hl", type=int, default=-1)
 args = ap.parse_args()
+WIDE = args.agents > 64
+MAX_HL = args.max_hl if args.max_hl >= 0 or not WIDE else 20
 CAP = 128  # states per result buffer (paths on these maps stay below it; a longer one would come back PATH_TRUNCATED)
 
 
@@ -56,6 +64,8 @@ def median(v):
 rng = np.random.default_rng(3)
 eng = ll.LowLevelEngine(device=0, n_tickets=1, slots=args.slots)
 try:
+    if WIDE:
+        raise StopIteration  # (comparison (1) is the narrow root call's)
     # maps, and one table per (map, potential goal): one launch
     worlds = []
     for _ in range(args.maps):
@@ -130,20 +140,27 @@ try:
                           root_batch=dict(root_call, roots_per_s=round(n / root_call["wall_s"])),
                           jobs_plus_scan=dict(jobs_call, roots_per_s=round(n / jobs_call["wall_s"])),
                           speedup=round(jobs_call["wall_s"] / root_call["wall_s"], 3))
+except StopIteration:
+    n, result = args.instances, dict(instances=args.instances, agents=args.agents, generator="ta_wide_corpus", max_hl=MAX_HL)
 finally:
     eng.close()
 
 # ---- the driver, roots as one call against roots as ordinary jobs
 from libmultirobotplanning_amd import hl  # noqa: E402
 
-dinst = [dict(dimx=32, dimy=32, obstacles=worlds[k % args.maps][2], starts=[list(c) for c in s],
+if WIDE:
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ta_wide_corpus  # noqa: E402
+    pool = args.pool or min(256, 2 * args.agents)
+    dinst = [ta_wide_corpus.instance(seed, args.agents, pool) for seed in range(args.instances)]
+dinst = dinst if WIDE else [dict(dimx=32, dimy=32, obstacles=worlds[k % args.maps][2], starts=[list(c) for c in s],
               potential_goals=[[list(c) for c in g]] * args.agents) for k, (_, s, g) in enumerate(inst)]
 driver, answers = {}, {}
 for use in (1, 0):
     walls, calls = [], []
     for _ in range(args.repeats + 1):
         t0 = time.perf_counter()
-        got, st = hl.solve_cbs_ta_batch(dinst, use_root_kernel=bool(use), path_cap=CAP)
+        got, st = hl.solve_cbs_ta_batch(dinst, use_root_kernel=bool(use), max_hl_expansions=MAX_HL, path_cap=CAP)
         calls.append(time.perf_counter() - t0)
         walls.append(st["wall_seconds"])
     answers[use] = [(g["status"], g["cost"], g["hl_expanded"], g["ll_expanded"], g["num_task_assignments"], g["digest"]) for g in got]

@@ -5,6 +5,10 @@ agents, twenty potential goals shared by all agents of an instance, w = 1.3.  Th
 after one warm-up run each; reported: the median, every run, and the spread (max - min) / median.
 --device-paths adds both forms once more under MRP_HL_TA_DEVICE_PATHS=1 (paths in the engine's path store, contexts by slot;
 --path-slots sets MRP_HL_TA_PATH_SLOTS), interleaved with the other two, answers compared with theirs.
+--agents N above 64: the instances come from the wide corpus generator (tests/ta_wide_corpus.py instance(seed, N, pool):
+32 x 32, 100 obstacles, 1 - 3 potential goals per agent among the six nearest of --pool cells, default min(256, 2 N)), seeds
+0 .. instances - 1, every tree under --max-hl expansions (default 20: deterministic counters, bounded time); the root call is
+then mrp_ll_ta_eps_root_batch_w.  E.g. --agents 96 --instances 16 and --agents 256 --instances 4.
 usage: python scripts/ecbs_ta_tree_throughput.py [--instances 2048] [--w 1.3] [--device-paths]  (prints one JSON line)"""
 import argparse
 import json
@@ -27,6 +31,8 @@ ap.add_argument("--repeats", type=int, default=5)
 ap.add_argument("--w", type=float, default=1.3)
 ap.add_argument("--device-paths", action="store_true")
 ap.add_argument("--path-slots", type=int, default=0)
+ap.add_argument("--pool", type=int, default=0)
+ap.add_argument("--max-hl", type=int, default=-1)
 args = ap.parse_args()
 CAP = 128  # states per result buffer
 
@@ -55,12 +61,19 @@ def median(v):
 
 rng = np.random.default_rng(3)
 worlds = []
-for _ in range(args.maps):
+WIDE = args.agents > 64
+MAX_HL = args.max_hl if args.max_hl >= 0 or not WIDE else 20
+if WIDE:
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ta_wide_corpus  # noqa: E402
+    pool = args.pool or min(256, 2 * args.agents)
+    insts = [ta_wide_corpus.instance(seed, args.agents, pool) for seed in range(args.instances)]
+for _ in range(0 if WIDE else args.maps):
     cells = rng.permutation(32 * 32)[:204]
     obst = {(int(c) % 32, int(c) // 32) for c in cells}
     worlds.append((component(32, obst), [list(o) for o in sorted(obst)]))
-insts = []
-for k in range(args.instances):
+insts = insts if WIDE else []
+for k in range(0 if WIDE else args.instances):
     comp, obst = worlds[k % args.maps]
     pick = rng.permutation(len(comp))[:args.agents + args.goals]
     goals = [list(comp[i]) for i in pick[args.agents:]]
@@ -80,14 +93,15 @@ for rep in range(args.repeats + 1):  # the first run of each form is the warm-up
             os.environ["MRP_HL_TA_DEVICE_PATHS"] = "1"
             if args.path_slots:
                 os.environ["MRP_HL_TA_PATH_SLOTS"] = str(args.path_slots)
-        got, st = hl.solve_ecbs_ta_batch(insts, args.w, use_root_kernel=bool(use), path_cap=CAP)
+        got, st = hl.solve_ecbs_ta_batch(insts, args.w, use_root_kernel=bool(use), max_hl_expansions=MAX_HL, path_cap=CAP)
         for knob in ("MRP_HL_TA_DEVICE_PATHS", "MRP_HL_TA_PATH_SLOTS"):
             os.environ.pop(knob, None)
         walls[name].append(st["wall_seconds"])
         last[name] = (got, st)
         answers[name] = [(g["status"], g["cost"], g["hl_expanded"], g["ll_expanded"], g["num_task_assignments"], g["digest"]) for g in got]
 assert all(a == answers["root_kernel"] for a in answers.values())
-result = dict(instances=n, agents=args.agents, potential_goals=args.goals, w=args.w, repeats=args.repeats)
+result = dict(instances=n, agents=args.agents, potential_goals=args.goals, w=args.w, repeats=args.repeats, max_hl=MAX_HL,
+              generator="ta_wide_corpus" if WIDE else "shared goals")
 for _, _, name in legs:
     v = walls[name][1:]
     m = median(v)
