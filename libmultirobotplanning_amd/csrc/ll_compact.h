@@ -206,6 +206,11 @@ static_assert(sizeof(CRes) <= 32 && oRes + 64 <= oOpen, "CRes fits its block of 
 #define MRP_CT_COUNT_SLOTS 7
 #endif
 #define MRP_CT_COUNTX(k, v) do { if ((k) < MRP_CT_COUNT_SLOTS) MRP_CT_COUNT(k, v); } while (0)
+// ... and the exits of the search loop, from 31 on (tests/support/emu_select.cpp names them)
+// hook of the emulator's drivers at the end of a search, with the window in its final state: nothing in the product
+#ifndef MRP_CT_DONE
+#define MRP_CT_DONE(lds) do { } while (0)
+#endif
 
 #define MRP_CT_JOB_U32(lds, field) ldsLoadS(lds, oJob + (uint32_t)offsetof(CJob, field))
 template <class T>
@@ -253,6 +258,36 @@ WV_FN V ctz(V v) { return splat(31u) - clz(v & (splat(0u) - v)); }
 #if defined(MRP_CT_CHECK_TOPS) && (defined(MRP_CT_LOAD_TOPS) || defined(__HIP_DEVICE_COMPILE__))
 #error "MRP_CT_CHECK_TOPS checks the kept heap roots: an emulator build without MRP_CT_LOAD_TOPS"
 #endif
+
+// The two forms of a predicated LDS store of the expansion's heap steps, and of the search loop's top and exits
+// (-DMRP_CT_PLAIN_EXPANSION turns these two off as well):
+//   MRP_CT_EXEC_STORES  ldsStoreSel is the masked store: an exec region (save, branch, restore) around every store
+//   MRP_CT_PLAIN_LOOP   the loop top tests the goal twice and the three limits one by one, and every exit is a `break`
+#define MRP_CT_RARE(c) __builtin_expect(!!(c), 0)  // an exit of the search loop: its block lies off the hot path
+#ifdef MRP_CT_PLAIN_EXPANSION
+#ifndef MRP_CT_EXEC_STORES
+#define MRP_CT_EXEC_STORES
+#endif
+#ifndef MRP_CT_PLAIN_LOOP
+#define MRP_CT_PLAIN_LOOP
+#endif
+#endif
+// The select-address store: every lane stores, and a lane whose predicate is off stores to the scratch word — one word of
+// the result block that no instance uses (CRes ends at oRes + 24, the diagnostic build's words begin at oRes + 32).
+// NOTHING EVER READS THE SCRATCH WORD: what it holds is whatever the last such lane wrote.  All the lanes that are off
+// share the one address, so they cost the store one more bank access at most.
+constexpr uint32_t oScratch = oRes + 28u;
+static_assert(sizeof(CRes) <= oScratch - oRes && oScratch + 4u <= oRes + 32u && oScratch % 4u == 0u && oScratch + 4u <= oOpen,
+              "the scratch word lies between the CRes and the profile words, in front of the heaps");
+WV_FN void ldsStoreSel(Lds lds, V addr, V val, B pred) {
+#ifdef MRP_CT_EXEC_STORES
+  ldsStore32m(lds, addr, val, pred);
+#else
+  // (the address is no inline constant, and a select cannot take its mask and a literal or a scalar operand at once: the
+  // compiler keeps it in one vector register across the search loop)
+  ldsStore32(lds, sel(pred, addr, splat(oScratch)), val);
+#endif
+}
 
 #ifndef WV_HAS_MASK_SLICES  // a vocabulary without the slices of wave-uniform masks
 // (what the tier asks of maskShr: sixteen bits of m from bit sh on, sh a multiple of 16 below 64)
@@ -320,7 +355,7 @@ WV_FN V dualDescendT(Lds lds, const Sides& S, V hb, V km, V cMax, V xk, V& top) 
     const B reached = ((g32 & S.anc) == S.anc) & (((r32 ^ S.needR) & S.anc) == 0u);
     const B onPath = reached & go;
     const uint64_t pM = ballot(onPath);
-    ldsStore32m(lds, hb + node * 4u, pe, onPath);       // every node on the path pulls its chosen child up
+    ldsStoreSel(lds, hb + node * 4u, pe, onPath);       // every node on the path pulls its chosen child up
     // the new hole of this lane's side: below the deepest node on the path (levels are index-ordered), on the side it chose
     const V pm = bothSides(S, lo32(pM), hi32(pM));
     const V steps = popc(pm);
@@ -341,6 +376,10 @@ WV_FN V dualDescend(Lds lds, const Sides& S, V hb, V km, V cMax, V xk) {
 // Lane l5 of a side loads the chain's ancestor l5 (lanes beyond the root read the word in front of the array, which no
 // element is better than); one ballot finds where the sequential loop would have stopped; the ancestors below that point
 // move down one level and the new element lands above them — one load, one store.
+// SEL: the store is a select-address store (ldsStoreSel).  The ordered walk of compactSearch passes false: there the
+// selects cost the narrow instance two vector registers (120 instead of 118) and the wide one two (148), for a store of a
+// path that 6 % of the expansions take.
+template <bool SEL = true>
 WV_FN void dualSiftUp(Lds lds, const Sides& S, V hb, V km, V p1, uint32_t e, bool idleA, bool idleB) {
   const V ancPos = (p1 >> (S.l5 + 1u)) - 1u;
   const V ae = ldsLoad32(lds, hb + ancPos * 4u);
@@ -349,7 +388,10 @@ WV_FN void dualSiftUp(Lds lds, const Sides& S, V hb, V km, V p1, uint32_t e, boo
   const uint32_t stopA = idleA ? 0u : ctz32(~lo32(worse)) + 1u, stopB = idleB ? 0u : ctz32(~hi32(worse)) + 1u;
   const V stop1 = bothSides(S, stopA, stopB);
   const V dest = (p1 >> S.l5) - 1u;                     // lane l5 < stop: ancestor l5 moves down to here; lane == stop: e
-  ldsStore32m(lds, hb + dest * 4u, sel((S.l5 + 1u) == stop1, splat(e), ae), S.l5 < stop1);
+  if (SEL)
+    ldsStoreSel(lds, hb + dest * 4u, sel((S.l5 + 1u) == stop1, splat(e), ae), S.l5 < stop1);
+  else
+    ldsStore32m(lds, hb + dest * 4u, sel((S.l5 + 1u) == stop1, splat(e), ae), S.l5 < stop1);
 }
 
 // Per-lane constants of the four-chains-in-one-wave step: the wave as four rows of 16 lanes.  A sift-up chain of these
@@ -379,6 +421,8 @@ WV_FN V perRow(const Rows& R, uint32_t x1, uint32_t x2, uint32_t y1, uint32_t y2
 // chains share (everything from their lowest common ancestor up; with p = 0 the first element itself): there an ancestor is either untouched, or the first
 // push's element, or its own parent moved down one level — all of which the second chain's lanes hold already (the parent
 // is the next lane of the row), so the fix-up is a row shift and two selects.
+// (SEL: as in dualSiftUp)
+template <bool SEL = true>
 WV_FN void pushPairs(Lds lds, const Rows& R, uint32_t hbX, uint32_t kmX, uint32_t pX, uint32_t nX, uint32_t eX1, uint32_t eX2,
                      uint32_t hbY, uint32_t kmY, uint32_t pY, uint32_t nY, uint32_t eY1, uint32_t eY2) {
   const V hb = sel(R.isY, splat(hbY), splat(hbX));
@@ -394,7 +438,10 @@ WV_FN void pushPairs(Lds lds, const Rows& R, uint32_t hbX, uint32_t kmX, uint32_
   // first ancestor that is not worse than the element, plus one (0: nothing to push)
   const uint32_t sX1 = nX >= 1u ? ctz32(~lo32(worse1)) + 1u : 0u, sY1 = nY >= 1u ? ctz32(~hi32(worse1)) + 1u : 0u;
   const V stop1 = sel(R.isY, splat(sY1), splat(sX1));
-  ldsStore32m(lds, dest, sel((R.l4 + 1u) == stop1, e, ae), (!R.isSecond) & (R.l4 < stop1));
+  if (SEL)
+    ldsStoreSel(lds, dest, sel((R.l4 + 1u) == stop1, e, ae), (!R.isSecond) & (R.l4 < stop1));
+  else
+    ldsStore32m(lds, dest, sel((R.l4 + 1u) == stop1, e, ae), (!R.isSecond) & (R.l4 < stop1));
   if (nX >= 2u || nY >= 2u) {
     // chains of p and p + 1 have the same depth unless p + 2 is a power of two (p + 1 starts a new level)
 #ifndef MRP_CT_PLAIN_EXPANSION
@@ -412,7 +459,10 @@ WV_FN void pushPairs(Lds lds, const Rows& R, uint32_t hbX, uint32_t kmX, uint32_
     const uint64_t worse2 = ballot((now & km) < ek);
     const uint32_t sX2 = nX >= 2u ? ctz32(~(lo32(worse2) >> 16)) + 1u : 0u, sY2 = nY >= 2u ? ctz32(~(hi32(worse2) >> 16)) + 1u : 0u;
     const V stop2 = sel(R.isY, splat(sY2), splat(sX2));
-    ldsStore32m(lds, dest, sel((R.l4 + 1u) == stop2, e, now), R.isSecond & (R.l4 < stop2));
+    if (SEL)
+      ldsStoreSel(lds, dest, sel((R.l4 + 1u) == stop2, e, now), R.isSecond & (R.l4 < stop2));
+    else
+      ldsStore32m(lds, dest, sel((R.l4 + 1u) == stop2, e, now), R.isSecond & (R.l4 < stop2));
   }
 }
 
@@ -429,7 +479,8 @@ WV_FN V rowStop(uint64_t worse, V rowSh) { return ctz(~maskShr(worse, rowSh)) + 
 //   tops      the root of this lane's heap (what counts is the root lane of each side, lanes 0 and 32), kept current: a
 //             push becomes the root exactly when the root's key is less than its own — every ancestor's key is <= the
 //             root's, so the sift-up runs to the top then, and stops at the root or below otherwise; equal keys stay
-// A row without a push (position + 1 = 1: its lanes read the word in front of the array) stores nothing.
+// A row without a push (position + 1 = 1: its lanes read the word in front of the array, and its destination would be
+// element 0) stores nothing: `act` is off in its lanes, which sends them to the scratch word.
 template <bool TOPS>
 WV_FN void pushTurn(Lds lds, const Rows& R, V hb, V km, V sideBits, uint32_t pair, uint32_t low, uint32_t e1s, uint32_t e2s, V& n,
                     V& tops) {
@@ -445,7 +496,7 @@ WV_FN void pushTurn(Lds lds, const Rows& R, V hb, V km, V sideBits, uint32_t pai
   const V ae = ldsLoad32(lds, hb + ancIdx * 4u - 4u);   // (lanes beyond the root: the word in front of the array)
   const V dest = hb + (p1 >> R.l4) * 4u - 4u;           // lane l4 < stop: ancestor l4 moves down to here; lane == stop: e
   const V stop1 = rowStop(ballot((ae & km) < ek), R.heapSh);  // (of the heap's FIRST row: the second row's fix-up asks for it)
-  ldsStore32m(lds, dest, sel((R.l4 + 1u) == stop1, e, ae), (!R.isSecond) & act & (R.l4 < stop1));
+  ldsStoreSel(lds, dest, sel((R.l4 + 1u) == stop1, e, ae), (!R.isSecond) & act & (R.l4 < stop1));
   if (TOPS) tops = sel(((tops & km) < (e1 & km)) & (cnt != 0u), e1, tops);
   if ((pair ^ low) != 0u) {
     // chains of p and p + 1 have the same depth unless p + 2 (the second row's p1) is a power of two
@@ -456,7 +507,7 @@ WV_FN void pushTurn(Lds lds, const Rows& R, V hb, V km, V sideBits, uint32_t pai
     // (p = 0: the first push IS the root, the parent of position 1)
     const V now = sel(shared, sel((j1p1 + 1u) < stop1, up, sel((j1p1 + 1u) == stop1, e1, ae)), sel((p1 == 2u) & (R.l4 == 0u), e1, ae));
     const V stop2 = rowStop(ballot((now & km) < ek), R.rowSh);
-    ldsStore32m(lds, dest, sel((R.l4 + 1u) == stop2, e, now), R.isSecond & act & (R.l4 < stop2));
+    ldsStoreSel(lds, dest, sel((R.l4 + 1u) == stop2, e, now), R.isSecond & act & (R.l4 < stop2));
     if (TOPS) tops = sel(((tops & km) < (splat(e2s) & km)) & (cnt > 1u), splat(e2s), tops);  // (a heap's second element is e2s)
   }
   n += cnt;
@@ -491,6 +542,7 @@ WV_ENTRY int32_t compactSearch(Lds window) {
   const uint32_t nAgentsPad = EPS ? MRP_CT_JOB_U32(lds, nAgentsPad) : 0u;
   int32_t status = C_NO_SOLUTION, cost = 0, fmin = 0, nStates = 0;
   uint32_t nOpen = 1, nFocal = EPS ? 1u : 0u, nodes = 1, expansions = 0;
+  uint32_t curG = 0, topG = 0;  // a goal pop: the popped entry and the open list's root
 
   MRP_CT_PROF_DECL;
   // ---- job set-up -------------------------------------------------------------------------------------------
@@ -630,14 +682,44 @@ WV_ENTRY int32_t compactSearch(Lds window) {
     if (EPS) ldsStoreS(lds, oFocal + 4u, e0);
     tops = splat(e0);
   }
+#ifndef MRP_CT_PLAIN_LOOP
+  // Everything that ends the search at a loop top — the goal cell, the tier's three limits, the expansion cap, a walk
+  // that outgrew its queue — as ONE sign test: each term below is negative exactly when its event is there (the operands
+  // are below 2^13, the counts below 2^31), and what does not change during the search is put together here.
+  const int32_t openRoom = (int32_t)openCap - 5;        // nOpen + 5 > openCap  <=>  openRoom - nOpen < 0
+  const uint32_t fhFloor = 2u * nAgentsPad;             // curFh + 2 nAgentsPad > kFhMax  <=>  (kFhMax - curFh) - fhFloor < 0
+  // expansions + 1 > maxExp  <=>  expRoom - expansions < 0   (a cap from 2^31 - 1 on is none: no search counts that far)
+  const int32_t expRoom = (int32_t)(maxExp < 0x7FFFFFFFu ? maxExp : 0x7FFFFFFFu) - 1;
+  int32_t walkOver = 0;                                 // -1 from the walk that outgrew its queue on
+#endif
   sync();
   MRP_CT_PROF_MARK(0);
 
+  // The loop has ONE exit, at its top: the open list is empty.  An exit further down says what it has to say (status, cost)
+  // and empties the count — nothing reads nOpen behind the loop — so that neither the hot path nor the back edge carries a
+  // code that says which exit was taken.  (-DMRP_CT_PLAIN_LOOP: every exit a break of its own)
+#ifndef MRP_CT_PLAIN_LOOP
+#define MRP_CT_LEAVE \
+  {                  \
+    nOpen = 0u;      \
+    continue;        \
+  }
+#else
+#define MRP_CT_LEAVE break;
+#endif
   for (;;) {
+#ifndef MRP_CT_PLAIN_LOOP
+    if (nOpen == 0u) {  // status: C_NO_SOLUTION from the start, unless an exit below has said otherwise
+      MRP_CT_COUNTX(33, status == C_NO_SOLUTION ? 1u : 0u);
+      break;
+    }
+#else
     if (nOpen == 0u) {
+      MRP_CT_COUNTX(33, 1u);
       status = C_NO_SOLUTION;
       break;
     }
+#endif
 #ifdef MRP_CT_LOAD_TOPS
     tops = ldsLoad32(lds, hb);                           // lanes 0..31: open.top(), lanes 32..63: focal.top()
 #elif defined(MRP_CT_CHECK_TOPS)
@@ -695,15 +777,19 @@ WV_ENTRY int32_t compactSearch(Lds window) {
           const uint32_t firstC = 2u * cur + 1u;
           const uint32_t nCh = firstC + 1u < nOpen ? 2u : firstC < nOpen ? 1u : 0u;
           if (npq + 2u > kAuxCap) {
+#ifndef MRP_CT_PLAIN_LOOP
+            walkOver = -1;  // (the loop top below reports it, in front of everything else)
+#else
             status = C_OVERFLOW;
             cost = 4;
+#endif
             break;
           }
           // discover the children (index order) before the node is tested; the node joins the focal list if it is in the band
           const uint32_t e1 = readlane(trio, 0), e2 = readlane(trio, 1);
           const float fv = (float)(int32_t)(kFMax - ((curKey >> kFShift) & kFMax));
           const bool inBand = fv > lo && fv <= hi;
-          pushPairs(lds, Rw, oAux + 4u, kMOAux, npq, nCh, ((e1 & kMO) << kAuxShift) | firstC, ((e2 & kMO) << kAuxShift) | (firstC + 1u),
+          pushPairs<false>(lds, Rw, oAux + 4u, kMOAux, npq, nCh, ((e1 & kMO) << kAuxShift) | firstC, ((e2 & kMO) << kAuxShift) | (firstC + 1u),
                     oFocal + 4u, kMF, nFocal,
                     inBand ? 1u : 0u, eCur, 0u);
           npq += nCh;
@@ -755,7 +841,7 @@ WV_ENTRY int32_t compactSearch(Lds window) {
             if (hole == 0u || !((above & kMOAux) < (value & kMOAux)))
               ldsStoreS(lds, oAux + 4u + 4u * hole, value);  // the usual case: the last element stays at the leaf
             else
-              dualSiftUp(lds, S, hbAux, kmAux, splat(hole + 1u), value, false, false);
+              dualSiftUp<false>(lds, S, hbAux, kmAux, splat(hole + 1u), value, false, false);
           }
         }
         // what the walk leaves in its queue is dropped: every slot "no element" again
@@ -764,7 +850,12 @@ WV_ENTRY int32_t compactSearch(Lds window) {
           const V4 head{sel(lane == 0u, splat(kFront), splat(kEmpty)), splat(kEmpty), splat(kEmpty), splat(kEmpty)};
           ldsStore128m(lds, splat(oAux + b) + lane * 16u, b == 0u ? head : none, (lane * 16u + b) < kAuxBytes);
         }
-        if (status == C_OVERFLOW) break;
+#ifdef MRP_CT_PLAIN_LOOP
+        if (status == C_OVERFLOW) {
+          MRP_CT_COUNTX(39, 1u);
+          break;
+        }
+#endif
         curE = ldsLoadS(lds, oFocal + 4u);
 #ifndef MRP_CT_LOAD_TOPS
         tops = sel(S.isB, splat(curE), tops);            // the walk has pushed into the focal list (and left the open list alone)
@@ -778,52 +869,76 @@ WV_ENTRY int32_t compactSearch(Lds window) {
     const uint32_t cell = curE & 1023u, curFh = kFhMax - (curE >> kFhShift);
     const uint32_t t = C::kLongT ? (kFMax - ((curE >> kFShift) & kFMax)) - (63u - ((curE >> 10) & 63u)) : (curE >> 10) & kGMax;
     const uint32_t x = cell & 31u, y = cell >> 5;
+#ifndef MRP_CT_PLAIN_LOOP
+    // The hot path has one test and one branch for all of its exits; which one it is, is found out in the cold block — in
+    // the order of the plain loop: a walk's overflow, the limits (not for a goal pop), the cap behind the count (onExpandNode
+    // counts the goal pop too), the goal.  cost and status are assigned there alone.  (The goal cell popped at t <= lastGoal
+    // is no goal: it comes back from the cold block and expands.)
+    {
+      int32_t rare = ((int32_t)(cell ^ goalCell) - 1) | (openRoom - (int32_t)nOpen) | ((int32_t)maxT - (int32_t)t) |
+                     (expRoom - (int32_t)expansions) | walkOver;
+      if (EPS && !C::kExactFhCheck) rare |= (int32_t)((curE >> kFhShift) - fhFloor);
+      if (MRP_CT_RARE(rare < 0)) {
+        if (walkOver) {
+          MRP_CT_COUNTX(39, 1u);
+          status = C_OVERFLOW;
+          cost = 4;
+          MRP_CT_LEAVE
+        }
+        const bool isGoal = cell == goalCell && (int32_t)t > lastGoal;
+        // (cost names the limit and `expanded` how far the search got: statistics for the caller, not results)
+        if (!isGoal && (nOpen + 5u > openCap || t > maxT || (EPS && !C::kExactFhCheck && curFh + 2u * nAgentsPad > kFhMax))) {
+          status = C_OVERFLOW;
+          cost = nOpen + 5u > openCap ? 1 : t > maxT ? 2 : 3;
+          MRP_CT_COUNTX(35 + (uint32_t)cost, 1u);
+          MRP_CT_LEAVE
+        }
+        if (expansions + 1u > maxExp) {
+          MRP_CT_COUNTX(35, 1u);
+          expansions += 1u;
+          status = C_CAP_EXP;
+          MRP_CT_LEAVE
+        }
+        MRP_CT_COUNTX(34, isGoal ? 0u : 1u);  // (the goal cell, too early)
+        if (isGoal) {
+          MRP_CT_COUNTX(31, 1u);
+          MRP_CT_COUNTX(32, expansions == 0u ? 1u : 0u);
+          expansions += 1u;
+          status = C_OK;
+          curG = curE;
+          topG = topO;
+          MRP_CT_LEAVE
+        }
+      }
+    }
+    expansions += 1u;  // onExpandNode (a_star_epsilon.hpp:193 / a_star.hpp:87)
+#else
     const bool isGoal = cell == goalCell && (int32_t)t > lastGoal;
     if (!isGoal) {
       // (cost names the limit and `expanded` how far the search got: statistics for the caller, not results)
       if (nOpen + 5u > openCap || t > maxT || (EPS && !C::kExactFhCheck && curFh + 2u * nAgentsPad > kFhMax)) {
         status = C_OVERFLOW;
         cost = nOpen + 5u > openCap ? 1 : t > maxT ? 2 : 3;
+        MRP_CT_COUNTX(35 + (uint32_t)cost, 1u);
         break;
       }
     }
     expansions += 1u;  // onExpandNode (a_star_epsilon.hpp:193 / a_star.hpp:87) — counts the goal pop too
     if (expansions > maxExp) {
+      MRP_CT_COUNTX(35, 1u);
       status = C_CAP_EXP;
       break;
     }
+    MRP_CT_COUNTX(34, !isGoal && cell == goalCell ? 1u : 0u);
     if (isGoal) {
-      // ---- a_star_epsilon.hpp:195-213: follow cameFrom back to the start.  The action bytes of eight time steps (eight
-      // 1 KB rows of the table) are fetched per round trip into the bitmap's LDS area, which the search no longer needs
+      MRP_CT_COUNTX(31, 1u);
+      MRP_CT_COUNTX(32, expansions == 1u ? 1u : 0u);
       status = C_OK;
-      cost = (int32_t)t;
-      fmin = (int32_t)(kFMax - (((EPS ? topO : curE) >> kFShift) & kFMax));
-      nStates = (int32_t)t + 1;
-      uint16_t* outPath = MRP_CT_JOB_PTR(uint16_t, lds, outPath);
-      sync();  // this wave's action stores have left the CU
-      uint32_t c = cell;
-      const uint32_t* tab32 = (const uint32_t*)parentTab;
-      constexpr int32_t kStage = BG ? (int32_t)C::kStageRows : 8;  // (the bitmap's own area holds eight rows)
-      for (int32_t k0 = (int32_t)t; k0 >= 1; k0 -= kStage) {
-        V rowW[kStage][4];
-        for (int32_t r = 0; r < kStage; ++r)
-          for (uint32_t q = 0; q < 4; ++q)
-            rowW[r][q] = (k0 - r >= 1) ? gLoad32Coherent(tab32, splat((uint32_t)(k0 - r) * 256u + q * 64u) + lane) : splat(0u);
-        for (int32_t r = 0; r < kStage; ++r)
-          for (uint32_t q = 0; q < 4; ++q) ldsStore32(lds, splat(oBuild + (uint32_t)r * 1024u + q * 256u) + lane * 4u, rowW[r][q]);
-        sync();
-        for (int32_t r = 0; r < kStage && k0 - r >= 1; ++r) {
-          const uint32_t k = (uint32_t)(k0 - r);
-          gStoreU16m(outPath, splat(k), splat((c & 31u) | ((c >> 5) << 8)), lane == 0u);
-          const uint32_t a = first(ldsLoadU8(lds, splat(oBuild + (uint32_t)r * 1024u + c)));
-          // the parent's cell: undo Wait, Left, Right, Up, Down
-          c = a == 1u ? c + 1u : a == 2u ? c - 1u : a == 3u ? c - 32u : a == 4u ? c + 32u : c;
-        }
-        sync();
-      }
-      gStoreU16m(outPath, splat(0u), splat((c & 31u) | ((c >> 5) << 8)), lane == 0u);
+      curG = curE;
+      topG = topO;
       break;
     }
+#endif
 
     MRP_CT_PROF_MARK(0);
     const uint32_t t1 = t + 1u;
@@ -908,7 +1023,13 @@ WV_ENTRY int32_t compactSearch(Lds window) {
       }
       uint32_t lastO = readlane(lastV, 0);
       const uint32_t lastF = EPS ? readlane(lastV, 32) : kFront;  // (no focal list: a key nothing is better than)
-      ldsStore32m(lds, lastAddr, splat(kEmpty), S.l5 == 0u);  // the vacated slots: "no element"
+      // the vacated slots: "no element".  (Every lane of a side names its side's slot and holds the same value: with all of
+      // them on, the store needs neither a predicate nor the scratch word)
+#ifdef MRP_CT_EXEC_STORES
+      ldsStore32m(lds, lastAddr, splat(kEmpty), S.l5 == 0u);
+#else
+      ldsStore32(lds, lastAddr, splat(kEmpty));
+#endif
       if (EPS && !atRoot) {  // boost erase = bubble to the root (every ancestor of p moves down one level), then pop
         const uint32_t depth = lg2(p + 1u);
         MRP_CT_COUNT(4, p >= 256u ? 1u : 0u);
@@ -916,7 +1037,7 @@ WV_ENTRY int32_t compactSearch(Lds window) {
         const B act = !S.isB & (S.l5 < depth);
         const V ancPos = (splat(p + 1u) >> (S.l5 + 1u)) - 1u;
         const V ae = ldsLoad32(lds, splat(oOpen + 4u) + ancPos * 4u);
-        ldsStore32m(lds, splat(oOpen + 4u) + ((splat(p + 1u) >> S.l5) - 1u) * 4u, ae, act);
+        ldsStoreSel(lds, splat(oOpen + 4u) + ((splat(p + 1u) >> S.l5) - 1u) * 4u, ae, act);
         // ... which has just overwritten the last element if the erased node WAS the last one: it is the node's parent
         // then, and the slot it sat in is vacated after all
         if (p == nOld - 1u && depth != 0u) {
@@ -940,7 +1061,16 @@ WV_ENTRY int32_t compactSearch(Lds window) {
       tops = sel(some, top, splat(kEmpty));
 #endif
       MRP_CT_COUNTX(7, EPS && !atRoot ? 1u : 0u);
+      MRP_CT_COUNTX(40, (nOpen == 0u ? 1u : 0u) + (EPS && nFocal == 0u ? 1u : 0u));      // a pop that empties a list
+      MRP_CT_COUNTX(41, EPS && (nOpen > 31u) != (nFocal > 31u) ? 1u : 0u);              // a second descend block with an idle side
+      MRP_CT_COUNTX(42, EPS && (nOpen > 63u) != (nFocal > 63u) ? 1u : 0u);
+      MRP_CT_COUNTX(43, nOld == 32u || nOld == 33u || nOld == 64u || nOld == 65u ? 1u : 0u);  // a heap crossing 31 / 32, 63 / 64
+      // (hole and x are the same in every lane of a side: what decides is whether the side has anything left)
+#ifdef MRP_CT_EXEC_STORES
       ldsStore32m(lds, hb + hole * 4u, x, (S.l5 == 0u) & some);
+#else
+      ldsStoreSel(lds, hb + hole * 4u, x, some);
+#endif
     }
 
     MRP_CT_PROF_MARK(3);
@@ -1002,9 +1132,10 @@ WV_ENTRY int32_t compactSearch(Lds window) {
       }
     }
     if (EPS && C::kExactFhCheck && ballot(mine & (fhV > kFhMax))) {  // a focalH beyond the entry's field: not a search of this tier
+      MRP_CT_COUNTX(38, 1u);
       status = C_OVERFLOW;
       cost = 3;
-      break;
+      MRP_CT_LEAVE
     }
     const V lowKey = C::kLongT ? (splat(63u + t1) - f) << 10 : splat(t1 << 10);  // g, or 63 - h (h = f - g)
     const V eV = ((splat(kFhMax) - fhV) << kFhShift) | ((splat(kFMax) - f) << kFShift) | lowKey | ncell;
@@ -1056,6 +1187,7 @@ WV_ENTRY int32_t compactSearch(Lds window) {
           MRP_CT_COUNTX(15, two ? 1u : 0u);
           MRP_CT_COUNTX(19, f1 != f2 ? 1u : 0u);             // a focal row 2 alone
           MRP_CT_COUNTX(20, f1 && f2 ? 1u : 0u);             // rows 2 and 3
+          MRP_CT_COUNTX(44, !two && !f1 ? 1u : 0u);          // one push into the open list, none into the focal list
           MRP_CT_COUNTX(21, !f1 && f2 ? 1u : 0u);            // the pair's first successor outside the bound, its second inside
           MRP_CT_COUNTX(22, two && ((pO + 2u) & (pO + 1u)) == 0u ? 1u : 0u);       // the second chain one level deeper: open
           MRP_CT_COUNTX(23, f1 && f2 && ((pF + 2u) & (pF + 1u)) == 0u ? 1u : 0u);  // ... focal
@@ -1086,6 +1218,7 @@ WV_ENTRY int32_t compactSearch(Lds window) {
       const uint32_t e1 = readlane(eV, k1), e2 = readlane(eV, k2);
       const bool f1 = EPS && ((maskF >> k1) & 1u), f2 = EPS && two && ((maskF >> k2) & 1u);
       const uint32_t nX = two ? 2u : 1u, nY = (f1 ? 1u : 0u) + (f2 ? 1u : 0u);
+      MRP_CT_COUNTX(44, !two && !f1 ? 1u : 0u);
 #ifndef MRP_CT_NO_SINGLE_PUSH
       if (!two)  // one successor (the usual case): its two chains side by side, half the bookkeeping
         dualSiftUp(lds, S, hb, km, bothSides(S, nOpen + 1u, f1 ? nFocal + 1u : 1u), e1, false, !f1);
@@ -1105,6 +1238,41 @@ WV_ENTRY int32_t compactSearch(Lds window) {
 #endif
     MRP_CT_PROF_MARK(5);
   }
+#undef MRP_CT_LEAVE
+  if (status == C_OK) {
+    // ---- the goal branch (behind the loop, which a goal pop leaves with the popped entry in curG and the open list's root
+    // in topG: the hot path holds nothing of it)
+    const uint32_t curE = curG, topO = topG, cell = curE & 1023u;
+    const uint32_t t = C::kLongT ? (kFMax - ((curE >> kFShift) & kFMax)) - (63u - ((curE >> 10) & 63u)) : (curE >> 10) & kGMax;
+    // ---- a_star_epsilon.hpp:195-213: follow cameFrom back to the start.  The action bytes of eight time steps (eight
+    // 1 KB rows of the table) are fetched per round trip into the bitmap's LDS area, which the search no longer needs
+    cost = (int32_t)t;
+    fmin = (int32_t)(kFMax - (((EPS ? topO : curE) >> kFShift) & kFMax));
+    nStates = (int32_t)t + 1;
+    uint16_t* outPath = MRP_CT_JOB_PTR(uint16_t, lds, outPath);
+    sync();  // this wave's action stores have left the CU
+    uint32_t c = cell;
+    const uint32_t* tab32 = (const uint32_t*)parentTab;
+    constexpr int32_t kStage = BG ? (int32_t)C::kStageRows : 8;  // (the bitmap's own area holds eight rows)
+    for (int32_t k0 = (int32_t)t; k0 >= 1; k0 -= kStage) {
+      V rowW[kStage][4];
+      for (int32_t r = 0; r < kStage; ++r)
+        for (uint32_t q = 0; q < 4; ++q)
+          rowW[r][q] = (k0 - r >= 1) ? gLoad32Coherent(tab32, splat((uint32_t)(k0 - r) * 256u + q * 64u) + lane) : splat(0u);
+      for (int32_t r = 0; r < kStage; ++r)
+        for (uint32_t q = 0; q < 4; ++q) ldsStore32(lds, splat(oBuild + (uint32_t)r * 1024u + q * 256u) + lane * 4u, rowW[r][q]);
+      sync();
+      for (int32_t r = 0; r < kStage && k0 - r >= 1; ++r) {
+        const uint32_t k = (uint32_t)(k0 - r);
+        gStoreU16m(outPath, splat(k), splat((c & 31u) | ((c >> 5) << 8)), lane == 0u);
+        const uint32_t a = first(ldsLoadU8(lds, splat(oBuild + (uint32_t)r * 1024u + c)));
+        // the parent's cell: undo Wait, Left, Right, Up, Down
+        c = a == 1u ? c + 1u : a == 2u ? c - 1u : a == 3u ? c - 32u : a == 4u ? c + 32u : c;
+      }
+      sync();
+    }
+    gStoreU16m(outPath, splat(0u), splat((c & 31u) | ((c >> 5) << 8)), lane == 0u);
+  }
   // the result block of the window
   ldsStoreS(lds, oRes + (uint32_t)offsetof(CRes, status), (uint32_t)status);
   ldsStoreS(lds, oRes + (uint32_t)offsetof(CRes, cost), (uint32_t)cost);
@@ -1114,6 +1282,7 @@ WV_ENTRY int32_t compactSearch(Lds window) {
   ldsStoreS(lds, oRes + (uint32_t)offsetof(CRes, nodes), nodes);
   MRP_CT_PROF_STORE(lds);
   sync();
+  MRP_CT_DONE(lds);
   return status;
 }
 
@@ -1332,6 +1501,7 @@ WV_ENTRY int32_t compactSearchTA(Lds window) {
   ldsStoreS(lds, oRes + (uint32_t)offsetof(CRes, expanded), expansions);
   ldsStoreS(lds, oRes + (uint32_t)offsetof(CRes, nodes), nodes);
   sync();
+  MRP_CT_DONE(lds);
   return status;
 }
 

@@ -219,13 +219,21 @@ static_assert(sizeof(DevJob) + sizeof(DevResult) <= ct::oJob, "control block of 
   DevJob& jobS = *(DevJob*)(smem + ct::oCtl);                                                         \
   DevResult& resS = *(DevResult*)(smem + ct::oCtl + sizeof(DevJob))
 // A kernel whose whole body is one job loop on the window's blocks
-#define MRP_LL_WINDOW_KERNEL(NAME, ...)                                                  \
+#define MRP_LL_WINDOW_KERNEL_PRE(NAME, PRE, ...)                                         \
   extern "C" __global__ void __launch_bounds__(64) NAME(LaunchParams Parg) {             \
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];                       \
+    PRE;                                                                                 \
     MRP_LL_WINDOW_BLOCKS(smem, jobS, resS);                                              \
     const LaunchParams& P = Parg;                                                        \
     __VA_ARGS__(P, smem, jobS, resS);                                                    \
   }
+#define MRP_LL_WINDOW_KERNEL(NAME, ...) MRP_LL_WINDOW_KERNEL_PRE(NAME, (void)0, __VA_ARGS__)
+// The A*-epsilon-only kernels stay at two waves per SIMD, eight windows per CU: they name vector register 175 once, at
+// their entry, where nothing is live, so their allocation is 176 registers — in the compiler's report, in the code object
+// and in what the runtime grants alike.  (Their own need is 155 since the goal branch of compactSearch, with its 32 staging
+// registers, stands behind the search loop: a third wave, ten windows per CU.  More searches per CU make each one slower,
+// DESIGN.md section 7, so that residency is a change of its own to measure.)
+#define MRP_LL_TWO_WAVES asm volatile("; two waves per SIMD" ::: "v175")
 template <int KIND>
 DEVI void batchLoop(const LaunchParams& P, uint8_t* smem, DevJob& jobS, DevResult& resS) {
   const uint32_t lane = threadIdx.x;
@@ -245,7 +253,7 @@ DEVI void batchLoop(const LaunchParams& P, uint8_t* smem, DevJob& jobS, DevResul
 }
 
 MRP_LL_WINDOW_KERNEL(mrp_ll_search_kernel, batchLoop<0>)  // mixed batches
-MRP_LL_WINDOW_KERNEL(mrp_ll_ecbs_search_kernel, batchLoop<1>)  // A*-epsilon jobs only
+MRP_LL_WINDOW_KERNEL_PRE(mrp_ll_ecbs_search_kernel, MRP_LL_TWO_WAVES, batchLoop<1>)  // A*-epsilon jobs only
 MRP_LL_WINDOW_KERNEL(mrp_ll_cbs_search_kernel, batchLoop<2>)  // A* jobs only
 MRP_LL_WINDOW_KERNEL(mrp_ll_ta_root_kernel, taRootLoop)  // roots of CBS-TA conflict trees (ll_ta_root.h), the A* kernels' window
 MRP_LL_WINDOW_KERNEL(mrp_ll_ta_eps_root_kernel, taEpsRootLoop)  // roots of ECBS-TA conflict trees (ll_ta_eps_root.h), the mixed kernel's window
@@ -453,7 +461,7 @@ DEVI void residentLoop(const LaunchParams& P, uint8_t* smem, DevJob& jobS, DevRe
 }
 
 MRP_LL_WINDOW_KERNEL(mrp_ll_persistent_kernel, residentLoop<false, 0>)  // mixed sessions
-MRP_LL_WINDOW_KERNEL(mrp_ll_ecbs_persistent_kernel, residentLoop<false, 1>)  // A*-epsilon only
+MRP_LL_WINDOW_KERNEL_PRE(mrp_ll_ecbs_persistent_kernel, MRP_LL_TWO_WAVES, residentLoop<false, 1>)  // A*-epsilon only
 // The front / heavy pair of an A*-epsilon session (ll_device.h heavy_q).  Front workgroups are the resident loop above
 // with the narrow compact tier alone — no arena-tier code, hence a smaller register allocation; heavy workgroups wait on
 // the device-side queue the front ones fill, run each search in the WIDE compact geometry (31.4 KB of LDS: open and focal
