@@ -114,7 +114,16 @@ extern "C" {
                            /* _CONSTRAINT_SET; path_ids or _STORE_RESULT with no store reserved.                              */
                            /* Runs in batches and in mixed sessions (mrp_ll_session_begin); the one-algorithm                  */
                            /* sessions and mrp_ll_session_occupancy answer MRP_LL_E_INVALID for it.                          */
-                           /* One tier, the arena (result.tier == 1): any map the context accepts, any number of              */
+                           /* Two tiers.  With MRP_LL_JOB_TRY_LDS the search starts in the LDS tier (result.tier == 0): maps   */
+                           /* up to 32 x 32, at most 64 vertex and 64 edge constraints (after the packer dropped those        */
+                           /* outside the map or the horizon), at most 128 context agents (n_agents rounded up to 16), and a  */
+                           /* launch with the LDS tier on and lds_path_bytes >= 4096 (mrp_ll_configure_tiers; the default).   */
+                           /* Inside it: 1023 nodes, 1023 open and 1023 focal entries (room for five more of each is asked    */
+                           /* in front of every expansion), expanded nodes at t <= min(61, lds_rows - 2), f and h <= 124,     */
+                           /* focalH <= 511.  A job that does not fit is not tried there; a search that outgrows the tier is  */
+                           /* run again from the start by the arena tier (result.tier == 1) — no limit of the LDS tier is     */
+                           /* ever an answer.  Without the flag:                                                              */
+                           /* one tier, the arena (result.tier == 1): any map the context accepts, any number of              */
                            /* constraints, any number of context agents.  Limits, with B = 40 * arena_nodes + 48 bytes:       */
                            /*   time steps  min(max_horizon, B / (8 * dimx * dimy))            -> MRP_LL_CAP_HORIZON          */
                            /*   nodes       (B - 4 * time steps * dimx * dimy - 64) / 48       -> MRP_LL_CAP_NODES            */
@@ -249,6 +258,10 @@ typedef struct mrp_ll_job {
  * path in place of agent_idx's, path_ids' paths for everybody else — and returns its first conflict and its number of
  * conflicts with the result.  Combines with MRP_LL_JOB_HEAVY and MRP_LL_JOB_STORE_RESULT; never changes a result. */
 #define MRP_LL_JOB_SCAN_CONFLICTS 16
+/* MRP_LL_JOB_TRY_LDS (hint, MRP_LL_ASTAR_EPS_TA; the other algorithms ignore it): start the search in that algorithm's LDS
+ * tier (see MRP_LL_ASTAR_EPS_TA above).  No result field but `tier` (0: finished in the LDS tier, 1: arena) ever depends on
+ * it.  Combines with MRP_LL_JOB_NO_GOAL, MRP_LL_JOB_STORE_RESULT and path_ids. */
+#define MRP_LL_JOB_TRY_LDS 128
 #define MRP_LL_JOB_NO_GOAL 2      /* mrp_ll_job.flags, MRP_LL_ASTAR_TA: the agent has no task (cbs_ta.cpp:283-319: h = 0, every
                                    * cell ends the search once time > the agent's last vertex constraint, every Wait is free) */
 

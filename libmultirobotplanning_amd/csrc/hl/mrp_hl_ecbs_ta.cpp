@@ -13,6 +13,7 @@
 // every search is told to leave its path in a slot of it (a root through mrp_ll_ta_eps_root_batch_stored), and a job whose
 // node has every other agent's path there goes out with path_ids instead of a shipped table.  Instances of more than 64
 // agents ignore the knob: their contexts ship, their searches store nothing and their roots go through the unstored call.
+// MRP_HL_TA_EPS_LDS=1 (solve_knobs.hpp TaEpsKnobs; off by default, same results): the jobs of call 3 carry MRP_LL_JOB_TRY_LDS.
 // A translation unit of its own, like csrc/hl/mrp_hl_ta.cpp.
 #include <chrono>
 #include <cstring>
@@ -21,6 +22,7 @@
 
 #include "../../../include/mrp_hl.h"
 #include "ecbs_ta_tree.hpp"
+#include "solve_knobs.hpp"
 #include "ta_batch_setup.hpp"
 
 // The engine's entry point for roots that leave their paths in the store.  A weak reference: an engine library without it
@@ -146,6 +148,7 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
   for (int32_t k = 0; k < n; ++k) trees[k]->w = w;
   // ---- MRP_HL_TA_DEVICE_PATHS: the store and its free list (null: the knob is off, and nothing below differs from before)
   const mrp_hl::ta::TaKnobs knobs = mrp_hl::ta::TaKnobs::read();
+  const bool tryLds = mrp_hl::TaEpsKnobs::read().tryLds;  // MRP_HL_TA_EPS_LDS: the jobs below start in the LDS tier
   PathSlotsP slots;
   if (knobs.devicePaths) {
     int64_t agents = 0;
@@ -308,6 +311,8 @@ extern "C" int mrp_hl_solve_ecbs_ta_batch(int32_t device, float w, const mrp_hl_
         epsJob(jobs[nRootJobs + 2 * q + s], t, t.childAgent[s], t.nodes[t.popped].taskOf[t.childAgent[s]], t.childCons[s].get(), c,
                budgetOf(t), takeSlot(t, nRootResults + 2 * q + s), stores(t) && c.byId(t.childAgent[s]));
     }
+    if (tryLds)
+      for (mrp_ll_job& j : jobs) j.flags |= MRP_LL_JOB_TRY_LDS;
     if (!jobs.empty()) {
       rc = mrp_ll_search_batch(eng.ctx, static_cast<int32_t>(jobs.size()), jobs.data(), res.data() + (nRootResults - nRootJobs));
       if (rc != MRP_LL_SUCCESS) return rc;

@@ -97,4 +97,17 @@ struct SolveKnobs {
   }
 };
 
+// MRP_HL_TA_EPS_LDS=1 (mrp_hl_solve_ecbs_ta_batch, read once per call; off by default, same results): every
+// MRP_LL_ASTAR_EPS_TA search the call sends as an ordinary job — the children's, and the roots' when they go out as dependent
+// jobs — carries MRP_LL_JOB_TRY_LDS and starts in that search's LDS tier (mrp_ll.h).  Roots planned by the root kernels are
+// not jobs and stay as they are.
+struct TaEpsKnobs {
+  bool tryLds = false;
+  static TaEpsKnobs read() {
+    TaEpsKnobs k;
+    if (const char* e = std::getenv("MRP_HL_TA_EPS_LDS")) k.tryLds = std::atoi(e) != 0;
+    return k;
+  }
+};
+
 }  // namespace mrp_hl

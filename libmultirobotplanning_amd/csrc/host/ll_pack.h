@@ -580,6 +580,7 @@ static inline bool packJob(const PackEnv& env, const mrp_ll_job& j, const PackAr
   d.path_off = 0;
   d.heur_off = epsTa ? heurOff : 0;  // (MRP_LL_ASTAR_EPS_TA needs both: the heuristic table and the focal path table)
   if ((j.flags & MRP_LL_JOB_HEAVY) && j.algo == MRP_LL_ASTAR_EPS) d.ctx_flags |= kCtxHeavy;
+  if ((j.flags & MRP_LL_JOB_TRY_LDS) && epsTa) d.ctx_flags |= kCtxTryLds;  // (a hint of this algorithm's; the others ignore it)
   // the result path also goes to a path-store slot only when the caller says so (a zero-initialised job names no slot)
   const bool storeResult = (j.flags & MRP_LL_JOB_STORE_RESULT) != 0;
   d.store_out_id = (storeResult && j.result_path_id >= 0 && static_cast<uint32_t>(j.result_path_id) < env.pathStoreSlots)

@@ -85,6 +85,10 @@ constexpr uint32_t kCtxScan = 128u;
 // slot of the replaced path (the searching agent's at the parent; it is NOT part of the focal table), the parent's number of
 // conflicts, and a time before which the parent has none (ll_node_scan.h nodeScanFromParent).
 constexpr uint32_t kCtxScanParent = 256u;
+// ctx_flags bit 9 (MRP_LL_JOB_TRY_LDS; MRP_LL_ASTAR_EPS_TA only): the search starts in the LDS tier (ll_compact_ta_eps.h) when the
+// job and the launch fit it, and is run again by the arena tier when it outgrows it.  A hint: only DevResult::tier and the
+// profile words depend on it.
+constexpr uint32_t kCtxTryLds = 512u;
 constexpr uint32_t kScanOutHalfs = 32;                             // (64 bytes: the area stays aligned for the path in front of it)
 constexpr uint32_t kChainEntryWords = 8;
 constexpr uint32_t kChainMaxAgents = 128;                          // (what the compact tier's focal context holds: two 64-lane row loads)

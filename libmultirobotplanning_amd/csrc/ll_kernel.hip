@@ -14,11 +14,12 @@
 // included once, here, in dependency order:
 //   ll_slot.h          the arena slot's layout: sizes and scratch areas (also the host's, mrp_ll_create)
 //   ll_compact.h       the compact tier (also compiled for the CPU emulator of the tests)
+//   ll_compact_ta_eps.h  the LDS tier of MRP_LL_ASTAR_EPS_TA, in the same vocabulary and window (likewise)
 //   ll_arena_heap.h    tiers, Mem views, the exact heap emulations, PushChains, the ordered walk
 //   ll_arena_search.h  ensureRows, initSearch, runSearch: the CBS / ECBS search of the arena tier
 //   ll_jobs.h          job staging and bracket, the arena slot's cut, baseCJob, runJob (stageFocalTable, compactAttempt,
 //                      arenaAttempt), publishPath and runChain (ECBS root chains)
-//   ll_ta.h            TaEnv, runTaArena / runJobTA, runJobTaEps: the task-assignment low levels
+//   ll_ta.h            TaEnv, runTaArena / runJobTA, runJobTaEps, runTaEpsLds: the task-assignment low levels
 //   ll_ta_root.h       runTaRoot, taRootLoop: the root node of a CBS-TA conflict tree, searches and scan, by one workgroup
 //   ll_ta_eps_root.h   runTaEpsRoot, taEpsRootLoop: the root node of an ECBS-TA conflict tree, likewise, one table for both
 //   ll_ta_root_wide.h  runTaRootWide, runTaEpsRootWide: their siblings for roots of up to 256 agents, four agents per lane
@@ -43,6 +44,7 @@
 #include "ll_launch.h"
 #include "wave_dev.h"
 #include "ll_compact.h"
+#include "ll_compact_ta_eps.h"
 
 #include "ll_arena_heap.h"
 #include "ll_arena_search.h"
@@ -166,7 +168,9 @@ DEVI bool processJob(const LaunchParams& P, const DevJob* jobSrc, DevResult* res
       runJob<true, false, kTiersAll>(P, J, smem, arenaSlot, res, outPath);
     else if (algo == 3)
       runJobTA(P, J, smem, arenaSlot, res, outPath);
-    else if (algo == 4) {  // MRP_LL_ASTAR_EPS_TA: arena tier only; the result comes back through the staging record
+    else if (algo == 4 && (rfl(J.ctx_flags) & kCtxTryLds) && runTaEpsLds(P, J, smem, arenaSlot, res, outPath)) {
+      // MRP_LL_ASTAR_EPS_TA with MRP_LL_JOB_TRY_LDS: answered in the LDS tier
+    } else if (algo == 4) {  // MRP_LL_ASTAR_EPS_TA: the arena tier; the result comes back through the staging record
       const uint64_t th0 = __builtin_amdgcn_s_memrealtime();
       runJobTaEps<false>(&jobS, &resS, arenaSlot, P.maps, P.cons, P.paths, P.arena_scratch_off, P.out_stride, P.arena_nodes,
                   P.arena_rows, P.arena_row_words, P.arena_paths_bytes, P.path_store, P.path_store_stride, P.path_store_slots);

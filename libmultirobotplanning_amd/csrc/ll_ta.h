@@ -1,6 +1,8 @@
 // The task-assignment low levels: TaEnv (the Environment of cbs_ta / ecbs_ta on the arena's records), runTaArena and
-// runJobTA (MRP_LL_ASTAR_TA: compact tier, then arena), orderedWalkTaEps and runJobTaEps (MRP_LL_ASTAR_EPS_TA).
-// Needs ll_arena_heap.h (heaps, Mem), ll_arena_search.h (ensureRows) and ll_jobs.h (staging, cutArena, cutHeaps).
+// runJobTA (MRP_LL_ASTAR_TA: compact tier, then arena), orderedWalkTaEps and runJobTaEps (MRP_LL_ASTAR_EPS_TA) and, in front
+// of it for a job that asks (MRP_LL_JOB_TRY_LDS), runTaEpsLds.
+// Needs ll_arena_heap.h (heaps, Mem), ll_arena_search.h (ensureRows), ll_jobs.h (staging, cutArena, cutHeaps) and
+// ll_compact_ta_eps.h.
 #ifndef MRP_LL_TA_H
 #define MRP_LL_TA_H
 
@@ -637,6 +639,64 @@ __device__ __attribute__((noinline)) void runJobTaEps(const DevJob* Jp, DevResul
   out->expanded = s.expansions;
   out->nodes_created = s.nNodes;
   out->tier = 1;
+}
+
+// MRP_LL_ASTAR_EPS_TA with MRP_LL_JOB_TRY_LDS (kCtxTryLds): the search in its LDS tier (ll_compact_ta_eps.h
+// ct::compactSearchTaEps), called by processJob in front of runJobTaEps.  True: the tier gave the answer (res.tier = 0).
+// False: the job or the launch does not fit the tier — a map beyond 32 x 32, more than 64 vertex or 64 edge constraints,
+// more than 128 context agents, the tier off or its path area below ct::kTePathBytes, a focal table that does not fit the
+// slot's path area or is refused — or the search outgrew it (prof[6] / prof[7]: the expansions thrown away, as runJobTA);
+// runJobTaEps<false> then runs the job from the start and stages everything again, unchanged.
+// Constraint words and focal table go where runJobTaEps puts them: the slot's copy areas.  The cameFrom table takes the
+// slot's node area, as for every compact tier.
+DEVI bool runTaEpsLds(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t* arenaSlot, DevResult& res, uint16_t* outPath) {
+  const uint32_t lane = threadIdx.x;
+  const uint32_t pathBytes = J.t_pad * J.n_agents_pad * 2;  // multiple of 32
+  const bool byId = (J.ctx_flags & kCtxById) != 0;
+  if (P.lds_nodes == 0 || P.lds_paths_bytes < ct::kTePathBytes || !ct::taEpsJobFits(J.dimx, J.dimy, J.n_vc, J.n_ec, J.n_agents_pad) ||
+      !compactFits<ct::Narrow>(P.arena_nodes, 0, false) || pathBytes > P.arena_paths_bytes || (byId && J.n_ctx > J.n_agents_pad))
+    return false;
+  const uint32_t* vc;
+  const uint32_t* ec;
+  stageConstraints(P.cons, J.vc_off, J.n_vc, J.n_ec, slot::consCopy(arenaSlot, P.arena_scratch_off, P.out_stride), vc, ec);
+  uint8_t* pathsArena = slot::pathsCopy(arenaSlot, P.arena_scratch_off, P.out_stride);
+  if (pathBytes != 0) {
+    if (byId) {
+      buildIdTableInArena((uint16_t*)pathsArena, P.cons + J.path_off, J.n_ctx, J.t_pad, J.n_agents_pad, P.path_store,
+                          P.path_store_stride, P.path_store_slots);
+    } else {
+      const uint32_t* psrc = (const uint32_t*)(P.paths + J.path_off);
+      uint32_t* dst = (uint32_t*)pathsArena;
+      for (uint32_t i = lane; i < pathBytes / 4; i += 64) dst[i] = hostLoad32(psrc + i);
+    }
+  }
+  __syncthreads();
+  ct::CJob cj = baseCJob(P, J, arenaSlot, outPath);
+  cj.sx = J.sx; cj.sy = J.sy; cj.gx = J.gx; cj.gy = J.gy;
+  cj.lastGoal = J.last_goal_constraint;
+  cj.nVc = J.n_vc; cj.nEc = J.n_ec;
+  cj.nAgentsPad = pathBytes ? J.n_agents_pad : 0u; cj.tPad = pathBytes ? J.t_pad : 0u;
+  cj.taNoGoal = (J.ctx_flags & kTaNoGoal) ? 1u : 0u;
+  cj.rows = ct::kTeNodeCap;
+  cj.vc = (uint64_t)vc; cj.ec = (uint64_t)ec;
+  cj.pathsG = (uint64_t)pathsArena;
+  cj.bitsG = (uint64_t)(P.maps + J.heur_off);  // the task's shortest-path table, [32][32] halfwords
+  putCJob(smem, cj);
+  const uint64_t tl0 = __builtin_amdgcn_s_memrealtime();
+  const int32_t crc = ct::compactSearchTaEps((wv::Lds)smem);
+  const ct::CRes cr = getCRes(smem);
+  res.prof[0] = (uint32_t)(__builtin_amdgcn_s_memrealtime() - tl0);
+  res.prof[1] = cr.expanded;
+  if (crc != ct::C_CAP_NODES && crc != ct::C_CAP_HORIZON && crc != ct::C_OVERFLOW) {  // an answer (the ST_ codes, ST_BAD included)
+    res.status = crc; res.cost = cr.cost; res.fmin = cr.fmin; res.n_states = cr.nStates;
+    res.expanded = cr.expanded; res.nodes_created = cr.nodes;
+    res.tier = 0;
+    return true;
+  }
+  res.prof[6] = cr.expanded;  // expansions thrown away with the attempt
+  res.prof[7] = 1;
+  __syncthreads();
+  return false;
 }
 
 }  // namespace mrp
