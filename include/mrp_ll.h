@@ -771,8 +771,9 @@ int mrp_ll_ta_eps_root_batch_stored(mrp_ll_ctx* ctx, float w, int32_t n_roots, c
  * mrp_ll_ta_root_batch_w and mrp_ll_ta_eps_root_batch_w are mrp_ll_ta_root_batch and mrp_ll_ta_eps_root_batch for roots of
  * 1 .. 256 agents (what mrp_ll_assign_series_create_w assigns): the same records, refusals (with 256 in place of 64), one
  * budget per root, MRP_LL_NOT_RUN, planned, ten conflict words, return codes and MRP_LL_E_BUSY, word for word.  Still ONE
- * workgroup per root and ONE launch per call, of kernels of their own (mrp_ll_ta_root_wide_kernel,
- * mrp_ll_ta_eps_root_wide_kernel: each lane keeps four agents); the narrow calls and their kernels are unchanged and go on
+ * workgroup per root and ONE launch per call.  The four root kernels are one source (csrc/ll_ta_root.h, a template over the
+ * algorithm and the agents per lane): mrp_ll_ta_root_wide_kernel and mrp_ll_ta_eps_root_wide_kernel keep four agents in each
+ * lane, the narrow calls' kernels one, and the narrow calls go on
  * refusing 65 agents.  A root of at most 64 agents gets from a _w call exactly what the narrow call returns.
  * The table of a root is  longest path x (n_agents rounded up to 16) x 2  bytes: 256 agents fill the default path area of
  * 128 KiB at 256 time steps.  Beyond it the narrow calls' fall-backs apply unchanged: the CBS-TA call completes the scan with

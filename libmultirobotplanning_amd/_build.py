@@ -20,9 +20,9 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-f
 TARGETS = {
     "libmrp_ll.so": dict(srcs=["ll_kernel.hip", "conflict_kernel.hip", "heur_kernel.hip", "assign_kernel.hip", "mrp_ll_host.cpp"],
                          deps=["ll_device.h", "ll_slot.h", "ll_compact.h", "ll_compact_ta_eps.h", "ll_arena_heap.h", "ll_arena_search.h", "ll_jobs.h", "ll_ta.h",
-                               "ll_ta_root.h", "ll_ta_eps_root.h", "ll_ta_root_wide.h", "ll_sipp.h", "ll_node_scan.h", "wave_dev.h", "wave_dev_bool.h", "heur_bfs.h", "heur_layout.h",
+                               "ll_ta_root.h", "ll_sipp.h", "ll_node_scan.h", "wave_dev.h", "wave_dev_bool.h", "heur_bfs.h", "heur_layout.h",
                                "assign_wave.h", "assign_wave_wide.h", "assign_layout.h", "host/assign_pack.h", "host/assign_series.h",
-                               "host/ll_assign_host.h", "host/ta_root_pack.h", "host/ll_ta_root_host.h", "host/ta_eps_root_pack.h", "host/ll_ta_eps_root_host.h",
+                               "host/ll_assign_host.h", "host/ta_root_pack.h", "host/ll_ta_root_host.h", "host/ta_eps_root_pack.h",
                                "ll_launch.h", "host/ll_pack.h", "host/ll_sipp_table.h", "host/ll_unpack.h", "host/ll_ctx.h",
                                "host/ll_maps.h", "host/ll_heur_host.h", "host/ll_stores.h", "host/ll_batch.h",
                                "host/ll_session.h", "host/ll_session_jobs.h", "host/ll_submit.h", "../../include/mrp_ll.h"],

@@ -123,7 +123,7 @@ constexpr uint32_t kHeurWords = 512;                               // a heuristi
 // of results filled in.
 constexpr uint32_t kTaRootAgentWords = 3;
 constexpr uint32_t kTaRootMaxAgents = 64;                          // (the narrow assignment's limit; one lane per agent)
-constexpr uint32_t kTaRootWideMaxAgents = 256;                     // mrp_ll_ta_root_batch_w / _eps_root_batch_w (ll_ta_root_wide.h):
+constexpr uint32_t kTaRootWideMaxAgents = 256;                     // mrp_ll_ta_root_batch_w / _eps_root_batch_w (ll_ta_root.h GROUPS):
                                                                    // the wide assignment's limit; four agents per lane
 constexpr uint32_t kTaRootPlannedWord = 10;
 constexpr uint32_t kTaRootScanSkipped = 0xFFFFFFFEu;
@@ -134,7 +134,7 @@ constexpr uint32_t kTaRootScanSkipped = 0xFFFFFFFEu;
 #endif
 // Agent a's descriptor out of the root's record `d` (in place) and the agent's three words: word for word what packJob makes
 // for the ordinary unconstrained MRP_LL_ASTAR_TA job with `budget` as its max_expansions.  ONE definition for the workgroup
-// (ll_ta_root.h runTaRoot) and for the check that compares it with packJob's (tests/support/ta_root_pack_check.cpp).
+// (ll_ta_root.h runTaRoot<false, .>) and for the check that compares it with packJob's (tests/support/ta_root_pack_check.cpp).
 MRP_DEV_FN void taRootAgentJob(DevJob& d, uint32_t startGoal, uint32_t heurOff, uint32_t flags, int64_t budget) {
   d.sx = startGoal & 0xFFu; d.sy = (startGoal >> 8) & 0xFFu; d.gx = (startGoal >> 16) & 0xFFu; d.gy = startGoal >> 24;
   d.path_off = heurOff;
@@ -142,7 +142,7 @@ MRP_DEV_FN void taRootAgentJob(DevJob& d, uint32_t startGoal, uint32_t heurOff, 
   d.max_expansions = budget;
   d.n_ctx = 0; d.reserved = 0;
 }
-// The root node of an ECBS-TA conflict tree (mrp_ll_ta_eps_root_batch; ll_ta_eps_root.h): the record and the agent words are
+// The root node of an ECBS-TA conflict tree (mrp_ll_ta_eps_root_batch; ll_ta_root.h, EPS): the record and the agent words are
 // the CBS-TA root's above, with algo MRP_LL_ASTAR_EPS_TA and w.  Agent a's descriptor: what packJob makes for the ordinary
 // unconstrained MRP_LL_ASTAR_EPS_TA job whose shipped context is the paths of agents 0 .. a - 1 — the table's width and rows
 // (0, 0 for agent 0, whose context is empty) —, except path_off: the workgroup's table lies in its slot already.

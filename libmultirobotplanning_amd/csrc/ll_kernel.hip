@@ -20,9 +20,8 @@
 //   ll_jobs.h          job staging and bracket, the arena slot's cut, baseCJob, runJob (stageFocalTable, compactAttempt,
 //                      arenaAttempt), publishPath and runChain (ECBS root chains)
 //   ll_ta.h            TaEnv, runTaArena / runJobTA, runJobTaEps, runTaEpsLds: the task-assignment low levels
-//   ll_ta_root.h       runTaRoot, taRootLoop: the root node of a CBS-TA conflict tree, searches and scan, by one workgroup
-//   ll_ta_eps_root.h   runTaEpsRoot, taEpsRootLoop: the root node of an ECBS-TA conflict tree, likewise, one table for both
-//   ll_ta_root_wide.h  runTaRootWide, runTaEpsRootWide: their siblings for roots of up to 256 agents, four agents per lane
+//   ll_ta_root.h       runTaRoot<EPS, GROUPS>, taRootLoop: the root node of a CBS-TA or an ECBS-TA conflict tree, searches
+//                      and scan, by one workgroup; roots of up to 64 agents, or up to 256 with four agents per lane
 //   ll_sipp.h          SIPP: its tiers, sippLoop, runSipp, processSippJob
 //   ll_node_scan.h     nodeScan, nodeScanFromParent: the conflicts of the conflict-tree node a search has completed (also
 //                      compiled for the CPU)
@@ -51,8 +50,6 @@
 #include "ll_jobs.h"
 #include "ll_ta.h"
 #include "ll_ta_root.h"
-#include "ll_ta_eps_root.h"
-#include "ll_ta_root_wide.h"
 #include "ll_sipp.h"
 #include "ll_node_scan.h"
 
@@ -259,10 +256,11 @@ DEVI void batchLoop(const LaunchParams& P, uint8_t* smem, DevJob& jobS, DevResul
 MRP_LL_WINDOW_KERNEL(mrp_ll_search_kernel, batchLoop<0>)  // mixed batches
 MRP_LL_WINDOW_KERNEL_PRE(mrp_ll_ecbs_search_kernel, MRP_LL_TWO_WAVES, batchLoop<1>)  // A*-epsilon jobs only
 MRP_LL_WINDOW_KERNEL(mrp_ll_cbs_search_kernel, batchLoop<2>)  // A* jobs only
-MRP_LL_WINDOW_KERNEL(mrp_ll_ta_root_kernel, taRootLoop)  // roots of CBS-TA conflict trees (ll_ta_root.h), the A* kernels' window
-MRP_LL_WINDOW_KERNEL(mrp_ll_ta_eps_root_kernel, taEpsRootLoop)  // roots of ECBS-TA conflict trees (ll_ta_eps_root.h), the mixed kernel's window
-MRP_LL_WINDOW_KERNEL(mrp_ll_ta_root_wide_kernel, taRootWideLoop)  // the same for roots of up to 256 agents (ll_ta_root_wide.h)
-MRP_LL_WINDOW_KERNEL(mrp_ll_ta_eps_root_wide_kernel, taEpsRootWideLoop)
+// ll_ta_root.h's one runner, four times (the macro is variadic: a template-id with a comma passes as it stands)
+MRP_LL_WINDOW_KERNEL(mrp_ll_ta_root_kernel, taRootLoop<false, 1>)  // roots of CBS-TA conflict trees, the A* kernels' window
+MRP_LL_WINDOW_KERNEL(mrp_ll_ta_eps_root_kernel, taRootLoop<true, 1>)  // roots of ECBS-TA conflict trees, the mixed kernel's window
+MRP_LL_WINDOW_KERNEL(mrp_ll_ta_root_wide_kernel, taRootLoop<false, kTaRootWideGroups>)  // the same for roots of up to 256 agents
+MRP_LL_WINDOW_KERNEL(mrp_ll_ta_eps_root_wide_kernel, taRootLoop<true, kTaRootWideGroups>)
 
 // SIPP batches (MRP_LL_SIPP jobs only) run in their own kernels so that the CBS/ECBS kernels' register allocation is
 // not widened by a path they never take.  Same queue discipline as mrp_ll_search_kernel.
@@ -634,17 +632,14 @@ extern "C" int mrp_ll_front_heavy_occupancy(int heavy, uint32_t ldsBytes) {
   return mrp::occupancyOf(frontHeavyKernel(heavy), heavy == 1 ? mrp_ll_heavy_lds_bytes() : ldsBytes);
 }
 
-// The roots of CBS-TA conflict trees (ll_ta_root.h): `grid` workgroups share P->n_jobs roots; the window of the A* kernels
-// (mrp_ll_lds_bytes(kind = 2)), so that every search meets the tiers an ordinary MRP_LL_ASTAR_TA batch gives it.
-// wide: the kernel for roots of up to 256 agents (ll_ta_root_wide.h), same window.
-extern "C" hipError_t mrp_ll_launch_ta_root(const mrp::LaunchParams* P, uint32_t grid, uint32_t ldsBytes, int wide, hipStream_t stream) {
-  return mrp::launchWithLds(mrp::kernelFor(wide ? mrp::kTaRootWide : mrp::kTaRoot, 0), P, grid, ldsBytes, stream);
-}
-
-// The roots of ECBS-TA conflict trees (ll_ta_eps_root.h), likewise; the window of the mixed kernel (mrp_ll_lds_bytes(kind = 0)),
-// which is what an ordinary MRP_LL_ASTAR_EPS_TA batch is launched with.
-extern "C" hipError_t mrp_ll_launch_ta_eps_root(const mrp::LaunchParams* P, uint32_t grid, uint32_t ldsBytes, int wide, hipStream_t stream) {
-  return mrp::launchWithLds(mrp::kernelFor(wide ? mrp::kTaEpsRootWide : mrp::kTaEpsRoot, 0), P, grid, ldsBytes, stream);
+// The roots of CBS-TA (eps = 0) or ECBS-TA (eps = 1) conflict trees (ll_ta_root.h): `grid` workgroups share P->n_jobs roots.
+// ldsBytes: the window of the A* kernels (mrp_ll_lds_bytes(kind = 2)) for CBS-TA and of the mixed kernel (kind = 0) for
+// ECBS-TA, so that every search meets the tiers an ordinary MRP_LL_ASTAR_TA / MRP_LL_ASTAR_EPS_TA batch gives it.
+// wide: the kernel for roots of up to 256 agents, same window.
+extern "C" hipError_t mrp_ll_launch_ta_root(const mrp::LaunchParams* P, uint32_t grid, uint32_t ldsBytes, int eps, int wide,
+                                            hipStream_t stream) {
+  const mrp::Role role = eps ? (wide ? mrp::kTaEpsRootWide : mrp::kTaEpsRoot) : (wide ? mrp::kTaRootWide : mrp::kTaRoot);
+  return mrp::launchWithLds(mrp::kernelFor(role, 0), P, grid, ldsBytes, stream);
 }
 
 // The SIPP kernels' LDS is static: no attribute to set.

@@ -63,8 +63,7 @@ int mrp_ll_persistent_occupancy(int kind, uint32_t ldsBytes);
 uint32_t mrp_ll_heavy_lds_bytes(void);
 hipError_t mrp_ll_launch_front_heavy(const mrp::LaunchParams* P, uint32_t grid, uint32_t ldsBytes, int heavy, hipStream_t stream);
 int mrp_ll_front_heavy_occupancy(int heavy, uint32_t ldsBytes);
-hipError_t mrp_ll_launch_ta_root(const mrp::LaunchParams* P, uint32_t grid, uint32_t ldsBytes, int wide, hipStream_t stream);
-hipError_t mrp_ll_launch_ta_eps_root(const mrp::LaunchParams* P, uint32_t grid, uint32_t ldsBytes, int wide, hipStream_t stream);
+hipError_t mrp_ll_launch_ta_root(const mrp::LaunchParams* P, uint32_t grid, uint32_t ldsBytes, int eps, int wide, hipStream_t stream);
 hipError_t mrp_ll_launch_sipp(const mrp::LaunchParams* P, uint32_t grid, hipStream_t stream);
 hipError_t mrp_ll_launch_sipp_persistent(const mrp::LaunchParams* P, uint32_t grid, hipStream_t stream);
 int mrp_ll_sipp_persistent_occupancy(void);

@@ -366,7 +366,7 @@ DEVI bool orderedWalkTaEps(Mem<TierHbm>& m, Mem<TierFocalPos>& mf, SState& s, fl
 
 // A real function (its own register allocation): the kernels that host it keep theirs.  The job is read where the kernel
 // staged it, the result goes to `out` (status, cost, fmin, n_states, expanded, nodes_created, tier).
-// IN_PLACE (ll_ta_eps_root.h): the focal table [t_pad][n_agents_pad] already lies in the slot's path area — where the
+// IN_PLACE (ll_ta_root.h, ECBS-TA): the focal table [t_pad][n_agents_pad] already lies in the slot's path area — where the
 // ordinary job copies its shipped one — and is taken as it is; nothing is copied, path_off is not looked at.  The ordinary
 // job is the IN_PLACE = false instance, which knows two more sources: a table shipped by the host (paths[path_off]), or —
 // kCtxById — the conflict-tree node's paths named by their path-store slots (n_ctx ids at cons[path_off]): the workgroup

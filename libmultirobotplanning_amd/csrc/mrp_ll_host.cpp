@@ -9,10 +9,9 @@
 //                           -> device words and back) and host/assign_series.h (HIP-free: open list and partition)
 //   host/ll_stores.h        path store, constraint store, SIPP tables
 //   host/ll_batch.h         batch mode: launch parameters, submit, wait
-//   host/ll_ta_root_host.h  the roots of CBS-TA conflict trees in one launch, with host/ta_root_pack.h (HIP-free: roots ->
-//                           device words and back)
-//   host/ll_ta_eps_root_host.h  the roots of ECBS-TA conflict trees likewise, with host/ta_eps_root_pack.h; a root whose table
-//                           outgrew its slot is finished here with ordinary jobs and the stand-alone scan
+//   host/ll_ta_root_host.h  the roots of CBS-TA and ECBS-TA conflict trees in one launch, one launcher for both, with
+//                           host/ta_root_pack.h and host/ta_eps_root_pack.h (HIP-free: roots -> device words and back); a root
+//                           whose table outgrew its slot is finished here with ordinary jobs and the stand-alone scan
 //   host/ll_session.h       session mode: begin (allocation, reset, launch), end, heartbeat
 //   host/ll_session_jobs.h  session mode: submit, poll, completion queue
 //   host/ll_submit.h        the submit / poll / wait entry points
@@ -25,7 +24,6 @@
 #include "host/ll_stores.h"
 #include "host/ll_batch.h"
 #include "host/ll_ta_root_host.h"
-#include "host/ll_ta_eps_root_host.h"
 #include "host/ll_session.h"
 #include "host/ll_session_jobs.h"
 #include "host/ll_submit.h"
