@@ -96,6 +96,20 @@ typedef struct mrp_hl_batch_stats {
 int mrp_hl_solve_batch(int32_t device, const mrp_hl_options* opt, int32_t n_instances, const mrp_hl_instance* instances,
                        mrp_hl_solution* solutions, mrp_hl_batch_stats* stats);
 
+/* mrp_hl_solve_batch with the true grid distance to the goal as the low-level heuristic (what example/cbs.cpp:445-557 carries
+ * switched off): the same contract, instances, options, solutions and statistics, but every low-level search of every conflict
+ * tree goes out with MRP_LL_JOB_TABLE_H (mrp_ll.h) and the shortest-path table of its agent's goal.  The call uploads the maps
+ * and computes one table per agent's goal with a single mrp_ll_compute_heuristics per engine, all BEFORE the timed region
+ * (stats->wall_seconds), as the reference builds its Environment before it starts its Timer.  It runs in the rounds
+ * schedule whatever opt->mode says: the session schedule opens one-algorithm sessions, which take no such job.
+ * What changes against mrp_hl_solve_batch: the searches' expansion counts and, where several paths of equal cost exist, the
+ * paths; CBS's cost (the optimum) does not, ECBS's stays within w of it.  The look-ahead, root-chain, device-scan and store
+ * knobs of the session schedule do not apply.
+ * MRP_LL_E_NOMEM: the tables do not fit the engines' maps buffer — the call fails with a message on stderr; it never falls back
+ * to the Manhattan searches. */
+int mrp_hl_solve_batch_table_h(int32_t device, const mrp_hl_options* opt, int32_t n_instances,
+                               const mrp_hl_instance* instances, mrp_hl_solution* solutions, mrp_hl_batch_stats* stats);
+
 /* Persistent form for benchmarking: engines (and their arenas) are created once and reused across batches. */
 typedef struct mrp_hl_solver mrp_hl_solver;
 int mrp_hl_solver_create(int32_t device, int32_t n_threads, const mrp_ll_options* ll_opt, mrp_hl_solver** out);

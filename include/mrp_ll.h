@@ -218,7 +218,7 @@ typedef struct mrp_ll_job {
   int32_t result_path_id;  /* with MRP_LL_JOB_STORE_RESULT: the slot (0 .. n_slots-1) that also receives the result path */
   int32_t flags;           /* MRP_LL_JOB_* bits; 0 = none */
   /* MRP_LL_ASTAR_TA / _EPS_TA: the shortest-path table of this job's goal cell (mrp_ll_upload_heuristic or mrp_ll_compute_heuristics); ignored with
-   * MRP_LL_JOB_NO_GOAL.  (Zero-initialised jobs of the other algorithms never look at it.) */
+   * MRP_LL_JOB_NO_GOAL.  MRP_LL_ASTAR / _EPS: the same with MRP_LL_JOB_TABLE_H.  (Zero-initialised jobs of the other algorithms never look at it.) */
   int32_t heuristic_id;
   int32_t chain_count;     /* MRP_LL_JOB_ROOT_CHAIN: plan at most this many agents (0 = all from agent_idx on): a caller with many
                             * agents cuts the root step into jobs of bounded length; the agents behind come back MRP_LL_NOT_RUN */
@@ -262,6 +262,37 @@ typedef struct mrp_ll_job {
  * tier (see MRP_LL_ASTAR_EPS_TA above).  No result field but `tier` (0: finished in the LDS tier, 1: arena) ever depends on
  * it.  Combines with MRP_LL_JOB_NO_GOAL, MRP_LL_JOB_STORE_RESULT and path_ids. */
 #define MRP_LL_JOB_TRY_LDS 128
+/* MRP_LL_JOB_TABLE_H (MRP_LL_ASTAR and MRP_LL_ASTAR_EPS; the other algorithms ignore it, as they ignore MRP_LL_JOB_TRY_LDS):
+ * admissibleHeuristic(s) is the value of the shortest-path table heuristic_id (mrp_ll_upload_heuristic or
+ * mrp_ll_compute_heuristics) at s's cell instead of the Manhattan distance of ecbs.cpp:276-279 — what example/cbs.cpp:445-557
+ * carries switched off.  Everything else of the search is example/ecbs.cpp / example/cbs.cpp as without the flag: neighbour
+ * order, unit costs (g == time), isSolution by the goal and m_lastGoalConstraint, the focal heuristics, the heaps' tie order,
+ * the binary32 bound, fmin, the expansion count; initial_cost works for MRP_LL_ASTAR as it does without the flag.  (A flag,
+ * because a zero-initialised job has heuristic_id == 0, which is a valid id.)
+ * The engine does not know which cell a table was made for: naming the table of the job's OWN goal is the caller's duty.  A
+ * table of another cell (of the same map) may give a wrong path and nothing else: no access outside the job's buffers, no
+ * search that ignores its caps.
+ * A start whose table value is "unreachable" cannot reach the goal at all (a reachable cell has only reachable neighbours, so
+ * the case arises nowhere else): the job comes back MRP_LL_NO_SOLUTION with expanded == 0 and no path, where the Manhattan
+ * search would run into a cap.
+ * Limit: f = g + h of the start and of every generated successor is at most 2045 (the arena tier's heap entry has an 11-bit f
+ * field; the Manhattan h is bounded by the map and never had to be tested).  A start or a successor beyond it ends the job
+ * MRP_LL_CAP_HORIZON, as it does for the task-assignment searches.  The other limits are those of the job without the flag:
+ * arena_nodes -> MRP_LL_CAP_NODES, max_horizon -> MRP_LL_CAP_HORIZON.  Any map the context accepts.
+ * Two tiers, as without the flag.  On a map up to 32 x 32, with at most 64 edge constraints and 128 context agents, under a
+ * launch with the LDS tier on and lds_path_bytes >= 2048 (mrp_ll_configure_tiers; the default is 4096), the search starts in
+ * the narrow LDS tier (result.tier == 0): the table's 2048 bytes stand in the window's path area, together with the focal path
+ * table where both fit (otherwise the focal table is read from the arena slot).  Inside it: 1023 open entries, expanded nodes at
+ * t <= 61, focalH <= 511, and f <= 124 for the start and for every generated successor (the tier's 7-bit f field).  A search
+ * that outgrows one of these is run again from the start by the arena tier (result.tier == 1) — no limit of the LDS tier is ever
+ * an answer.  A job that is answered before any search (the unreachable start above) reports tier 1.  The wide LDS geometry of
+ * the heavy workgroups and the one-algorithm kernels have no table form.
+ * MRP_LL_BAD_JOB, never a silent Manhattan search: heuristic_id unknown or of another map than map_id; the flag together
+ * with MRP_LL_JOB_STORE_RESULT, _ROOT_CHAIN, _HEAVY, _SCAN_CONFLICTS, _SCAN_FROM_PARENT or _CONSTRAINT_SET, or with
+ * path_ids; a flagged job in a one-algorithm session (mrp_ll_session_begin_algo / _tiers / _tiers_gated).  Runs in
+ * mrp_ll_search_batch / mrp_ll_submit and in mixed sessions (mrp_ll_session_begin); a batch that holds a flagged job runs in
+ * the mixed kernel. */
+#define MRP_LL_JOB_TABLE_H 256
 #define MRP_LL_JOB_NO_GOAL 2      /* mrp_ll_job.flags, MRP_LL_ASTAR_TA: the agent has no task (cbs_ta.cpp:283-319: h = 0, every
                                    * cell ends the search once time > the agent's last vertex constraint, every Wait is free) */
 

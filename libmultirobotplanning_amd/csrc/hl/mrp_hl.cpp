@@ -40,6 +40,10 @@ using namespace mrp_hl;
 // library without it still loads, and its front workgroups keep their tables in LDS.
 extern "C" __attribute__((weak)) int mrp_ll_session_front_tables(mrp_ll_ctx* ctx, int32_t in_memory);
 
+// mrp_ll_compute_heuristics likewise (mrp_hl_solve_batch_table_h): without it that call answers MRP_LL_E_INVALID.
+extern "C" __attribute__((weak)) int mrp_ll_compute_heuristics(mrp_ll_ctx* ctx, int32_t n, const int32_t* map_ids, const int32_t* goals_xy,
+                                                               int32_t* heuristic_ids);
+
 struct mrp_hl_preloaded {
   mrp_hl_solver* owner = nullptr;
   int32_t nInst = 0;
@@ -412,6 +416,106 @@ int mrp_hl_solve_batch(int32_t device, const mrp_hl_options* opt, int32_t nInst,
   int rc = mrp_hl_solver_create(device, opt ? opt->n_threads : 0, nullptr, &s);
   if (rc != MRP_LL_SUCCESS) return rc;
   rc = mrp_hl_solver_solve(s, opt, nInst, instances, solutions, stats);
+  mrp_hl_solver_destroy(s);
+  return rc;
+}
+
+// mrp_hl.h: mrp_hl_solve_batch's contract with every search under MRP_LL_JOB_TABLE_H.  The rounds schedule whatever opt->mode
+// says (the session schedule opens one-algorithm sessions, which take no such job); maps and tables are on the engines before
+// the timed region starts: one mrp_ll_compute_heuristics per engine for the goals of all agents of that engine's instances.
+int mrp_hl_solve_batch_table_h(int32_t device, const mrp_hl_options* optIn, int32_t nInst, const mrp_hl_instance* instances,
+                               mrp_hl_solution* solutions, mrp_hl_batch_stats* stats) {
+  if (!optIn || nInst < 0 || (nInst > 0 && (!instances || !solutions))) return MRP_LL_E_INVALID;
+  if (&mrp_ll_compute_heuristics == nullptr) {
+    std::fprintf(stderr, "mrp_hl_solve_batch_table_h: the low-level library has no mrp_ll_compute_heuristics\n");
+    return MRP_LL_E_INVALID;
+  }
+  mrp_hl_options opt = *optIn;
+  opt.mode = 1;
+  mrp_hl_solver* s = nullptr;
+  int rc = mrp_hl_solver_create(device, opt.n_threads, nullptr, &s);
+  if (rc != MRP_LL_SUCCESS) return rc;
+  mrp_hl_preloaded* pre = nullptr;
+  rc = mrp_hl_solver_preload(s, opt.n_threads, nInst, instances, &pre);
+  if (rc != MRP_LL_SUCCESS) {
+    std::fprintf(stderr, "mrp_hl_solve_batch_table_h: %s\n", s->err.c_str());
+    mrp_hl_solver_destroy(s);
+    return rc;
+  }
+  const int32_t nRun = static_cast<int32_t>(pre->idx.size());
+  std::vector<int64_t> agentFirst(static_cast<size_t>(nInst) + 1, 0);
+  for (int32_t k = 0; k < nInst; ++k) agentFirst[k + 1] = agentFirst[k] + std::max(instances[k].n_agents, 0);
+  const int64_t nTables = agentFirst[nInst];
+  std::vector<std::vector<int32_t>> heurIds(static_cast<size_t>(nRun));
+  std::vector<int> rcs(static_cast<size_t>(nRun), MRP_LL_SUCCESS);
+  if (nTables > INT32_MAX) rc = MRP_LL_E_INVALID;
+  if (rc == MRP_LL_SUCCESS) {
+    std::vector<int32_t> goals(static_cast<size_t>(nTables) * 2);
+    for (int32_t k = 0; k < nInst; ++k)
+      if (instances[k].n_agents > 0)
+        std::memcpy(goals.data() + agentFirst[k] * 2, instances[k].goals_xy, sizeof(int32_t) * 2 * static_cast<size_t>(instances[k].n_agents));
+    std::vector<std::thread> th;
+    for (int32_t t = 0; t < nRun; ++t)
+      th.emplace_back([&, t]() {
+        // the tables of THIS engine's instances (the rounds schedule's static split), one launch
+        std::vector<int32_t> mapIds, goalsT, ids;
+        for (int32_t k : pre->idx[t])
+          for (int64_t q = agentFirst[k]; q < agentFirst[k + 1]; ++q) {
+            mapIds.push_back(pre->mapBase[t] + k);
+            goalsT.push_back(goals[2 * q]);
+            goalsT.push_back(goals[2 * q + 1]);
+          }
+        ids.assign(mapIds.size(), -1);
+        rcs[t] = mrp_ll_compute_heuristics(s->engines[t], static_cast<int32_t>(mapIds.size()), mapIds.data(), goalsT.data(), ids.data());
+        heurIds[t].assign(static_cast<size_t>(nTables), -1);
+        size_t n = 0;
+        for (int32_t k : pre->idx[t])
+          for (int64_t q = agentFirst[k]; q < agentFirst[k + 1]; ++q) heurIds[t][q] = ids[n++];
+      });
+    for (auto& x : th) x.join();
+    for (int32_t t = 0; t < nRun && rc == MRP_LL_SUCCESS; ++t)
+      if (rcs[t] != MRP_LL_SUCCESS) {  // MRP_LL_E_NOMEM: the tables do not fit the maps buffer — no fall-back to Manhattan
+        rc = rcs[t];
+        std::fprintf(stderr, "mrp_hl_solve_batch_table_h: %s\n", llError("mrp_ll_compute_heuristics", s->engines[t]).c_str());
+      }
+  }
+  if (rc == MRP_LL_SUCCESS) {
+    const int32_t horizon = s->llOpt.max_horizon > 0 ? s->llOpt.max_horizon : 512;
+    std::vector<GroupResult> gr(static_cast<size_t>(nRun));
+    auto t0 = std::chrono::steady_clock::now();
+    {
+      std::vector<std::thread> th;
+      for (int32_t t = 0; t < nRun; ++t)
+        th.emplace_back([&, t]() {
+          pinWorker(t);
+          runGroup(s->engines[t], opt, instances, solutions, pre->idx[t], pre->mapBase[t], horizon, gr[t], heurIds[t].data(),
+                   agentFirst.data());
+        });
+      for (auto& x : th) x.join();
+    }
+    auto t1 = std::chrono::steady_clock::now();
+    mrp_hl_batch_stats st;
+    std::memset(&st, 0, sizeof(st));
+    st.wall_seconds = std::chrono::duration<double>(t1 - t0).count();
+    for (auto& g : gr) {
+      if (!g.err.empty()) {
+        std::fprintf(stderr, "mrp_hl_solve_batch_table_h: %s\n", g.err.c_str());
+        rc = MRP_LL_E_DEVICE;
+        break;
+      }
+      st.rounds += g.rounds;
+      st.ll_searches += g.searches;
+      st.ll_expansions += g.expansions;
+      st.build_seconds += g.buildS;
+      st.ll_call_seconds += g.llS;
+      st.consume_seconds += g.consumeS;
+    }
+    if (rc == MRP_LL_SUCCESS) {
+      for (int32_t k = 0; k < nInst; ++k) st.solved += solutions[k].status == MRP_HL_SOLVED ? 1 : 0;
+      if (stats) *stats = st;
+    }
+  }
+  mrp_hl_preloaded_free(pre);
   mrp_hl_solver_destroy(s);
   return rc;
 }

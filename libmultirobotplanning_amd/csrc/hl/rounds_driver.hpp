@@ -10,8 +10,11 @@ namespace mrp_hl {
 
 // Drives instances idx[...] (map ids mapBase + idx[...]) to completion on one engine, one mrp_ll_search_batch per round
 // of ready searches.
+// heurIds (mrp_hl_solve_batch_table_h; nullptr: the Manhattan searches): every search goes out with MRP_LL_JOB_TABLE_H and the
+// table of its agent's goal on this engine, heurIds[agentFirst[instance] + agent].
 inline void runGroup(mrp_ll_ctx* ctx, const mrp_hl_options& opt, const mrp_hl_instance* instIn, mrp_hl_solution* sols,
-              const std::vector<int32_t>& idx, int32_t mapBase, int32_t horizon, GroupResult& out) {
+              const std::vector<int32_t>& idx, int32_t mapBase, int32_t horizon, GroupResult& out,
+              const int32_t* heurIds = nullptr, const int64_t* agentFirst = nullptr) {
   const size_t n = idx.size();
   std::vector<std::unique_ptr<Instance>> inst(n);
   for (size_t k = 0; k < n; ++k) inst[k].reset(new Instance(instIn[idx[k]], mapBase + idx[k], opt));
@@ -29,7 +32,13 @@ inline void runGroup(mrp_ll_ctx* ctx, const mrp_hl_options& opt, const mrp_hl_in
     auto tA = clockNow();
     batch.clear();
     for (size_t k = 0; k < n; ++k)
-      for (const LLRequest& r : req[k]) batch.add(*inst[k], r);
+      for (const LLRequest& r : req[k]) {
+        mrp_ll_job& j = batch.add(*inst[k], r);
+        if (heurIds) {
+          j.flags |= MRP_LL_JOB_TABLE_H;
+          j.heuristic_id = heurIds[agentFirst[idx[k]] + r.agent];
+        }
+      }
     if (jobs.empty()) break;
     batch.patch();
     results.assign(jobs.size(), mrp_ll_result());

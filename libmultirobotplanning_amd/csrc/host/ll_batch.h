@@ -140,8 +140,10 @@ int batchSubmit(mrp_ll_ctx* ctx, const SubmitArgs& a, int32_t* ticketOut) {
     t.sipp = nSipp != 0;
     int nEps = 0, nEpsTa = 0;
     for (int i = 0; i < nJobs; ++i) nEps += jobs[i].algo == MRP_LL_ASTAR_EPS ? 1 : 0;
-    for (int i = 0; i < nJobs; ++i) nEpsTa += jobs[i].algo == MRP_LL_ASTAR_EPS_TA ? 1 : 0;
-    // a one-algorithm batch runs the specialised kernel; MRP_LL_ASTAR_EPS_TA lives in the mixed kernel only
+    for (int i = 0; i < nJobs; ++i)  // (a table-h job counts as a job of another algorithm)
+      nEpsTa += (jobs[i].algo == MRP_LL_ASTAR_EPS_TA ||
+                 ((jobs[i].flags & MRP_LL_JOB_TABLE_H) && (jobs[i].algo == MRP_LL_ASTAR || jobs[i].algo == MRP_LL_ASTAR_EPS))) ? 1 : 0;
+    // a one-algorithm batch runs the specialised kernel; MRP_LL_ASTAR_EPS_TA and MRP_LL_JOB_TABLE_H live in the mixed kernel only
     t.kind = (t.sipp || nEpsTa != 0) ? 0 : nEps == nJobs ? 1 : nEps == 0 ? 2 : 0;
   }
   t.jobs.clear();

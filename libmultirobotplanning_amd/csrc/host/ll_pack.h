@@ -428,6 +428,17 @@ static inline bool packJob(const PackEnv& env, const mrp_ll_job& j, const PackAr
   // constraint set and no conflict scan: both ask for MRP_LL_ASTAR / MRP_LL_ASTAR_EPS); the path store as MRP_LL_ASTAR_EPS has it
   if (epsTa && (j.initial_cost != 0 || (j.flags & (MRP_LL_JOB_ROOT_CHAIN | MRP_LL_JOB_HEAVY)))) return false;
   if (j.initial_cost < 0 || j.initial_cost >= 0x40000000) return false;  // (bit 30 of the per-job word marks MRP_LL_ASTAR_TA, jobInitOf)
+  // MRP_LL_JOB_TABLE_H (mrp_ll.h): h from a shortest-path table.  A plain search of the mixed kernels: none of the stores, hints
+  // and scans, no one-algorithm session — refused, never run as a Manhattan search.
+  const bool tableH = (j.flags & MRP_LL_JOB_TABLE_H) != 0 && (j.algo == MRP_LL_ASTAR || j.algo == MRP_LL_ASTAR_EPS);
+  if (tableH) {
+    if ((j.flags & (MRP_LL_JOB_STORE_RESULT | MRP_LL_JOB_ROOT_CHAIN | MRP_LL_JOB_HEAVY | MRP_LL_JOB_SCAN_CONFLICTS |
+                    MRP_LL_JOB_SCAN_FROM_PARENT | MRP_LL_JOB_CONSTRAINT_SET)) != 0 || j.path_ids)
+      return false;
+    if (env.session.active && (env.session.sipp || env.session.kind != 0)) return false;
+    if (j.heuristic_id < 0 || j.heuristic_id >= static_cast<int32_t>(env.heurs.size()) || env.heurs[j.heuristic_id].mapId != j.map_id)
+      return false;
+  }
   // The agent's set by its slot in the constraint store (mrp_ll.h mrp_ll_submit_sets): the arrays are the additions.
   const bool bySet = (j.flags & MRP_LL_JOB_CONSTRAINT_SET) != 0;
   const ConsSetRec* baseSet = nullptr;
@@ -579,6 +590,11 @@ static inline bool packJob(const PackEnv& env, const mrp_ll_job& j, const PackAr
   d.t_pad = 0;
   d.path_off = 0;
   d.heur_off = epsTa ? heurOff : 0;  // (MRP_LL_ASTAR_EPS_TA needs both: the heuristic table and the focal path table)
+  if (tableH) {
+    d.heur_off = env.heurs[j.heuristic_id].wordOff;
+    d.ctx_flags |= kCtxTableH;
+    d.algo = kAlgoTableH | static_cast<uint32_t>(j.algo);
+  }
   if ((j.flags & MRP_LL_JOB_HEAVY) && j.algo == MRP_LL_ASTAR_EPS) d.ctx_flags |= kCtxHeavy;
   if ((j.flags & MRP_LL_JOB_TRY_LDS) && epsTa) d.ctx_flags |= kCtxTryLds;  // (a hint of this algorithm's; the others ignore it)
   // the result path also goes to a path-store slot only when the caller says so (a zero-initialised job names no slot)

@@ -31,10 +31,13 @@ DEVI void ensureRows(Mem<T>& m, SState& s, const Ctx& c, uint32_t t1) {
 }
 
 // ---- one search in one tier ------------------------------------------------------------------------------------
-template <class T, bool EPS>
-DEVI void initSearch(Mem<T>& m, SState& s, const Ctx& c) {
+// TH (MRP_LL_JOB_TABLE_H): admissibleHeuristic is a halfword of the shortest-path table `heur` (rows of heurStride halfwords)
+// instead of the Manhattan distance; the caller has made sure that the start's value fits the entry's f field.
+template <class T, bool EPS, bool TH = false>
+DEVI void initSearch(Mem<T>& m, SState& s, const Ctx& c, const uint16_t* heur = nullptr, uint32_t heurStride = 0) {
   static_assert(T::AS == 1 && T::kWideNodes, "the arena tier: heaps, bitmap and four-word node records in global memory");
   uint32_t h0 = (c.sx > c.gx ? c.sx - c.gx : c.gx - c.sx) + (c.sy > c.gy ? c.sy - c.gy : c.gy - c.sy);
+  if constexpr (TH) h0 = rfl(heur[c.sy * heurStride + c.sx]);
   s.nNodes = 1;
   s.nOpen = 1;
   s.nFocal = EPS ? 1 : 0;
@@ -57,9 +60,12 @@ DEVI void initSearch(Mem<T>& m, SState& s, const Ctx& c) {
 // expansion's nodes / time step: runJob reports those as ST_CAP_NODES / ST_CAP_HORIZON.  (Nothing migrates any more; the
 // two codes stay out of band because returning the statuses directly makes the compiler allocate registers differently in
 // every kernel that hosts this search — a change for a pull request that measures it.)
+// TH: a successor whose f = g + h does not fit the entry's field ends the search ST_CAP_HORIZON (the Manhattan h is bounded
+// by the map and needs no test), as the task-assignment searches do (ll_ta.h TaEnv::fits).
 enum : int { RUN_MIGRATE_NODES = -1, RUN_MIGRATE_ROWS = -2 };
-template <class T, bool EPS>
-DEVI int runSearch(Mem<T>& m, SState& s, const Ctx& c, DevResult& res, uint16_t* outPath) {
+template <class T, bool EPS, bool TH = false>
+DEVI int runSearch(Mem<T>& m, SState& s, const Ctx& c, DevResult& res, uint16_t* outPath, const uint16_t* heur = nullptr,
+                   uint32_t heurStride = 0) {
   static_assert(T::AS == 1 && T::kWideNodes, "the arena tier: heaps, bitmap and four-word node records in global memory");
   typedef typename T::E E;
   const uint32_t lane = threadIdx.x;
@@ -203,8 +209,12 @@ DEVI int runSearch(Mem<T>& m, SState& s, const Ctx& c, DevResult& res, uint16_t*
     const bool mine = (lane < 5) && ((mask >> lane) & 1u);
     const uint32_t nBase = s.nNodes;
     const uint32_t nid = nBase + (uint32_t)__builtin_popcount(mask & ((1u << lane) - 1u));
-    const uint32_t h = (nx > c.gx ? nx - c.gx : c.gx - nx) + (ny > c.gy ? ny - c.gy : c.gy - ny);
+    uint32_t h = (nx > c.gx ? nx - c.gx : c.gx - nx) + (ny > c.gy ? ny - c.gy : c.gy - ny);
+    if constexpr (TH) h = mine ? heur[ny * heurStride + nx] : 0u;  // (a lane without a successor has no cell to look up)
     const uint32_t f = t1 + h;
+    if constexpr (TH) {
+      if (ballot64(mine && f > kFMax - 2u)) return ST_CAP_HORIZON;
+    }
     uint32_t fh = curFh;
     if (EPS && c.nAgentsPad) {
       // focalStateHeuristic (ecbs.cpp:282-295) + focalTransitionHeuristic (ecbs.cpp:298-312): lanes hold the other

@@ -519,8 +519,15 @@ WV_FN void pushTurn(Lds lds, const Rows& R, V hb, V km, V sideBits, uint32_t pai
 // vector-memory instruction is the cameFrom store — so nothing in it ever waits on vmcnt.
 // BG: the (time, cell) bitmap is in device memory (CJob::bitsG): one masked load per expansion, requested before the pops,
 // and one merged store per touched word (the Wait / Left / Right successors share theirs).
-template <bool EPS, bool PLDS, bool BG = false, class C = Narrow>
+// TH (MRP_LL_JOB_TABLE_H; narrow geometry, bitmap in the window): admissibleHeuristic is a halfword of the goal's shortest-path
+// table, [y * 32 + x] (0xFFFF: unreachable), instead of the Manhattan distance.  CJob::bitsG — free in a BG = false instance —
+// names the table in device memory; its 2048 bytes are copied into the window's path area at job start, behind the focal path
+// table of a PLDS instance (the launcher has made sure that both fit), and h is read from LDS.  With a table the static
+// bound "f = g + h fits its field" (TierCfg) does not hold: the start's h and every generated successor's f are tested
+// against kFMax - 3, and one beyond it makes the search C_OVERFLOW — the rule kExactFhCheck follows for focalH.
+template <bool EPS, bool PLDS, bool BG = false, class C = Narrow, bool TH = false>
 WV_ENTRY int32_t compactSearch(Lds window) {
+  static_assert(!TH || (!BG && !C::kLongT), "the table form: narrow geometry, bitmap in the window");
   // the geometry of this instance (the names below hide the narrow tier's at namespace scope)
   constexpr uint32_t kGroups = C::kGroups, kHeapClamp = C::kHeapClamp, kAuxCap = C::kAuxCap, kAuxBytes = C::kAuxBytes,
                      kAuxClamp = C::kAuxClamp, kRows = C::kRows, kBitsBytes = C::kBitsBytes;
@@ -673,9 +680,25 @@ WV_ENTRY int32_t compactSearch(Lds window) {
   const uint32_t goalCell = gx | (gy << 5);
   int32_t bestF;
   V tops;  // the roots: lane 0 open.top(), lane 32 focal.top() (an empty list: kEmpty, whose key every push is better than)
+  // TH: where the shortest-path table stands in the window, and whether the start's h is beyond the entry's f field
+  const uint32_t oHeur = oPathsX + ((TH && EPS && PLDS) ? tPad * nAgentsPad * 2u : 0u);
+  bool h0Over = false;
+  if constexpr (TH) {
+    const uint32_t* heur = MRP_CT_JOB_PTR(const uint32_t, lds, bitsG);
+    for (uint32_t q = 0; q < 8u; ++q) ldsStore32(lds, splat(oHeur + q * 256u) + lane * 4u, gLoad32m(heur, splat(q * 64u) + lane, bsplat(true)));
+    sync();
+  }
   {
     const uint32_t sx = MRP_CT_JOB_U32(lds, sx), sy = MRP_CT_JOB_U32(lds, sy);
-    const uint32_t h0 = (sx > gx ? sx - gx : gx - sx) + (sy > gy ? sy - gy : gy - sy);
+    uint32_t h0 = (sx > gx ? sx - gx : gx - sx) + (sy > gy ? sy - gy : gy - sy);
+    if constexpr (TH) {
+      h0 = first(ldsLoadU16(lds, splat(oHeur + ((sx & 31u) | ((sy & 31u) << 5)) * 2u)));
+      h0Over = h0 > kFMax - 3u;
+      if (h0Over) {  // not a search of this tier: nothing is expanded
+        h0 = kFMax - 3u;
+        nOpen = 0u;
+      }
+    }
     bestF = (int32_t)h0;
     const uint32_t e0 = (kFhMax << kFhShift) | ((kFMax - h0) << kFShift) | ((C::kLongT ? 63u - h0 : 0u) << 10) | (sx | (sy << 5));
     ldsStoreS(lds, oOpen + 4u, e0);
@@ -1096,7 +1119,15 @@ WV_ENTRY int32_t compactSearch(Lds window) {
 #else
     const B mine = (lane < 5u) & (((splat(mask) >> lane) & 1u) != 0u);
 #endif
-    const V f = sad(nx, splat(gx), sad(ny, splat(gy), splat(t1)));  // g + admissibleHeuristic (ecbs.cpp:276-279)
+    V f = sad(nx, splat(gx), sad(ny, splat(gy), splat(t1)));  // g + admissibleHeuristic (ecbs.cpp:276-279)
+    if constexpr (TH) {
+      f = splat(t1) + ldsLoadU16(lds, splat(oHeur) + ncell * 2u);  // (ncell is inside the table for every lane)
+      if (ballot(mine & (f > kFMax - 3u))) {  // an f beyond the entry's field: not a search of this tier
+        status = C_OVERFLOW;
+        cost = 4;
+        MRP_CT_LEAVE
+      }
+    }
     V fhV = splat(curFh);
     if (EPS && nAgentsPad) {
       // focalStateHeuristic (ecbs.cpp:282-295) + focalTransitionHeuristic (ecbs.cpp:298-312): an agent counts once if it
@@ -1239,6 +1270,12 @@ WV_ENTRY int32_t compactSearch(Lds window) {
     MRP_CT_PROF_MARK(5);
   }
 #undef MRP_CT_LEAVE
+  if constexpr (TH) {
+    if (h0Over) {
+      status = C_OVERFLOW;
+      cost = 5;
+    }
+  }
   if (status == C_OK) {
     // ---- the goal branch (behind the loop, which a goal pop leaves with the popped entry in curG and the open list's root
     // in topG: the hot path holds nothing of it)

@@ -89,7 +89,14 @@ constexpr uint32_t kCtxScanParent = 256u;
 // job and the launch fit it, and is run again by the arena tier when it outgrows it.  A hint: only DevResult::tier and the
 // profile words depend on it.
 constexpr uint32_t kCtxTryLds = 512u;
-constexpr uint32_t kScanOutHalfs = 32;                             // (64 bytes: the area stays aligned for the path in front of it)
+// ctx_flags bit 10 (MRP_LL_JOB_TABLE_H; MRP_LL_ASTAR / MRP_LL_ASTAR_EPS): h comes from the shortest-path table at word offset
+// heur_off of the maps buffer (rows of 32 halfwords on maps up to 32 x 32, of dimx beyond; 0xFFFF: unreachable) instead of the
+// Manhattan distance.  Such a job's algo word is kAlgoTableH | MRP_LL_ASTAR or MRP_LL_ASTAR_EPS: an algorithm of its own to the
+// kernels, so that only the mixed ones (processJob<0>) run it and the one-algorithm kernels leave it ST_BAD as they leave
+// every job that is not theirs.
+constexpr uint32_t kCtxTableH = 1024u;
+constexpr uint32_t kAlgoTableH = 0x100u;
+constexpr uint32_t kScanOutHalfs = 32;                            // (64 bytes: the area stays aligned for the path in front of it)
 constexpr uint32_t kChainEntryWords = 8;
 constexpr uint32_t kChainMaxAgents = 128;                          // (what the compact tier's focal context holds: two 64-lane row loads)
 constexpr uint32_t kChainRows = 64;                                // rows of the chain's focal table (the compact tier ends at t = 62)

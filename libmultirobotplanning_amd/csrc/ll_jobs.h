@@ -334,9 +334,12 @@ DEVI bool stageFocalTable(const LaunchParams& P, const DevJob& J, uint8_t* ldsPa
 // to 32 x 32 and up to 128 agents in the focal context; a search that outgrows the tier (open list, time steps, focalH
 // field) comes back as C_OVERFLOW with nothing of it observable, and is run again from the start by the next tier.
 // Returns true when the search ended here: its answer is in rc, res and s.
-template <bool EPS, bool BG, int TIERS>
+// TH (runJobTableH): the table form of the narrow tier (ll_compact.h): h from the 2 KiB table `heur`, which the search copies
+// into the window's path area behind a focal table that stands there.
+template <bool EPS, bool BG, int TIERS, bool TH = false>
 DEVI bool compactAttempt(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t* arenaSlot, const Ctx& c, DevResult& res,
-                         uint16_t* outPath, SState& s, int& rc) {
+                         uint16_t* outPath, SState& s, int& rc, const uint16_t* heur = nullptr) {
+  static_assert(!TH || (!BG && TIERS == kTiersAll), "the table form exists for the mixed kernels' narrow tier");
   typedef typename std::conditional<TIERS == kTiersHeavy, ct::Wide, ct::Narrow>::type Geo;
   // the wide geometry: as many time steps as the arena slot's node area has room for (cameFrom table + bitmap), in
   // chunks of 64, up to the job's horizon
@@ -347,7 +350,8 @@ DEVI bool compactAttempt(const LaunchParams& P, const DevJob& J, uint8_t* smem, 
   }
   const bool compactOk = !(TIERS == kTiersAll && (J.ctx_flags & kCtxHeavy) != 0) && P.lds_nodes != 0 && c.dimx <= 32u &&
                          c.dimy <= 32u && c.nAgentsPad <= 128u && c.nEc <= 64u && geoRows >= 64u &&
-                         compactFits<Geo>(P.arena_nodes, geoRows, BG);
+                         compactFits<Geo>(P.arena_nodes, geoRows, BG) &&
+                         (!TH || P.lds_paths_bytes >= 2048u + (EPS && c.pathsLds != nullptr ? c.tPad * c.nAgentsPad * 2u : 0u));
   bool done = false;
   if (compactOk) {
     ct::CJob cj = baseCJob<Geo>(P, J, arenaSlot, outPath, geoRows);
@@ -363,13 +367,19 @@ DEVI bool compactAttempt(const LaunchParams& P, const DevJob& J, uint8_t* smem, 
     }
     cj.vc = (uint64_t)c.vc; cj.ec = (uint64_t)c.ec;
     cj.pathsG = (uint64_t)c.paths;
+    if constexpr (TH) cj.bitsG = (uint64_t)heur;  // (free in a BG = false job)
     putCJob(smem, cj);
     const bool tableInLds = !EPS || c.nAgentsPad == 0u || c.pathsLds != nullptr;
 #ifndef MRP_LL_TRACE  // (the trace build uses prof[] for its phase counters)
     const uint64_t tl0 = __builtin_amdgcn_s_memrealtime();
 #endif
     int32_t crc;
-    if constexpr (TIERS == kTiersHeavy)
+    if constexpr (TH && !EPS)
+      crc = ct::compactSearch<false, true, false, ct::Narrow, true>((wv::Lds)smem);
+    else if constexpr (TH)
+      crc = tableInLds ? ct::compactSearch<true, true, false, ct::Narrow, true>((wv::Lds)smem)
+                       : ct::compactSearch<true, false, false, ct::Narrow, true>((wv::Lds)smem);
+    else if constexpr (TIERS == kTiersHeavy)
       crc = ct::compactSearch<EPS, false, BG, ct::Wide>((wv::Lds)smem);
     else
       crc = tableInLds ? ct::compactSearch<EPS, true, BG>((wv::Lds)smem) : ct::compactSearch<EPS, false, BG>((wv::Lds)smem);
@@ -404,9 +414,10 @@ DEVI bool compactAttempt(const LaunchParams& P, const DevJob& J, uint8_t* smem, 
 
 // runJob's third phase, the arena tier: the search from the start with its state in the arena slot (cutArena) and the heaps'
 // top levels in the LDS window.  Returns runSearch's code.
-template <bool EPS, bool BG, int TIERS>
+// TH (runJobTableH): the searches read h from the shortest-path table `heur` (ll_arena_search.h).
+template <bool EPS, bool BG, int TIERS, bool TH = false>
 DEVI int arenaAttempt(const LaunchParams& P, uint8_t* smem, uint8_t* arenaSlot, const Ctx& c, DevResult& res, uint16_t* outPath,
-                      SState& s) {
+                      SState& s, const uint16_t* heur = nullptr, uint32_t heurStride = 0) {
   typedef typename std::conditional<TIERS == kTiersHeavy, ct::Wide, ct::Narrow>::type Geo;
   int rc;
   // HBM tier view of this workgroup's arena slot
@@ -438,7 +449,12 @@ DEVI int arenaAttempt(const LaunchParams& P, uint8_t* smem, uint8_t* arenaSlot, 
   Mem<TierHybXy> ghx = viewAs<TierHybXy>(gh);
   res.tier = 1;
   __syncthreads();  // previous job's / the compact attempt's LDS accesses are done
-  if (xyEntries)
+  if constexpr (TH) {
+    if (xyEntries)
+      initSearch<TierHybXy, EPS, true>(ghx, s, c, heur, heurStride);
+    else
+      initSearch<TierHyb, EPS, true>(gh, s, c, heur, heurStride);
+  } else if (xyEntries)
     initSearch<TierHybXy, EPS>(ghx, s, c);
   else
     initSearch<TierHyb, EPS>(gh, s, c);
@@ -446,7 +462,12 @@ DEVI int arenaAttempt(const LaunchParams& P, uint8_t* smem, uint8_t* arenaSlot, 
 #ifndef MRP_LL_TRACE
   const uint64_t th0 = __builtin_amdgcn_s_memrealtime();
 #endif
-  if (xyEntries)
+  if constexpr (TH) {
+    if (xyEntries)
+      rc = runSearch<TierHybXy, EPS, true>(ghx, s, c, res, outPath, heur, heurStride);
+    else
+      rc = runSearch<TierHyb, EPS, true>(gh, s, c, res, outPath, heur, heurStride);
+  } else if (xyEntries)
     rc = runSearch<TierHybXy, EPS>(ghx, s, c, res, outPath);
   else
     rc = runSearch<TierHyb, EPS>(gh, s, c, res, outPath);
@@ -496,6 +517,74 @@ DEVI bool runJob(const LaunchParams& P, const DevJob& J, uint8_t* smem, uint8_t*
   res.expanded = s.expansions;
   res.nodes_created = s.nNodes;
   return false;
+}
+
+// One CBS / ECBS job with MRP_LL_JOB_TABLE_H (ll_device.h kCtxTableH): runJob's staging, then the arena tier with h read from
+// the goal's shortest-path table in the maps buffer — rows of 32 halfwords on maps up to 32 x 32, of dimx beyond
+// (host/ll_pack.h heurStride).  The table belongs to the job's map (the packer checked), so every cell of the map has a
+// halfword in it; what the halfwords SAY is the caller's: a value that does not fit f's field ends the job
+// ST_CAP_HORIZON.  A start the table calls unreachable is answered at once: ST_NO_SOLUTION, nothing expanded.
+// A real function with plain values for arguments (as runJobTaEps is, ll_ta.h): its own register allocation, and the mixed
+// kernels keep theirs.  The job is read where the kernel staged it; status, cost, fmin, n_states, expanded, nodes_created and
+// tier go to `out`.  The arguments arrive in vector registers and are made wave-uniform here.
+template <bool EPS>
+__device__ __attribute__((noinline)) void runJobTableH(const DevJob* Jp, DevResult* out, uint8_t* smem, uint8_t* arenaSlot,
+                                                       const uint32_t* maps, const uint32_t* consHost, const uint16_t* pathsHost,
+                                                       uint32_t scratchOff, uint32_t outStride, uint32_t arenaNodes,
+                                                       uint32_t arenaRows, uint32_t arenaRowWords, uint32_t arenaPathsBytes,
+                                                       uint32_t ldsNodes, uint32_t ldsPathsBytes) {
+  LaunchParams P = {};  // what the staging and the arena tier read of the launch
+  P.maps = (const uint32_t*)rfl64((uint64_t)maps);
+  P.cons = (const uint32_t*)rfl64((uint64_t)consHost);
+  P.paths = (const uint16_t*)rfl64((uint64_t)pathsHost);
+  P.arena_scratch_off = rfl(scratchOff); P.out_stride = rfl(outStride);
+  P.arena_nodes = rfl(arenaNodes); P.arena_rows = rfl(arenaRows); P.arena_row_words = rfl(arenaRowWords);
+  P.arena_paths_bytes = rfl(arenaPathsBytes);
+  P.lds_nodes = rfl(ldsNodes); P.lds_paths_bytes = rfl(ldsPathsBytes);
+  smem = (uint8_t*)rfl64((uint64_t)smem);
+  arenaSlot = (uint8_t*)rfl64((uint64_t)arenaSlot);
+  DevJob J;  // a wave-uniform copy of the staged descriptor's words
+  for (uint32_t q = 0; q < sizeof(DevJob) / 4; ++q) ((uint32_t*)&J)[q] = rfl(((const uint32_t*)Jp)[q]);
+  J.ctx_flags &= ~kCtxById;  // (the packer refuses path_ids with this flag; the path store is not passed in)
+  DevResult res = {};
+  Ctx c;
+  fillCtx(c, J, P.maps, nullptr);
+  if (!EPS) { c.nAgentsPad = 0; c.tPad = 0; }
+  uint16_t* outPath = slot::outPath(arenaSlot, P.arena_scratch_off, P.out_stride);
+  stageConstraints(P.cons, J.vc_off, c.nVc, c.nEc, slot::consCopy(arenaSlot, P.arena_scratch_off, P.out_stride), c.vc, c.ec);
+  {  // the focal table goes behind the window only where the 2 KiB heuristic table still fits behind it
+    LaunchParams Pst = P;
+    Pst.lds_paths_bytes = P.lds_paths_bytes >= 2048u ? P.lds_paths_bytes - 2048u : 0u;
+    stageFocalTable<kTiersAll>(Pst, J, smem + ct::Narrow::windowBytes(false), slot::pathsCopy(arenaSlot, P.arena_scratch_off, P.out_stride), c);
+  }
+  __syncthreads();
+  const uint16_t* heur = (const uint16_t*)(P.maps + J.heur_off);
+  const uint32_t heurStride = (c.dimx <= 32u && c.dimy <= 32u) ? 32u : c.dimx;
+  const bool startInMap = c.sx < c.dimx && c.sy < c.dimy;
+  const uint32_t h0 = startInMap ? rfl(heur[c.sy * heurStride + c.sx]) : 0u;
+  int rc = ST_BAD;
+  res.tier = 1;
+  if (!startInMap) {
+    rc = ST_BAD;  // (the host packer refuses such a job)
+  } else if (h0 == 0xFFFFu) {
+    rc = ST_NO_SOLUTION;  // the start cannot reach the goal at all: nothing to expand
+  } else if (h0 > kFMax - 2u) {
+    rc = ST_CAP_HORIZON;
+  } else {
+    SState s;
+    res.tier = 0;
+    // the narrow LDS tier first (maps up to 32 x 32, room for the table in the window's path area); a search that outgrows
+    // it — open list, time steps, focalH, and here also h(start) or a successor's f beyond 124 — is run again by the arena tier
+    if (!compactAttempt<EPS, false, kTiersAll, true>(P, J, smem, arenaSlot, c, res, outPath, s, rc, heur))
+      rc = arenaAttempt<EPS, false, kTiersAll, true>(P, smem, arenaSlot, c, res, outPath, s, heur, heurStride);
+    if (rc == RUN_MIGRATE_NODES) rc = ST_CAP_NODES;
+    if (rc == RUN_MIGRATE_ROWS) rc = ST_CAP_HORIZON;
+    res.expanded = s.expansions;
+    res.nodes_created = s.nNodes;
+  }
+  out->status = rc; out->cost = res.cost; out->fmin = res.fmin; out->n_states = res.n_states;
+  out->expanded = res.expanded; out->nodes_created = res.nodes_created; out->tier = res.tier;
+  for (int q = 0; q < 8; ++q) out->prof[q] = res.prof[q];
 }
 
 // A search's path, `len` states at outPath, becomes visible: to the host at hostDst, then (f2) as cells in the device path

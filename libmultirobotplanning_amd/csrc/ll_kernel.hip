@@ -161,7 +161,23 @@ DEVI bool processJob(const LaunchParams& P, const DevJob* jobSrc, DevResult* res
       algo = 0xFFFFFFFFu;  // no search below takes it
   }
   if constexpr (KIND == 0) {
-    if (algo == 1)
+    // MRP_LL_JOB_TABLE_H: the arena tier with h from the goal's table.  (Its algo word is kAlgoTableH | algo: the
+    // one-algorithm kernels below take no such job and leave it ST_BAD without a test of their own.)
+    if ((algo & ~1u) == kAlgoTableH && (rfl(J.ctx_flags) & kCtxTableH)) {
+      if (algo & 1u)
+        runJobTableH<true>(&jobS, &resS, smem, arenaSlot, P.maps, P.cons, P.paths, P.arena_scratch_off, P.out_stride, P.arena_nodes,
+                           P.arena_rows, P.arena_row_words, P.arena_paths_bytes, P.lds_nodes, P.lds_paths_bytes);
+      else
+        runJobTableH<false>(&jobS, &resS, smem, arenaSlot, P.maps, P.cons, P.paths, P.arena_scratch_off, P.out_stride, P.arena_nodes,
+                            P.arena_rows, P.arena_row_words, P.arena_paths_bytes, P.lds_nodes, P.lds_paths_bytes);
+      __syncthreads();
+      res.status = rfli(resS.status); res.cost = rfli(resS.cost); res.fmin = rfli(resS.fmin);
+      res.n_states = rfli(resS.n_states);
+      res.expanded = (int64_t)rfl64((uint64_t)resS.expanded);
+      res.nodes_created = rfl(resS.nodes_created);
+      res.tier = rfl(resS.tier);
+      for (int q = 0; q < 8; ++q) res.prof[q] = rfl(resS.prof[q]);  // the tiers' ticks and expansions (compactAttempt, arenaAttempt)
+    } else if (algo == 1)
       runJob<true, false, kTiersAll>(P, J, smem, arenaSlot, res, outPath);
     else if (algo == 3)
       runJobTA(P, J, smem, arenaSlot, res, outPath);
@@ -229,6 +245,16 @@ static_assert(sizeof(DevJob) + sizeof(DevResult) <= ct::oJob, "control block of 
     __VA_ARGS__(P, smem, jobS, resS);                                                    \
   }
 #define MRP_LL_WINDOW_KERNEL(NAME, ...) MRP_LL_WINDOW_KERNEL_PRE(NAME, (void)0, __VA_ARGS__)
+// The two mixed kernels are held to three waves per SIMD (168 registers): their own need is 167 vector registers, and the
+// scalar registers saved around the calls of the searches that are real functions (runJobTaEps, runTaEpsLds, runJobTableH) took
+// one accumulation register beyond that — a fourth of the kernel's residency for a register that holds spilled scalars.
+#define MRP_LL_MIXED_KERNEL(NAME, ...)                                                                          \
+  extern "C" __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3))) NAME(LaunchParams Parg) { \
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];                                              \
+    MRP_LL_WINDOW_BLOCKS(smem, jobS, resS);                                                                     \
+    const LaunchParams& P = Parg;                                                                               \
+    __VA_ARGS__(P, smem, jobS, resS);                                                                           \
+  }
 // The A*-epsilon-only kernels stay at two waves per SIMD, eight windows per CU: they name vector register 175 once, at
 // their entry, where nothing is live, so their allocation is 176 registers — in the compiler's report, in the code object
 // and in what the runtime grants alike.  (Their own need is 155 since the goal branch of compactSearch, with its 32 staging
@@ -253,7 +279,7 @@ DEVI void batchLoop(const LaunchParams& P, uint8_t* smem, DevJob& jobS, DevResul
   DBG(P, 4, 1);
 }
 
-MRP_LL_WINDOW_KERNEL(mrp_ll_search_kernel, batchLoop<0>)  // mixed batches
+MRP_LL_MIXED_KERNEL(mrp_ll_search_kernel, batchLoop<0>)  // mixed batches
 MRP_LL_WINDOW_KERNEL_PRE(mrp_ll_ecbs_search_kernel, MRP_LL_TWO_WAVES, batchLoop<1>)  // A*-epsilon jobs only
 MRP_LL_WINDOW_KERNEL(mrp_ll_cbs_search_kernel, batchLoop<2>)  // A* jobs only
 // ll_ta_root.h's one runner, four times (the macro is variadic: a template-id with a comma passes as it stands)
@@ -462,7 +488,7 @@ DEVI void residentLoop(const LaunchParams& P, uint8_t* smem, DevJob& jobS, DevRe
   reportTicks(P, 0, busyTicks, idleTicks);
 }
 
-MRP_LL_WINDOW_KERNEL(mrp_ll_persistent_kernel, residentLoop<false, 0>)  // mixed sessions
+MRP_LL_MIXED_KERNEL(mrp_ll_persistent_kernel, residentLoop<false, 0>)  // mixed sessions
 MRP_LL_WINDOW_KERNEL_PRE(mrp_ll_ecbs_persistent_kernel, MRP_LL_TWO_WAVES, residentLoop<false, 1>)  // A*-epsilon only
 // The front / heavy pair of an A*-epsilon session (ll_device.h heavy_q).  Front workgroups are the resident loop above
 // with the narrow compact tier alone — no arena-tier code, hence a smaller register allocation; heavy workgroups wait on

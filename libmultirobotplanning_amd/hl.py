@@ -63,7 +63,8 @@ EXPORTS = ["mrp_hl_solver_prioritized_sipp", "mrp_hl_solver_preload", "mrp_hl_so
            "mrp_hl_preloaded_free", "mrp_hl_solve_batch", "mrp_hl_solver_create", "mrp_hl_solver_destroy", "mrp_hl_solver_solve",
            "mrp_hl_solver_ll_stats", "mrp_hl_solver_last_error", "mrp_hl_generate_instance", "mrp_hl_generate_instances", "mrp_hl_astar_grid2d",
            "mrp_hl_ct_create", "mrp_hl_ct_destroy", "mrp_hl_ct_n_requests", "mrp_hl_ct_request", "mrp_hl_ct_deliver",
-           "mrp_hl_ct_done", "mrp_hl_ct_solution", "mrp_hl_solve_cbs_ta_batch", "mrp_hl_solve_ecbs_ta_batch"]
+           "mrp_hl_ct_done", "mrp_hl_ct_solution", "mrp_hl_solve_cbs_ta_batch", "mrp_hl_solve_ecbs_ta_batch",
+           "mrp_hl_solve_batch_table_h"]
 
 _lib = None
 
@@ -156,6 +157,9 @@ def load_library(path: Optional[str] = None):
         lib.mrp_hl_generate_instances.restype = ctypes.c_int
         lib.mrp_hl_generate_instances.argtypes = [ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                   ctypes.c_int32, ctypes.c_int32, I32P, I32P, I32P]
+        if hasattr(lib, "mrp_hl_solve_batch_table_h"):  # (a test build against an older engine stand-in may lack it)
+            lib.mrp_hl_solve_batch_table_h.restype = ctypes.c_int
+            lib.mrp_hl_solve_batch_table_h.argtypes = lib.mrp_hl_solve_batch.argtypes
         if hasattr(lib, "mrp_hl_solve_cbs_ta_batch"):  # (a test build of mrp_hl.cpp alone has no task-assignment driver)
             lib.mrp_hl_solve_cbs_ta_batch.restype = ctypes.c_int
             lib.mrp_hl_solve_cbs_ta_batch.argtypes = [ctypes.c_int32, ctypes.POINTER(mrp_hl_ta_options), ctypes.c_int32,
@@ -569,6 +573,51 @@ class ConflictTree:
         if sol.status == SOLVED:
             rec["paths"] = [pxy[a, :plen[a]].tolist() for a in range(self.n_agents)]
         return rec
+
+
+def solve_batch_table_h(instances: Sequence[Dict], algo: int = ECBS, w: float = 1.3, max_ll_expansions: int = -1,
+                        max_hl_expansions: int = -1, n_threads: int = 0, device: int = 0, want_paths: bool = True,
+                        path_cap: int = 512):
+    """mrp_hl_solve_batch_table_h: CBS / ECBS for a batch of instances (dicts with dimx, dimy, obstacles, starts, goals) with
+    the shortest-path table of every agent's goal as the low-level heuristic (MRP_LL_JOB_TABLE_H) instead of the Manhattan
+    distance.  One call: engines, maps and tables are made inside it, before the timed region; always the rounds schedule.
+    Returns (results, stats) as BatchSolver.solve does."""
+    lib = load_library()
+    n = len(instances)
+    cin = (mrp_hl_instance * max(n, 1))()
+    csol = (mrp_hl_solution * max(n, 1))()
+    keep, plen, pxy = [], [], []
+    for i in range(n):
+        inst = instances[i]
+        ob = np.ascontiguousarray(np.asarray(inst["obstacles"], dtype=np.int32).reshape(-1, 2))
+        st = np.ascontiguousarray(np.asarray(inst["starts"], dtype=np.int32).reshape(-1, 2))
+        go = np.ascontiguousarray(np.asarray(inst["goals"], dtype=np.int32).reshape(-1, 2))
+        keep.append((ob, st, go))
+        c = cin[i]
+        c.dimx, c.dimy = inst["dimx"], inst["dimy"]
+        c.n_obstacles, c.obstacles_xy = len(ob), ob.ctypes.data_as(I32P)
+        c.n_agents, c.starts_xy, c.goals_xy = len(st), st.ctypes.data_as(I32P), go.ctypes.data_as(I32P)
+        if want_paths:
+            a = np.zeros(len(st), dtype=np.int32)
+            b = np.zeros((len(st), path_cap, 2), dtype=np.int32)
+            plen.append(a)
+            pxy.append(b)
+            csol[i].path_len, csol[i].paths_xy, csol[i].path_cap = a.ctypes.data_as(I32P), b.ctypes.data_as(I32P), path_cap
+    opt = mrp_hl_options(algo, w, max_ll_expansions, max_hl_expansions, n_threads, 1)
+    st = mrp_hl_batch_stats()
+    rc = lib.mrp_hl_solve_batch_table_h(device, ctypes.byref(opt), n, cin, csol, ctypes.byref(st))
+    if rc != 0:
+        raise RuntimeError(f"mrp_hl_solve_batch_table_h failed rc={rc}")
+    out = []
+    for i in range(n):
+        s = csol[i]
+        rec = dict(status=s.status, cost=s.cost, makespan=s.makespan, hl_expanded=s.high_level_expanded,
+                   ll_expanded=s.low_level_expanded, ll_searches=s.n_ll_searches, schedule_digest=s.schedule_digest)
+        if want_paths and s.status == SOLVED:
+            assert int(plen[i].max(initial=0)) <= path_cap
+            rec["paths"] = [pxy[i][a, :plen[i][a]].tolist() for a in range(len(plen[i]))]
+        out.append(rec)
+    return out, {f: getattr(st, f) for f, _ in mrp_hl_batch_stats._fields_}
 
 
 def _solve_ta_batch(call, name, instances, opt, device, path_cap):

@@ -20,6 +20,7 @@ JOB_STORE_RESULT, JOB_NO_GOAL, JOB_ROOT_CHAIN, JOB_HEAVY = 1, 2, 4, 8  # mrp_ll_
 JOB_SCAN_CONFLICTS = 16  # mrp_ll_job.flags: mrp_ll_submit_scan also returns the conflicts of the node the job completes
 JOB_CONSTRAINT_SET = 32  # mrp_ll_job.flags: mrp_ll_submit_sets' sets[i] names the agent's set in the device constraint store
 JOB_SCAN_FROM_PARENT = 64  # mrp_ll_job.flags: mrp_ll_submit_node's bases[i] holds what the parent node's scan established
+JOB_TABLE_H = 256        # mrp_ll_job.flags: ASTAR / ASTAR_EPS take h from the shortest-path table heuristic_id (not Manhattan)
 JOB_TRY_LDS = 128        # mrp_ll_job.flags: an ASTAR_EPS_TA search starts in its LDS tier (a hint; only LLResult.tier depends on it)
 SCAN_UNTOUCHED = -2      # search_batch_scan: what every field of an entry the engine did not write still holds
 OK, NO_SOLUTION, CAP_EXPANSIONS, CAP_NODES, CAP_HORIZON, BAD_JOB, PATH_TRUNCATED, CAP_FOCAL = range(8)
@@ -260,6 +261,7 @@ class LLJob:
     result_path_id: int = -1                  # f2: path-store slot that also receives the result path
     heuristic_id: int = -1                    # ASTAR_TA / ASTAR_EPS_TA: LowLevelEngine.upload_heuristic of the goal cell
     heavy: bool = False                       # MRP_LL_JOB_HEAVY: the search is known to outgrow the LDS tier (a hint)
+    table_h: bool = False                     # MRP_LL_JOB_TABLE_H: ASTAR / ASTAR_EPS with h = table heuristic_id of the job's own goal
     try_lds: bool = False                     # MRP_LL_JOB_TRY_LDS: ASTAR_EPS_TA starts in its LDS tier (a hint; other algorithms ignore it)
     scan_conflicts: bool = False              # MRP_LL_JOB_SCAN_CONFLICTS: the node's conflicts come back too (search_batch_scan)
     # device constraint store (constraint_store_reserve): the agent's set at the parent node by its slot, and the slot that
@@ -404,7 +406,8 @@ class LowLevelEngine:
             cj.flags = (JOB_STORE_RESULT if j.result_path_id >= 0 else 0) | (JOB_NO_GOAL if j.goal is None else 0) | \
                 (JOB_HEAVY if j.heavy else 0) | (JOB_SCAN_CONFLICTS if j.scan_conflicts else 0) | \
                 (JOB_CONSTRAINT_SET if (j.base_set_id >= 0 or j.result_set_id >= 0) else 0) | \
-                (JOB_SCAN_FROM_PARENT if j.scan_base is not None else 0) | (JOB_TRY_LDS if j.try_lds else 0)
+                (JOB_SCAN_FROM_PARENT if j.scan_base is not None else 0) | (JOB_TRY_LDS if j.try_lds else 0) | \
+                (JOB_TABLE_H if j.table_h else 0)
             cj.heuristic_id = j.heuristic_id
             if j.path_ids is not None:
                 ids = np.ascontiguousarray(np.asarray(j.path_ids, dtype=np.int32))
