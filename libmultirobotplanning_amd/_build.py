@@ -28,7 +28,7 @@ TARGETS = {
                                "host/ll_session.h", "host/ll_session_jobs.h", "host/ll_submit.h", "../../include/mrp_ll.h"],
                          extra=[]),
     "libmrp_hl.so": dict(srcs=["hl/mrp_hl.cpp", "hl/mrp_hl_ta.cpp", "hl/mrp_hl_ecbs_ta.cpp"],
-                         deps=["hl/exact_heap.hpp", "hl/cbs_ta_tree.hpp", "hl/ecbs_ta_tree.hpp", "hl/ta_batch_setup.hpp", "hl/grid_mapf.hpp", "hl/ct_solver.hpp",
+                         deps=["hl/exact_heap.hpp", "hl/ta_tree_base.hpp", "hl/cbs_ta_tree.hpp", "hl/ecbs_ta_tree.hpp", "hl/ta_batch_setup.hpp", "hl/ta_rounds.hpp", "hl/grid_mapf.hpp", "hl/ct_solver.hpp",
                                                        "hl/ct_session.hpp", "hl/grid2d_astar.hpp", "hl/instance_io.hpp",
                                                        "hl/solve_knobs.hpp", "hl/launch_plan.hpp", "hl/rounds_driver.hpp",
                                                        "hl/sipp_drivers.hpp", "hl/ct_stepped.hpp",

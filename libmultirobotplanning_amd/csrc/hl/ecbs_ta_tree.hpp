@@ -1,8 +1,8 @@
 // One ECBS-TA conflict tree as a resumable state machine (ecbs_ta.hpp:94-352 as example/ecbs_ta.cpp compiles it —
 // REBUILT_FOCAL_LIST, STYLE_MINROOT, Cost = int — over that file's Environment), cut at the three things a tree asks of the
 // engine: the next task assignment, a new root (whole, or its next search), the two searches of an expanded node's children.  Pure host
-// logic: no engine call, no HIP; csrc/hl/mrp_hl_ecbs_ta.cpp drives many of these in rounds.  Paths, constraints, conflicts and
-// the conflict scan are cbs_ta_tree.hpp's (example/ecbs_ta.cpp:440-511 equals example/cbs_ta.cpp there).
+// logic: no engine call, no HIP; csrc/hl/mrp_hl_ecbs_ta.cpp drives many of these in the rounds of hl/ta_rounds.hpp.  Paths,
+// constraints, conflicts, the conflict scan and the tree's base are hl/ta_tree_base.hpp's.
 //   open list          d_ary_heap ordered by cost alone (:387-391), replayed by hl/exact_heap.hpp
 //   focal list         rebuilt before every expansion (:160-179): the open list in ordered_begin() order up to the first node with
 //                      (float)cost > nextRootNodeCost; ordered by focalHeuristic, then cost (:420-428)
@@ -14,15 +14,14 @@
 // What the reference leaves undefined is defined in include/mrp_hl.h: an empty open list at :302 asks for a new root, a still
 // empty one at :344 ends the tree MRP_HL_NO_SOLUTION, an empty focal list at :238 ends it MRP_HL_LL_ERROR.
 #pragma once
-#include "cbs_ta_tree.hpp"
+#include "exact_heap.hpp"
+#include "ta_tree_base.hpp"
 
 namespace mrp_hl {
 namespace ecbs_ta {
 
 using ta::Conflict;
 using ta::Cons;
-using ta::ConsP;
-using ta::Path;
 using ta::PathP;
 
 // focalHeuristic, ecbs_ta.cpp:347-382: every vertex and every edge pair of every step t < (longest state count) - 1
@@ -47,29 +46,14 @@ inline int32_t countConflicts(const std::vector<PathP>& sol) {
 
 inline int32_t rootCostBound(int64_t lb, float w) { return static_cast<int32_t>(static_cast<float>(lb) * w); }
 
-struct Node {  // ecbs_ta.hpp:372-391
-  std::vector<PathP> sol;
-  std::vector<int32_t> fmin;    // per agent: PlanResult::fmin of its path
-  std::vector<ConsP> cons;
-  std::vector<int32_t> taskOf;  // per agent: task index, -1 = none
-  int64_t cost = 0, lb = 0;
+struct Node : ta::Node {  // ecbs_ta.hpp:372-391
+  std::vector<int32_t> fmin;  // per agent: PlanResult::fmin of its path
+  int64_t lb = 0;
   int32_t focalH = 0;
-  int32_t id = 0;
-  bool isRoot = false;
-  Conflict conflict;  // getFirstConflict of `sol`, found when the node was made
 };
 
-struct Tree {
-  enum Status : int32_t { kRunning = -1 };
-  // the instance
-  int32_t nAgents = 0, mapId = -1;
+struct Tree : ta::TreeBase {
   float w = 1.0f;
-  std::vector<int32_t> starts;           // [n][2]
-  std::vector<int32_t> taskXY, taskHeur; // the distinct potential goals in order of first appearance; their tables
-  int32_t maskWords = 1;                 // max(1, ceil(tasks / 64))
-  std::vector<uint64_t> allowed;         // [nAgents][maskWords] the tasks an agent may take, as mrp_ll_assign_problem_w's masks
-  // the search
-  int32_t status = kRunning;
   std::vector<Node> nodes;
   struct Worse {
     const std::vector<Node>* nodes;
@@ -86,32 +70,16 @@ struct Tree {
   };
   ExactHeap<Worse> open{Worse{&nodes}};
   int32_t nextRootNodeCost = 0;
-  int32_t nextId = 1;
-  int64_t hlExpanded = 0, llExpanded = 0, numTaskAssignments = 0;
-  int32_t nSearches = 0, nRootSearches = 0, nRoots = 0, rootConflicts = 0, solution = -1;
+  int32_t nextId = 1, solution = -1;
   bool firstRoot = true;
-  // what the tree asks of this round (at most one of the three)
-  bool wantAssignment = true, wantRoot = false, wantChildren = false;
-  std::vector<int32_t> rootTasks;        // the assignment the pending root plans
+  // the pending root (a tree asks at most one of the base's three things of a round)
   std::vector<PathP> rootPaths;          // its paths so far: agents 0 .. rootAgent - 1, the rest null
   std::vector<int32_t> rootFmin;
   int32_t rootAgent = 0;                 // the agent whose search is pending
-  int32_t popped = -1;                   // the node whose children are pending
-  int32_t childAgent[2] = {0, 0};
-  ConsP childCons[2];
 
-  Tree() = default;
-  Tree(const Tree&) = delete;
-
-  bool running() const { return status == kRunning; }
-  void end(int32_t st) {
-    status = st;
-    wantAssignment = wantRoot = wantChildren = false;
-  }
-  // nextTaskAssignment (ecbs_ta.cpp:513-527), first half: is the series asked at all?
-  bool assignmentAllowed(int64_t maxTaskAssignments) const { return !(numTaskAssignments > maxTaskAssignments); }
-  // ... second half: `taskOf` == nullptr or without any task: the empty assignment.  The FIRST root is planned even then,
-  // every agent without a task (ecbs_ta.hpp:104, :117-137 — unlike cbs_ta.hpp:105-113); a later one is not (:309).
+  // nextTaskAssignment (ecbs_ta.cpp:513-527), second half: `taskOf` == nullptr or without any task: the empty assignment.
+  // The FIRST root is planned even then, every agent without a task (ecbs_ta.hpp:104, :117-137 — unlike cbs_ta.hpp:105-113);
+  // a later one is not (:309).
   void gotAssignment(const int32_t* taskOf) {
     wantAssignment = false;
     bool any = false;
@@ -247,65 +215,11 @@ struct Tree {
       return;
     }
     if (P.isRoot) rootConflicts += 1;
-    const Conflict& c = P.conflict;
-    childAgent[0] = c.agent1;
-    childAgent[1] = c.agent2;
-    for (int k = 0; k < 2; ++k) {
-      auto nc = std::make_shared<Cons>(*P.cons[childAgent[k]]);
-      if (c.type == 0) {
-        nc->vc.insert(nc->vc.end(), {c.time, c.x1, c.y1});
-      } else if (k == 0) {
-        nc->ec.insert(nc->ec.end(), {c.time, c.x1, c.y1, c.x2, c.y2});
-      } else {
-        nc->ec.insert(nc->ec.end(), {c.time, c.x2, c.y2, c.x1, c.y1});
-      }
-      childCons[k] = nc;
-    }
+    constrainChildren(P.conflict, P.cons);
     wantChildren = true;
   }
 
-  void write(mrp_hl_ta_solution& s) const {
-    s.status = status;
-    s.n_ll_searches = nSearches;
-    s.cost = 0;
-    s.makespan = 0;
-    s.high_level_expanded = hlExpanded;
-    s.low_level_expanded = llExpanded;
-    s.num_task_assignments = numTaskAssignments;
-    s.n_roots = nRoots;
-    s.n_root_searches = nRootSearches;
-    s.root_conflicts = rootConflicts;
-    s.schedule_digest = 0;
-    if (s.path_len)
-      for (int a = 0; a < nAgents; ++a) s.path_len[a] = 0;
-    if (s.task_xy)
-      for (int a = 0; a < 2 * nAgents; ++a) s.task_xy[a] = -1;
-    if (status != MRP_HL_SOLVED) return;
-    const Node& n = nodes[solution];
-    ta::Fnv d;
-    for (int a = 0; a < nAgents; ++a) {
-      const Path& p = *n.sol[a];
-      s.cost += p.cost;
-      s.makespan = p.cost > s.makespan ? p.cost : s.makespan;
-      for (int k = 0; k < p.len(); ++k) {
-        d.byte(static_cast<uint32_t>(p.xy[2 * k]));
-        d.byte(static_cast<uint32_t>(p.xy[2 * k + 1]));
-        if (s.paths_xyt && k < s.path_cap) {
-          int32_t* q = s.paths_xyt + (static_cast<size_t>(a) * s.path_cap + k) * 3;
-          q[0] = p.xy[2 * k];
-          q[1] = p.xy[2 * k + 1];
-          q[2] = p.g[k];
-        }
-      }
-      d.byte(0xFFu);
-      if (s.path_len) s.path_len[a] = p.len();
-      if (s.task_xy && n.taskOf[a] >= 0) {
-        s.task_xy[2 * a] = taskXY[2 * n.taskOf[a]];
-        s.task_xy[2 * a + 1] = taskXY[2 * n.taskOf[a] + 1];
-      }
-    }
-    s.schedule_digest = d.h;
-  }
+  void write(mrp_hl_ta_solution& s) const { TreeBase::write(s, status == MRP_HL_SOLVED ? &nodes[solution] : nullptr); }
 };
 
 }  // namespace ecbs_ta

@@ -7,6 +7,8 @@
 // erase = swap up to the root unconditionally, then pop; ordered iteration = best-first traversal driven by a
 // std::priority_queue with the same comparator.
 #pragma once
+#include <stddef.h>
+
 #include <cstdint>
 #include <queue>
 #include <vector>

@@ -1,6 +1,7 @@
-// What the two task-assignment drivers (csrc/hl/mrp_hl_ta.cpp: CBS-TA, csrc/hl/mrp_hl_ecbs_ta.cpp: ECBS-TA) share around their
-// trees: the engine context with its assignment series, the caller-side result buffers of a round, a result turned into a
-// tree's path, and the set-up of a batch — maps, tasks, one launch for all shortest-path tables, one for all optima.
+// What the rounds of the two task-assignment solvers (hl/ta_rounds.hpp; csrc/hl/mrp_hl_ta.cpp: CBS-TA, csrc/hl/mrp_hl_ecbs_ta.cpp:
+// ECBS-TA) need around their trees: the engine context with its assignment series, the caller-side result buffers of a round,
+// a result turned into a tree's path, and the set-up of a batch — maps, tasks, one launch for all shortest-path tables, one
+// for all optima.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -9,7 +10,7 @@
 #include <vector>
 
 #include "../../../include/mrp_hl.h"
-#include "cbs_ta_tree.hpp"
+#include "ta_tree_base.hpp"
 
 // The engine's wide entry points (up to 256 agents and tasks).  Weak references, as mrp_hl_ecbs_ta.cpp's to the stored root
 // call: an engine library without them still loads; an instance beyond 64 agents or tasks then ends MRP_HL_LL_ERROR, and a
@@ -126,13 +127,14 @@ struct Engine {
 constexpr int32_t kNarrowLimit = 64;   // agents and tasks of mrp_ll_assign_series_create and of the narrow root calls
 constexpr int32_t kWideLimit = 256;    // ... of mrp_ll_assign_series_create_w and of the _w root calls
 
-// Fills trees[k] (TreeT: ta::Tree or ecbs_ta::Tree) from inst[k]; an instance beyond the limits — 256 agents or 256 distinct
-// potential goals, 64 of each with an engine that has no mrp_ll_assign_series_create_w — ends MRP_HL_LL_ERROR.
+// Makes trees[k] (TreeT: ta::Tree or ecbs_ta::Tree) and fills its base from inst[k]; an instance beyond the limits — 256
+// agents or 256 distinct potential goals, 64 of each with an engine that has no mrp_ll_assign_series_create_w — ends
+// MRP_HL_LL_ERROR.
 // The instances within 64 x 64 share ONE mrp_ll_assign_series_create, the others ONE mrp_ll_assign_series_create_w, which is
 // called only when there are such instances.  Returns MRP_LL_SUCCESS or the engine's error.
 template <typename TreeT>
 int setUpBatch(Engine& eng, int32_t n, const mrp_hl_ta_instance* inst, std::vector<std::unique_ptr<TreeT>>& trees) {
-  typedef TreeT Tree;
+  typedef TreeBase Tree;
   int rc = MRP_LL_SUCCESS;
   const int32_t limit = &mrp_ll_assign_series_create_w != nullptr ? kWideLimit : kNarrowLimit;
   // ---- the instances: maps, tasks, one launch for all tables, one for all optima
@@ -141,7 +143,7 @@ int setUpBatch(Engine& eng, int32_t n, const mrp_hl_ta_instance* inst, std::vect
   std::vector<int32_t> tabMap, tabGoal;
   for (int32_t k = 0; k < n; ++k) {
     const mrp_hl_ta_instance& I = inst[k];
-    trees[k].reset(new Tree());
+    trees[k].reset(new TreeT());
     Tree& t = *trees[k];
     t.nAgents = I.n_agents;
     if (I.n_agents < 1 || I.n_agents > limit || !I.starts_xy || !I.goal_first || (I.goal_first[I.n_agents] > 0 && !I.goals_xy) ||
